@@ -12,7 +12,8 @@ index   : synthetic: Bernoulli(p) background bits, p = 1 - exp(
 step    : one pass of the hot path over the rank's whole k-mer batch (+ the RCCL all-reduce of the 3*C
           per-colour counters when N > 1).  N > 1: reads are sharded over ranks, the index is replicated.
 
-Side records of the one JSON line (N = 1 only; never `value`; the line stays under 7 KB):
+A plain run sets up, warms up, times --steps steps and prints the line (headline, roofline of the timed launches, counters digest).
+Side records of the one JSON line, with --full only (N = 1 only; never `value`; the line stays under 7 KB):
   config.codes_input       the same query as 2-bit codes (cid_search_count_codes_dev), 10 steps
   config.producer_ordered  2-bit codes grouped by the 128-byte index line of their first row as a separate pass: search_ms = the
                            search alone, in_step_ms = grouping + search inside one step
@@ -38,6 +39,9 @@ Launch: `python bench.py [--gpus N]` — for N > 1 without a launcher (WORLD_SIZ
         a device (rank r uses device r mod device_count) — how tests/test_gpu_bench_launch.py runs the N > 1 branches on one GPU.
         --emulate-world W (one rank): the same W shards / stripes, searched one after the other by one rank; its `counters`
         digest must equal the W-rank run's.
+        --dump-outputs DIR: rank 0 writes what the last timed step computed as DIR/<name>.npy — hits, n_unique, sum_unique_freq
+        (per colour, float64) and unique_colour_sample (float32) at the k-mer indices unique_colour_sample_index (float64), a fixed
+        seeded sample of 2^20 k-mers; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -146,7 +150,16 @@ def parse_args():
     ap.add_argument("--only", default=None, help="profiling: run just this side record (readid_long) and print it as the JSON line")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch from a separate rocprofv3 --pmc pass (profiles/), if known")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the side records (codes_input, producer_ordered, e2e, rows128, readid, readid_long), "
+                         "the CPU baseline with its bit-exactness check and the clocks under load; a plain run times the headline steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step computed as DIR/<name>.npy (float64 / float32): the per-colour "
+                         "counters and a fixed, seeded sample of the per-k-mer unique colours")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
 
 def make_reads_kmers(dev, seed, n_reads, read_len, k, n_colours, err_rate, return_reads=False, return_codes=False):
@@ -381,6 +394,36 @@ def counters_digest(*tensors):
     return {"sha256": h.hexdigest(), "sums": sums}
 
 
+DUMP_SAMPLE = 1 << 20       # --dump-outputs: per-k-mer outputs are sampled (120 M k-mers x 4 B would be 480 MB); 12 MB with the indices
+DUMP_LIMIT = 64 << 20
+
+
+def per_colour_outputs(hits, n_unique, sum_unique_freq):
+    """the three per-colour counters of a search step (device u64) as float64: exact, every count is far below 2^53"""
+    return {name: t.detach().cpu().numpy().astype(np.float64)
+            for name, t in (("hits", hits), ("n_unique", n_unique), ("sum_unique_freq", sum_unique_freq))}
+
+
+def per_kmer_sample(name, t, n_sample, seed=20240611):
+    """a fixed, seeded sample of a per-k-mer device array: {name_sample: values as float32, name_sample_index: their k-mer indices
+    as float64}; the same k-mer count gives the same indices in every run"""
+    n = t.shape[0]
+    idx = np.arange(n) if n <= n_sample else np.sort(np.random.default_rng(seed).choice(n, n_sample, replace=False))
+    vals = t[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+    return {f"{name}_sample": vals.astype(np.float32), f"{name}_sample_index": idx.astype(np.float64)}
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy"""
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 def workload_key(a):
     """the parameters that decide the counters, as one string: the key of tests/golden/scale_digests.json"""
     if a.placement == "striped":
@@ -505,7 +548,9 @@ def bench_striped(a, json_out, world, rank, device_index, dev, ctx, stream):
     elapsed = time.perf_counter() - t0
     digest = counters_digest(hits, nu, sf)   # the timed steps' result, before the clock pass adds further launches into `hits`
     n_hits = int(hits.sum().item())
-    clocks = clocks_under_load(device_index, lambda: si.search_count_local(kmers, fact, hits)) if rank == 0 else None
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {**per_colour_outputs(hits, nu, sf), **per_kmer_sample("unique_colour", uc, DUMP_SAMPLE)})
+    clocks = clocks_under_load(device_index, lambda: si.search_count_local(kmers, fact, hits)) if rank == 0 and a.full else None
     kern_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
     coll_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
     fin_ms = float(np.mean([e[2].elapsed_time(e[3]) for e in ev]))
@@ -668,7 +713,12 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     final_counters = out.clone()     # the timed steps' result (the clock pass below launches without the reduction)
-    clocks = clocks_under_load(device_index, launch) if rank == 0 else None
+    if a.dump_outputs and rank == 0:    # (the --full records below launch into `out` and `uc` again)
+        dumped = per_colour_outputs(final_counters[:C], final_counters[C:2 * C], final_counters[2 * C:])
+        for i, u in enumerate(ucs):     # one shard, except under --emulate-world
+            dumped.update(per_kmer_sample("unique_colour" + (f"_shard{i}" if len(ucs) > 1 else ""), u, DUMP_SAMPLE // len(ucs)))
+        dump_outputs(a.dump_outputs, dumped)
+    clocks = clocks_under_load(device_index, launch) if rank == 0 and a.full else None
     kern_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
     coll_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
     ranks = per_rank_times(dev, world, kern_ms, coll_ms, elapsed / a.steps * 1e3, K)
@@ -710,7 +760,7 @@ def main():
                                        "traffic_frac": a.traffic_bytes / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS})
         else:
             traffic_fields(result["roofline"], kern_ms, shards[0][0].shape[0], C, m, n, k)
-        if world == 1 and not a.codes and not a.no_variants and not a.emulate_world:
+        if a.full and world == 1 and not a.codes and not a.no_variants and not a.emulate_world:
             # for the record, not the headline: the same query with the k-mers as the 2-bit codes that GPU k-mer counting
             # produces (what `colorid search` feeds the kernel for k <= 32): 8 instead of k input bytes per k-mer
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -754,7 +804,7 @@ def main():
             result["rows128"] = side_rows128(a, dev, ctx, stream, kmers, freq, planted)
             result["readid"] = side_readid(a, dev, ctx, stream, with_oracle=not a.no_cpu_baseline)
             result["readid_long"] = side_readid_long(a, dev, ctx, stream, with_oracle=not a.no_cpu_baseline)
-        if world == 1 and not a.no_cpu_baseline and not a.emulate_world:
+        if a.full and world == 1 and not a.no_cpu_baseline and not a.emulate_world:
             result["cpu_baseline"], result["bit_exact"] = cpu_baseline(a, hx, ptr, kmers, freq, C, n, k, m, rs)
     exit_code = 0
     if result is not None:

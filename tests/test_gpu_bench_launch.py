@@ -89,6 +89,27 @@ def test_scale_check_fails_loudly_on_other_counters(tmp_path):
     assert bad["scale_check"]["ok"] is False
 
 
+def test_dump_outputs_are_the_last_steps_results(tmp_path):
+    """--dump-outputs DIR: the per-colour counters of the last timed step (their sums are the line's `counters` sums) and a seeded sample of
+    the per-k-mer unique colours, float arrays only, the same in two runs; a plain run carries no side record"""
+    import numpy as np
+    names = ["hits", "n_unique", "sum_unique_freq", "unique_colour_sample", "unique_colour_sample_index"]
+    lines, arrs = [], []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        lines.append(one_json_line(run_bench(TOY + ["--dump-outputs", str(d)])))
+        assert sorted(p.name for p in d.iterdir()) == sorted(n + ".npy" for n in names)
+        arrs.append({n: np.load(d / (n + ".npy")) for n in names})
+    a, line = arrs[0], lines[0]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert [int(a[n].sum()) for n in names[:3]] == line["counters"]["sums"] and all(a[n].shape == (256,) for n in names[:3])
+    K = line["config"]["kmers_per_gpu"]
+    assert a["unique_colour_sample"].shape == a["unique_colour_sample_index"].shape == (min(K, 1 << 20),)
+    assert a["unique_colour_sample_index"].max() < K and set(np.unique(a["unique_colour_sample"])) <= set(range(-1, 256))
+    assert all(np.array_equal(a[n], arrs[1][n]) for n in names)
+    assert line["steps"] == 2 and not {"cpu_baseline", "e2e", "rows128", "readid", "readid_long"} & set(line)
+
+
 def test_nccl_without_enough_devices_is_a_one_line_refusal():
     import torch
     if torch.cuda.device_count() >= 2:

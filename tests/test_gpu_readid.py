@@ -242,7 +242,7 @@ def test_readid_dev_understated_maxima_are_flagged(orc, phage):
     assert np.array_equal(rep[~over], want[0][~over])
 
 
-def test_readid_dense_report_is_sliced(orc, phage):
+def test_readid_dense_report_is_sliced(orc, phage, tmp_path):
     """The dense host call works through a batch in slices whose report rows fit a device scratch budget
     (CID_DENSE_REPORT_BYTES; 2 GiB by default): same rows as one launch."""
     import subprocess
@@ -252,13 +252,14 @@ def test_readid_dense_report_is_sliced(orc, phage):
     reads = sample_reads(orc, rng, genomes, 300, 120, True)
     bases, seq_off, read_seq0 = pack_reads(reads)
     want = oix.readid_counts(bases, seq_off, read_seq0, 1, 3)
-    np.savez("/tmp/_slice_case.npz", bases=bases, seq_off=seq_off, read_seq0=read_seq0, rep=want[0], nk=want[1], st=want[2], rows=oix.rows())
+    case = str(tmp_path / "slice_case.npz")
+    np.savez(case, bases=bases, seq_off=seq_off, read_seq0=read_seq0, rep=want[0], nk=want[1], st=want[2], rows=oix.rows())
     # the budget is read once per process: run the sliced call in a child with 37 rows per slice
     code = f"""
 import sys, numpy as np
 sys.path.insert(0, {os.path.dirname(HERE)!r})
 import colorid_amd
-z = np.load('/tmp/_slice_case.npz')
+z = np.load({case!r})
 ctx = colorid_amd.Context(0)
 hx = colorid_amd.Index(ctx, {oix.m}, {oix.n_hash}, {oix.k}, {oix.n_colors})
 hx.put_dense(z['rows']); hx.finalize()

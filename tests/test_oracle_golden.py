@@ -108,14 +108,14 @@ def test_sizing_kat_phage_b056(orc):  # 42 records, 33 726 bp, 32
     assert len(km) == 32634
 
 
-def test_sizing_kat_egd_e(orc):
+def test_sizing_kat_egd_e(orc, tmp_path):
     """the 2 912 954 distinct canonical 31-mers of refs/LmonoEGDe.fasta (configs[0]'s query genome, 2.94 Mbp) — the
-    second sizing KAT the survey asked the C oracle to re-derive.  The genome is not a fixture of this repository (3 MB): the test runs in
-    the container that holds /root/reference and is skipped on the GPU box."""
-    path = "/root/reference/refs/LmonoEGDe.fasta"
-    if not os.path.exists(path):
-        pytest.skip("the reference tree is not mounted here")
-    seqs = orc.read_fasta(path)
+    second sizing KAT the survey asked the C oracle to re-derive.  The genome is stored xz-compressed (0.8 MB) under tests/golden/genomes/
+    and unpacked for the oracle's plain-file reader."""
+    import lzma
+    path = tmp_path / "LmonoEGDe.fasta"
+    path.write_bytes(lzma.open(os.path.join(HERE, "golden", "genomes", "LmonoEGDe.fasta.xz")).read())
+    seqs = orc.read_fasta(str(path))
     km = orc.Kmers(31)
     for s in seqs:
         km.kmerize_vector(s, 1)
