@@ -150,6 +150,54 @@ int cid_index_put_records(cid_index *ix, const uint8_t *records, size_t n_record
     return cid::index_put_records_slice(ix, records, n_records, ix->n_colors, 0);
 }
 
+// `merge`: file colour c -> index colour colour_map[c].  The map is increasing, so the file colours of one output word are one run;
+// the plan lists the words the file reaches (k_put_records_mapped).  Only one upload chunk of records is on the device at a time.
+int cid_index_put_records_mapped(cid_index *ix, const uint8_t *records, size_t n_records, uint32_t n_colors_file, const uint32_t *colour_map) {
+    if (!ix || (n_records && !records) || !colour_map) return fail(CID_ERR_INVALID, "null argument");
+    if (ix->finalized) return fail(CID_ERR_STATE, "index already finalized");
+    if (n_colors_file == 0 || n_colors_file > ix->n_colors)
+        return fail(CID_ERR_INVALID, "%u file colours into an index of %u", n_colors_file, ix->n_colors);
+    std::vector<cid::MergePlan> plan;
+    for (uint32_t c = 0; c < n_colors_file; ++c) {
+        const uint32_t to = colour_map[c];
+        if (to >= ix->n_colors) return fail(CID_ERR_INVALID, "colour_map[%u] = %u >= n_colors %u", c, to, ix->n_colors);
+        if (c && to <= colour_map[c - 1]) return fail(CID_ERR_INVALID, "colour_map not strictly increasing at %u (%u after %u)", c, to, colour_map[c - 1]);
+        if (plan.empty() || plan.back().w != to / 32u) plan.push_back(cid::MergePlan{to / 32u, c, 0u, 0u});
+        plan.back().mask |= 1u << (to % 32u);
+    }
+    if (n_records == 0) return CID_OK;
+    cid_ctx *c = ix->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t w32_rec = (n_colors_file + 31u) / 32u;
+    const size_t rec_bytes = 24 + 4ull * w32_rec;
+    const uint32_t n_plan = (uint32_t)plan.size();
+    // records per upload: 256 MiB of them, and no more than 2^30 threads a launch
+    const size_t batch = std::min<size_t>((256u << 20) / rec_bytes, (1ull << 30) / n_plan);
+    void *d_plan;
+    int rc = slot_reserve(c, S_ROWIDS, plan.size() * sizeof(cid::MergePlan), &d_plan);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d_plan, plan.data(), plan.size() * sizeof(cid::MergePlan), hipMemcpyHostToDevice, c->stream));
+    for (size_t r0 = 0; r0 < n_records; r0 += batch) {
+        const size_t nr = n_records - r0 < batch ? n_records - r0 : batch;
+        void *d_rec, *d_err;
+        rc = slot_reserve(c, S_WORDS, nr * rec_bytes, &d_rec);
+        if (rc) return rc;
+        rc = slot_reserve(c, S_MISC, 16, &d_err);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_rec, records + r0 * rec_bytes, nr * rec_bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(cid::launch_put_records_mapped(ix->mat, ix->rs, (const uint32_t *)d_rec, w32_rec, (const cid::MergePlan *)d_plan, n_plan, nr, ix->m,
+                                               n_colors_file, (uint32_t *)d_err, c->stream));
+        uint32_t err = 0;
+        HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (err)
+            return fail(CID_ERR_INVALID, "malformed row record(s):%s%s%s%s", (err & 1) ? " word count != ceil(n_colors/32)" : "",
+                        (err & 2) ? " bit count != n_colors" : "", (err & 4) ? " row >= bloom_size" : "", (err & 8) ? " bits beyond n_colors" : "");
+    }
+    return CID_OK;
+}
+
 int cid_index_device_matrix(cid_index *ix, void **dev_ptr, uint64_t *row_stride_words) {
     if (!ix || !dev_ptr || !row_stride_words) return fail(CID_ERR_INVALID, "null argument");
     *dev_ptr = ix->mat;

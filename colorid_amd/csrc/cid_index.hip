@@ -38,6 +38,49 @@ __global__ void k_put_records(uint32_t *mat32, uint32_t rs, const uint32_t *rec3
     if (row < bloom_size) mat32[row * (2ull * rs) + w] = rec[4 + w_off + w];
 }
 
+// `merge`: the records of a file with n_colors_file colours OR-ed into a wider index through an increasing colour map.  The file
+// colours that land in output word plan[j].w are one contiguous run [lo, lo + popc(mask)) — at most 32 bits over at most two source
+// words: funnel-shifted together, then deposited into the bits of `mask` run by run (a software pdep).  One thread per (record, plan
+// entry); entry 0's thread checks the record as k_put_records does.  A file holds each row once and the inputs go one after the other
+// on one stream, so no two threads touch one word: a plain read-modify-write.
+__global__ void k_put_records_mapped(uint32_t *mat32, uint32_t rs, const uint32_t *rec32, uint32_t w32_rec, const MergePlan *plan,
+                                     uint32_t n_plan, uint64_t n_records, uint64_t bloom_size, uint32_t n_colors_file, uint32_t tail_mask,
+                                     uint32_t *err) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_records * n_plan) return;
+    const uint64_t r = i / n_plan;
+    const uint32_t j = (uint32_t)(i % n_plan);
+    const uint32_t *rec = rec32 + r * (6ull + w32_rec);
+    const uint64_t row = (uint64_t)rec[0] | ((uint64_t)rec[1] << 32);
+    if (j == 0) {
+        const uint64_t nw = (uint64_t)rec[2] | ((uint64_t)rec[3] << 32);
+        const uint64_t nbits = (uint64_t)rec[4 + w32_rec] | ((uint64_t)rec[5 + w32_rec] << 32);
+        uint32_t e = (nw != w32_rec ? 1u : 0u) | (nbits != n_colors_file ? 2u : 0u) | (row >= bloom_size ? 4u : 0u) |
+                     ((rec[4 + w32_rec - 1] & ~tail_mask) ? 8u : 0u);
+        if (e) atomicOr(err, e);
+    }
+    if (row >= bloom_size) return;
+    const MergePlan p = plan[j];
+    const uint32_t n = __builtin_popcount(p.mask);
+    const uint32_t s0 = p.lo >> 5, sh = p.lo & 31u;
+    const uint32_t lo_word = rec[4 + s0];
+    const uint32_t hi_word = sh + n > 32u ? rec[4 + s0 + 1] : 0u;   // (the run ends inside the file's colours: s0 + 1 < w32_rec)
+    uint32_t bits = __builtin_amdgcn_alignbit(hi_word, lo_word, sh);   // (hi:lo) >> sh
+    if (n < 32u) bits &= (1u << n) - 1u;
+    if (bits == 0) return;
+    uint32_t out = 0, m = p.mask;
+    while (m) {
+        const uint32_t at = __builtin_ctz(m);
+        const uint32_t rest = m >> at;
+        const uint32_t len = rest == 0xFFFFFFFFu ? 32u : (uint32_t)__builtin_ctz(~rest);
+        const uint32_t run = len == 32u ? 0xFFFFFFFFu : (1u << len) - 1u;
+        out |= (bits & run) << at;
+        bits = len == 32u ? 0u : bits >> len;
+        m &= ~(run << at);
+    }
+    mat32[row * (2ull * rs) + p.w] |= out;
+}
+
 __global__ void k_get_rows(const uint32_t *mat32, uint32_t rs, const uint64_t *row_ids, uint32_t *words, uint32_t w32,
                            uint64_t n_rows) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -119,6 +162,18 @@ hipError_t launch_put_records(uint64_t *mat, uint32_t rs, const uint32_t *d_reco
     const uint32_t tail_bits = n_colors % 32;
     hipLaunchKernelGGL(k_put_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<uint32_t *>(mat), rs, d_records,
                        w32_rec, w_off, w32_take, n_records, bloom_size, n_colors, tail_bits ? ((1u << tail_bits) - 1u) : 0xFFFFFFFFu, d_err);
+    return hipGetLastError();
+}
+
+hipError_t launch_put_records_mapped(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, const MergePlan *d_plan,
+                                     uint32_t n_plan, uint64_t n_records, uint64_t bloom_size, uint32_t n_colors_file, uint32_t *d_err,
+                                     hipStream_t stream) {
+    const uint64_t n = n_records * n_plan;
+    if (n == 0) return hipSuccess;
+    const uint32_t tail_bits = n_colors_file % 32;
+    hipLaunchKernelGGL(k_put_records_mapped, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<uint32_t *>(mat), rs,
+                       d_records, w32_rec, d_plan, n_plan, n_records, bloom_size, n_colors_file,
+                       tail_bits ? ((1u << tail_bits) - 1u) : 0xFFFFFFFFu, d_err);
     return hipGetLastError();
 }
 

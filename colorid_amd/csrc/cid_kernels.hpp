@@ -172,6 +172,12 @@ hipError_t launch_put_rows(uint64_t *mat, uint32_t rs, const uint64_t *d_row_ids
                            uint64_t n_rows, hipStream_t stream);
 hipError_t launch_put_records(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, uint32_t w_off, uint32_t w32_take,
                               uint64_t n_records, uint64_t bloom_size, uint32_t n_colors, uint32_t *d_err, hipStream_t stream);
+// One output word that the colours of a merged file reach: the file colours [lo, lo + popc(mask)) become the set bits of `mask`
+// in u32 word w of every row (k_put_records_mapped).
+struct MergePlan { uint32_t w, lo, mask, pad; };
+hipError_t launch_put_records_mapped(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, const MergePlan *d_plan,
+                                     uint32_t n_plan, uint64_t n_records, uint64_t bloom_size, uint32_t n_colors_file, uint32_t *d_err,
+                                     hipStream_t stream);
 hipError_t launch_get_rows(const uint64_t *mat, uint32_t rs, const uint64_t *d_row_ids, uint32_t *d_words, uint32_t w32,
                            uint64_t n_rows, hipStream_t stream);
 hipError_t launch_insert_kmers(const InsertParams &p, hipStream_t stream);

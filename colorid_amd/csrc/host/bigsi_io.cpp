@@ -1,6 +1,7 @@
 // .bxi (bincode 1.x of BigsyMapNew, src/bigsi.rs:19-27 / SURVEY.md App. A) <-> device-resident index,
 // and the index builder (src/build.rs:15-130) with the Bloom inserts done on the GPU.
 #include <algorithm>
+#include <cstdarg>
 #include <cstring>
 #include <future>
 #include <thread>
@@ -26,10 +27,21 @@ struct BufReader {  // big sequential reads; the file is parsed once, front to b
     FILE *f;
     std::vector<uint8_t> buf;
     size_t pos = 0, end = 0;
-    explicit BufReader(const std::string &path) : f(fopen(path.c_str(), "rb")), buf(1u << 20) {
+    std::string label;   // non-empty: every error names the file (merge reads several)
+    explicit BufReader(const std::string &path, bool name_in_errors = false)
+        : f(fopen(path.c_str(), "rb")), buf(1u << 20), label(name_in_errors ? path : std::string()) {
         if (!f) die("Can't open index!: %s", path.c_str());
     }
     ~BufReader() { fclose(f); }
+    [[noreturn]] void fail(const char *fmt, ...) __attribute__((format(printf, 2, 3))) {
+        char msg[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(msg, sizeof msg, fmt, ap);
+        va_end(ap);
+        if (label.empty()) die("%s", msg);
+        die("%s: %s", label.c_str(), msg);
+    }
     void need(size_t n) {
         if (end - pos >= n) return;
         memmove(buf.data(), buf.data() + pos, end - pos);
@@ -38,7 +50,7 @@ struct BufReader {  // big sequential reads; the file is parsed once, front to b
         if (n > buf.size()) buf.resize(n);
         while (end < n) {
             size_t got = fread(buf.data() + end, 1, buf.size() - end, f);
-            if (got == 0) die("can't deserialize: unexpected end of file");
+            if (got == 0) fail("can't deserialize: unexpected end of file");
             end += got;
         }
     }
@@ -69,20 +81,20 @@ struct BufReader {  // big sequential reads; the file is parsed once, front to b
                 for (int t = 1; t < n_threads; ++t) th.emplace_back(work, t);
                 work(0);
                 for (auto &x : th) x.join();
-                for (int b : bad) if (b) die("can't deserialize: unexpected end of file");
-                if (fseeko(f, at + (off_t)rest, SEEK_SET) != 0) die("can't deserialize: seek failed");
+                for (int b : bad) if (b) fail("can't deserialize: unexpected end of file");
+                if (fseeko(f, at + (off_t)rest, SEEK_SET) != 0) fail("can't deserialize: seek failed");
                 return;
             }
         }
         while (got < n) {
             const size_t g = fread(dst + got, 1, n - got, f);
-            if (g == 0) die("can't deserialize: unexpected end of file");
+            if (g == 0) fail("can't deserialize: unexpected end of file");
             got += g;
         }
     }
     uint64_t tell() { return (uint64_t)ftello(f) - (end - pos); }   // the file offset of the next byte this reader hands out
     void seek(uint64_t at) {
-        if (fseeko(f, (off_t)at, SEEK_SET) != 0) die("can't deserialize: seek failed");
+        if (fseeko(f, (off_t)at, SEEK_SET) != 0) fail("can't deserialize: seek failed");
         pos = end = 0;
     }
     uint64_t u64() {
@@ -94,7 +106,7 @@ struct BufReader {  // big sequential reads; the file is parsed once, front to b
     }
     std::string str() {
         const uint64_t n = u64();
-        if (n > (1u << 30)) die("can't deserialize: string of %llu bytes", (unsigned long long)n);
+        if (n > (1u << 30)) fail("can't deserialize: string of %llu bytes", (unsigned long long)n);
         need(n);
         std::string s(reinterpret_cast<const char *>(buf.data() + pos), n);
         pos += n;
@@ -152,62 +164,56 @@ MappedIndex mapped_index(const std::string &path) {
 }
 }  // namespace
 
-Bigsi read_bigsi(cid_ctx *ctx, const std::string &path, int hash_variant, bool meta_only, cid_group *group, std::vector<cid_index *> *stripes) {
-    BufReader r(path);
-    Bigsi b;
+namespace {
+
+// The file up to its row records: the struct's scalars, then the colours by id.  Returns the number of row records; r is left at
+// the first of them.
+uint64_t read_header(BufReader &r, const std::string &path, Bigsi &b) {
     b.bloom_size = r.u64();
     b.num_hash = r.u64();
     b.k_size = r.u64();
     const bool mini = path.size() >= 4 && path.compare(path.size() - 4, 4, ".mxi") == 0;   // the suffix selects the struct (main.rs:723)
     if (mini) b.m_size = r.u64();                                                            // BigsyMapMiniNew.m_size
     const uint64_t nc = r.u64();
-    if (nc == 0 || nc > (1u << 24)) die("can't deserialize: %llu colours", (unsigned long long)nc);
+    if (nc == 0 || nc > (1u << 24)) r.fail("can't deserialize: %llu colours", (unsigned long long)nc);
     b.colors.assign(nc, std::string());
     for (uint64_t i = 0; i < nc; ++i) {
         const uint64_t id = r.u64();
         std::string name = r.str();
-        if (id >= nc) die("can't deserialize: colour id %llu of %llu", (unsigned long long)id, (unsigned long long)nc);
+        if (id >= nc) r.fail("can't deserialize: colour id %llu of %llu", (unsigned long long)id, (unsigned long long)nc);
         b.colors[id] = std::move(name);
     }
-    const uint32_t w32 = (uint32_t)((nc + 31) / 32);
-    const uint64_t n_rows = r.u64();
-    if (!meta_only && stripes) {   // one colour stripe per rank of the group (an index larger than one GPU's HBM)
-        if (mini) die("Error: an index with minimizers (.mxi) cannot be striped over GPUs");
-        int n_ranks = 0;
-        CID_TRY(cid_group_size(group, &n_ranks));
-        stripes->assign((size_t)n_ranks, nullptr);
-        CID_TRY(cid_group_stripes_create(group, b.bloom_size, (uint32_t)b.num_hash, (uint32_t)b.k_size, (uint32_t)nc, hash_variant, stripes->data()));
-    } else if (!meta_only) {
-        CID_TRY(cid_index_create(ctx, b.bloom_size, (uint32_t)b.num_hash, (uint32_t)b.k_size, (uint32_t)nc, hash_variant, &b.index));
-        if (mini) CID_TRY(cid_index_set_minimizer(b.index, (uint32_t)b.m_size));
+    return r.u64();
+}
+
+size_t record_bytes(const Bigsi &b) { return 24 + 4ull * ((b.colors.size() + 31) / 32); }
+
+// The file after its row records: n_ref_kmers by accession name, kept in colour order
+void read_tail(BufReader &r, Bigsi &b) {
+    const uint64_t nc = b.colors.size();
+    b.n_ref_kmers.assign(nc, 0);
+    std::map<std::string, uint64_t> by_name;
+    for (uint64_t c = 0; c < nc; ++c) by_name[b.colors[c]] = c;
+    const uint64_t n_ref = r.u64();
+    for (uint64_t i = 0; i < n_ref; ++i) {
+        std::string name = r.str();
+        const uint64_t v = r.u64();
+        auto it = by_name.find(name);
+        if (it != by_name.end()) b.n_ref_kmers[it->second] = v;
     }
-    // The row records go to the device as they sit in the file — { u64 row ; u64 W32 ; W32 x u32 ; u64 nbits } each — and are
-    // parsed and checked there (cid_index_put_records); a second thread reads the next chunk while this one is uploaded.
-    const size_t rec = 24 + 4ull * w32;
-    if (n_rows > (~0ull) / rec) die("can't deserialize: %llu rows", (unsigned long long)n_rows);
-    if (meta_only) {   // `info`: no device; the records are still checked, as deserialising them would
-        std::vector<uint8_t> chunk;
-        for (uint64_t left = n_rows; left;) {
-            const size_t nr = (size_t)std::min<uint64_t>(left, (16u << 20) / rec + 1);
-            chunk.resize(nr * rec);
-            r.read_exact(chunk.data(), nr * rec);
-            for (size_t i = 0; i < nr; ++i) {
-                uint64_t nw, nbits;
-                memcpy(&nw, chunk.data() + i * rec + 8, 8);
-                memcpy(&nbits, chunk.data() + i * rec + 16 + 4ull * w32, 8);
-                if (nw != w32) die("can't deserialize: row with %llu words, expected %u", (unsigned long long)nw, w32);
-                if (nbits != nc) die("can't deserialize: row of %llu bits, expected %llu", (unsigned long long)nbits, (unsigned long long)nc);
-            }
-            left -= nr;
-        }
-    } else if (const MappedIndex mi = mapped_index(path); mi.p) {   // straight from the mapping (bigsi_read_ahead)
+}
+
+// The row records go to the device as they sit in the file — { u64 row ; u64 W32 ; W32 x u32 ; u64 nbits } each — and are parsed and
+// checked there (put: cid_index_put_records or one of its kin): straight from the mapping when bigsi_read_ahead made one, else a second
+// thread reads the next chunk while this one is uploaded.  r is at the first record and is left just past the last.
+void stream_records(BufReader &r, const std::string &path, uint64_t n_rows, size_t rec, const std::function<int(const uint8_t *, size_t)> &put) {
+    if (const MappedIndex mi = mapped_index(path); mi.p) {
         const uint64_t at = r.tell();
         if (at > mi.n || n_rows * rec > mi.n - at) die("can't deserialize: unexpected end of file");
         const size_t chunk_recs = std::max<size_t>(1, (256u << 20) / rec);
         for (uint64_t done = 0; done < n_rows;) {
             const size_t nr = (size_t)std::min<uint64_t>(n_rows - done, chunk_recs);
-            const uint8_t *src = mi.p + at + done * rec;
-            const int rc = stripes ? cid_group_stripes_put_records(group, stripes->data(), src, nr) : cid_index_put_records(b.index, src, nr);
+            const int rc = put(mi.p + at + done * rec, nr);
             if (rc != CID_OK) die("can't deserialize: %s", cid_last_error());
             done += nr;
         }
@@ -228,27 +234,140 @@ Bigsi read_bigsi(cid_ctx *ctx, const std::string &path, int hash_variant, bool m
         int cur = 0;
         while (have[cur]) {
             std::thread prefetch([&, cur] { fill(cur ^ 1); });
-            const int rc = stripes ? cid_group_stripes_put_records(group, stripes->data(), bufs[cur].data(), have[cur])
-                                   : cid_index_put_records(b.index, bufs[cur].data(), have[cur]);
+            const int rc = put(bufs[cur].data(), have[cur]);
             prefetch.join();
             if (rc != CID_OK) die("can't deserialize: %s", cid_last_error());
             cur ^= 1;
         }
     }
-    b.n_ref_kmers.assign(nc, 0);
-    std::map<std::string, uint64_t> by_name;
-    for (uint64_t c = 0; c < nc; ++c) by_name[b.colors[c]] = c;
-    const uint64_t n_ref = r.u64();
-    for (uint64_t i = 0; i < n_ref; ++i) {
-        std::string name = r.str();
-        const uint64_t v = r.u64();
-        auto it = by_name.find(name);
-        if (it != by_name.end()) b.n_ref_kmers[it->second] = v;
+}
+
+}  // namespace
+
+Bigsi read_bigsi(cid_ctx *ctx, const std::string &path, int hash_variant, bool meta_only, cid_group *group, std::vector<cid_index *> *stripes) {
+    BufReader r(path);
+    Bigsi b;
+    const uint64_t n_rows = read_header(r, path, b);
+    const bool mini = b.m_size != 0;
+    const uint64_t nc = b.colors.size();
+    const uint32_t w32 = (uint32_t)((nc + 31) / 32);
+    if (!meta_only && stripes) {   // one colour stripe per rank of the group (an index larger than one GPU's HBM)
+        if (mini) die("Error: an index with minimizers (.mxi) cannot be striped over GPUs");
+        int n_ranks = 0;
+        CID_TRY(cid_group_size(group, &n_ranks));
+        stripes->assign((size_t)n_ranks, nullptr);
+        CID_TRY(cid_group_stripes_create(group, b.bloom_size, (uint32_t)b.num_hash, (uint32_t)b.k_size, (uint32_t)nc, hash_variant, stripes->data()));
+    } else if (!meta_only) {
+        CID_TRY(cid_index_create(ctx, b.bloom_size, (uint32_t)b.num_hash, (uint32_t)b.k_size, (uint32_t)nc, hash_variant, &b.index));
+        if (mini) CID_TRY(cid_index_set_minimizer(b.index, (uint32_t)b.m_size));
     }
+    const size_t rec = record_bytes(b);
+    if (n_rows > (~0ull) / rec) die("can't deserialize: %llu rows", (unsigned long long)n_rows);
+    if (meta_only) {   // `info`: no device; the records are still checked, as deserialising them would
+        std::vector<uint8_t> chunk;
+        for (uint64_t left = n_rows; left;) {
+            const size_t nr = (size_t)std::min<uint64_t>(left, (16u << 20) / rec + 1);
+            chunk.resize(nr * rec);
+            r.read_exact(chunk.data(), nr * rec);
+            for (size_t i = 0; i < nr; ++i) {
+                uint64_t nw, nbits;
+                memcpy(&nw, chunk.data() + i * rec + 8, 8);
+                memcpy(&nbits, chunk.data() + i * rec + 16 + 4ull * w32, 8);
+                if (nw != w32) die("can't deserialize: row with %llu words, expected %u", (unsigned long long)nw, w32);
+                if (nbits != nc) die("can't deserialize: row of %llu bits, expected %llu", (unsigned long long)nbits, (unsigned long long)nc);
+            }
+            left -= nr;
+        }
+    } else {
+        stream_records(r, path, n_rows, rec, [&](const uint8_t *src, size_t nr) {
+            return stripes ? cid_group_stripes_put_records(group, stripes->data(), src, nr) : cid_index_put_records(b.index, src, nr);
+        });
+    }
+    read_tail(r, b);
     if (!meta_only && stripes) {
         for (cid_index *ix : *stripes) CID_TRY(cid_index_finalize(ix));
     } else if (!meta_only) CID_TRY(cid_index_finalize(b.index));
     return b;
+}
+
+// merge: no counterpart in the reference.  Every check reads only the inputs' headers and n_ref_kmers tails (the tail lies at
+// header_end + n_rows x (24 + 4 W32)), so a refusal costs no GPU context and no pass over the rows.
+Bigsi merge_check(const std::vector<std::string> &paths, const std::string &out_path, std::vector<MergeInput> &inputs) {
+    if (paths.size() < 2) die("merge needs at least two input indices (-i a.bxi b.bxi ...), got %zu", paths.size());
+    auto is_mxi = [](const std::string &p) { return p.size() >= 4 && p.compare(p.size() - 4, 4, ".mxi") == 0; };
+    for (const std::string &p : paths)
+        if (is_mxi(p) != is_mxi(paths[0]))
+            die("merge: %s and %s are not the same kind of index (.bxi / .mxi): inputs must all be .bxi or all .mxi", paths[0].c_str(), p.c_str());
+    struct stat out_st;
+    const bool out_exists = stat(out_path.c_str(), &out_st) == 0;
+    inputs.assign(paths.size(), MergeInput());
+    std::map<std::string, std::pair<size_t, uint64_t>> owner;   // accession -> (input, colour in it); iterates in byte order, as tab_to_map
+    uint64_t total = 0;
+    for (size_t i = 0; i < paths.size(); ++i) {
+        MergeInput &in = inputs[i];
+        in.path = paths[i];
+        struct stat st;
+        if (stat(in.path.c_str(), &st) != 0) die("Can't open index!: %s", in.path.c_str());
+        if (out_exists && st.st_dev == out_st.st_dev && st.st_ino == out_st.st_ino)
+            die("merge: the output %s is the input %s: write the merged index to another file", out_path.c_str(), in.path.c_str());
+        BufReader r(in.path, /*name_in_errors=*/true);
+        in.n_rows = read_header(r, in.path, in.meta);
+        const uint64_t header_end = r.tell();
+        const size_t rec = record_bytes(in.meta);
+        if (in.n_rows > ((uint64_t)st.st_size) / rec || header_end + in.n_rows * rec + 8 > (uint64_t)st.st_size)
+            die("merge: %s is truncated: %llu row records of %zu bytes from byte %llu do not fit in its %llu bytes", in.path.c_str(),
+                (unsigned long long)in.n_rows, rec, (unsigned long long)header_end, (unsigned long long)st.st_size);
+        r.seek(header_end + in.n_rows * rec);
+        read_tail(r, in.meta);
+        const Bigsi &a = inputs[0].meta, &b = in.meta;
+        const struct { const char *name; uint64_t first, here; } fields[] = {
+            {"bloom_size", a.bloom_size, b.bloom_size}, {"num_hash", a.num_hash, b.num_hash}, {"k_size", a.k_size, b.k_size}, {"m_size", a.m_size, b.m_size}};
+        for (const auto &f : fields)
+            if (f.first != f.here)
+                die("merge: %s differs: %llu in %s, %llu in %s", f.name, (unsigned long long)f.first, inputs[0].path.c_str(), (unsigned long long)f.here,
+                    in.path.c_str());
+        for (uint64_t c = 0; c < b.colors.size(); ++c) {
+            // build numbers colours in name order (build.rs:105); the deposit needs that order (an increasing colour map)
+            if (c && b.colors[c] < b.colors[c - 1])
+                die("merge: %s numbers its accessions out of name order (%s before %s): merge takes indices as build writes them", in.path.c_str(),
+                    b.colors[c - 1].c_str(), b.colors[c].c_str());
+            const auto ins = owner.emplace(b.colors[c], std::make_pair(i, c));
+            if (!ins.second) {
+                const size_t j = ins.first->second.first;
+                if (j == i) die("merge: %s holds accession %s twice", in.path.c_str(), b.colors[c].c_str());
+                die("merge: accession %s is in both %s and %s", b.colors[c].c_str(), inputs[j].path.c_str(), in.path.c_str());
+            }
+        }
+        total += b.colors.size();
+    }
+    if (total > (1u << 20)) die("merge: %llu accessions in all, more than an index holds (2^20 = 1048576)", (unsigned long long)total);
+    Bigsi m;
+    m.bloom_size = inputs[0].meta.bloom_size; m.num_hash = inputs[0].meta.num_hash; m.k_size = inputs[0].meta.k_size; m.m_size = inputs[0].meta.m_size;
+    for (MergeInput &in : inputs) in.colour_map.assign(in.meta.colors.size(), 0);
+    for (const auto &kv : owner) {
+        MergeInput &in = inputs[kv.second.first];
+        in.colour_map[kv.second.second] = (uint32_t)m.colors.size();
+        m.colors.push_back(kv.first);
+        m.n_ref_kmers.push_back(in.meta.n_ref_kmers[kv.second.second]);
+    }
+    return m;
+}
+
+void merge_records(cid_ctx *ctx, Bigsi &m, const std::vector<MergeInput> &inputs) {
+    CID_TRY(cid_index_create(ctx, m.bloom_size, (uint32_t)m.num_hash, (uint32_t)m.k_size, (uint32_t)m.colors.size(), CID_HASH_XXH3_V08, &m.index));
+    if (m.m_size) CID_TRY(cid_index_set_minimizer(m.index, (uint32_t)m.m_size));
+    for (size_t i = 0; i < inputs.size(); ++i) {
+        const MergeInput &in = inputs[i];
+        fprintf(stderr, "Merging %s into index (%zu/%zu): %zu accessions, %llu rows\n", in.path.c_str(), i + 1, inputs.size(), in.meta.colors.size(),
+                (unsigned long long)in.n_rows);
+        BufReader r(in.path, /*name_in_errors=*/true);
+        Bigsi again;
+        if (read_header(r, in.path, again) != in.n_rows || again.colors != in.meta.colors) die("merge: %s changed while it was merged", in.path.c_str());
+        const uint32_t nc = (uint32_t)in.meta.colors.size();
+        stream_records(r, in.path, in.n_rows, record_bytes(in.meta), [&](const uint8_t *src, size_t nr) {
+            return cid_index_put_records_mapped(m.index, src, nr, nc, in.colour_map.data());
+        });
+    }
 }
 
 void save_bigsi(const std::string &path, const Bigsi &b) {

@@ -302,6 +302,18 @@ Bigsi read_bigsi(cid_ctx *ctx, const std::string &path, int hash_variant, bool m
 // map the index file and start touching its pages — call it before the GPU context is made; read_bigsi then uploads from the mapping
 void bigsi_read_ahead(const std::string &path);
 void save_bigsi(const std::string &path, const Bigsi &b);                                           // bigsi.rs:51-57
+// `merge` (no reference counterpart): indices of one shape and disjoint accessions as one index over the union of their accessions,
+// colours in name order as `build` numbers them.  merge_check reads every input's header and n_ref_kmers (not its rows) and refuses,
+// naming field or accession and files, what cannot be merged — before any GPU work; it returns the merged metadata (no index yet) and
+// each input's colour map.  merge_records makes the index on ctx and ORs every input's row records into it (not finalized).
+struct MergeInput {
+    std::string path;
+    Bigsi meta;                        // header, colours and n_ref_kmers; no device index
+    uint64_t n_rows = 0;
+    std::vector<uint32_t> colour_map;  // input colour -> merged colour (increasing)
+};
+Bigsi merge_check(const std::vector<std::string> &paths, const std::string &out_path, std::vector<MergeInput> &inputs);
+void merge_records(cid_ctx *ctx, Bigsi &merged, const std::vector<MergeInput> &inputs);
 Bigsi build_single(cid_ctx *ctx, const std::string &ref_tsv, uint64_t bloom, uint64_t hashes, uint64_t k, uint8_t quality,
                    int64_t cutoff, int hash_variant, uint64_t m_size = 0);   // build.rs:15-130; m_size > 0: build_single_mini :396-492
 

@@ -2,8 +2,9 @@
 //   search  (src/main.rs:127-217, :555-628)   read_id (:241-328, :704-868)   batch_id (:329-418, :869-888: read_id over a sample sheet)
 //   build   (:31-126, :466-554; needed to produce .bxi files)   info (:218-240, :630-703)
 // Same flag letters, defaults, stdout/stderr/file formats.  Extra flags: --device N, --gpus N | --devices a,b,.. (search, read_id:
-// the query is sharded over the GPUs), --hash xxh3_v08|xxh3_v07.  Extra command:
-// hashcheck (which hash variant was an index built with).
+// the query is sharded over the GPUs), --hash xxh3_v08|xxh3_v07.  Extra commands:
+// hashcheck (which hash variant was an index built with); merge (indices of one shape and disjoint accessions as one index, the
+// file `build` writes over the union of their reference lists).
 // Minimizer indices (.mxi): build -m [-v M], info, read_id, batch_id.  Not provided (outside the query path): read_filter.
 #include <cctype>
 #include <cerrno>
@@ -308,6 +309,44 @@ int cmd_build(int argc, char **argv) {
     return 0;
 }
 
+// merge: -b OUT -i a.bxi b.bxi [...] writes OUT.bxi (OUT.mxi for .mxi inputs): every accession of every input, colours in name order,
+// rows and n_ref_kmers as `build` over the union of the reference lists writes them.  Everything that would refuse the merge is checked
+// on the inputs' headers before the GPU is opened; the rows then go to the device one upload chunk at a time (the inputs are never
+// held there whole).  The file format carries no hash id: the inputs must have been built with one hash variant (`colorid hashcheck`).
+int cmd_merge(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {{'b', "bigsi", true, false}, {'i', "input", true, true}, {0, "device", true, false}});
+    for (const char *req : {"bigsi", "input"})
+        if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
+    const std::vector<std::string> &paths = a.values.at("input");
+    const bool minimizer = ends_with(paths[0], ".mxi");
+    const std::string out = a.one("bigsi") + (minimizer ? ".mxi" : ".bxi");
+    std::vector<MergeInput> inputs;
+    Bigsi b = merge_check(paths, out, inputs);
+    phase_done("inputs checked");
+    std::string in_list, parts;
+    for (const MergeInput &in : inputs) {
+        in_list += (in_list.empty() ? "" : " ") + in.path;
+        parts += (parts.empty() ? "" : " + ") + std::to_string(in.meta.colors.size());
+    }
+    printf(" Input indices : %s\n Bigsi file : %s\nK-mer size: %llu\nBloom filter parameters: num hashes %llu, filter size %llu\n", in_list.c_str(),
+           out.c_str(), (unsigned long long)b.k_size, (unsigned long long)b.num_hash, (unsigned long long)b.bloom_size);
+    if (minimizer) printf("Build with minimizers, minimizer size: %llu\n", (unsigned long long)b.m_size);
+    printf("Accessions: %zu (%s)\n", b.colors.size(), parts.c_str());
+    for (const MergeInput &in : inputs) bigsi_read_ahead(in.path);   // pages come in beside the runtime's start-up, as for `search`
+    cid_ctx *ctx = make_ctx(a);
+    phase_done("GPU context");
+    merge_records(ctx, b, inputs);
+    phase_done("records streamed and deposited");
+    if (cid_index_finalize(b.index) != CID_OK) die("cid_index_finalize: %s", cid_last_error());
+    phase_done("finalize");
+    printf("Saving BIGSI to file.\n");
+    save_bigsi(out, b);
+    phase_done("index written");
+    cid_index_destroy(b.index);
+    cid_ctx_destroy(ctx);
+    return 0;
+}
+
 int cmd_search(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, with_common({{'b', "bigsi", true, false}, {'q', "query", true, true}, {'r', "reverse", true, true},
                                                      {'f', "filter", true, false}, {'p', "p_shared", true, false}, {'g', "gene_search", false, false},
@@ -593,12 +632,12 @@ int main(int argc, char **argv) {
     // src/main.rs:16-20: init_log() prints this banner on stdout before anything else
     printf("\n ************** initializing logger *****************\n\n");
     if (argc < 2) {
-        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck> [FLAGS]\n");
+        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge> [FLAGS]\n");
         return 1;
     }
     const std::string cmd = argv[1];
     if (cmd == "--help" || cmd == "-h" || cmd == "help") {
-        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
+        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
                "ENVIRONMENT:\n"
                "    COLORID_FAST_EXIT=1      leave without the GPU runtime's teardown once the results are written, closed and flushed\n"
                "                             (-0.05 to -0.15 s per run); =0, or COLORID_FULL_TEARDOWN=1: always the orderly exit\n"
@@ -615,6 +654,7 @@ int main(int argc, char **argv) {
     if (cmd == "info") return leave(cmd_info(argc, argv));
     if (cmd == "read_id") return leave(cmd_read_id(argc, argv));
     if (cmd == "hashcheck") return leave(cmd_hashcheck(argc, argv));
+    if (cmd == "merge") return leave(cmd_merge(argc, argv));
     if (cmd == "debug-kmers") return cmd_debug_kmers(argc, argv);
     if (cmd == "debug-records") return cmd_debug_records(argc, argv);
     if (cmd == "batch_id") return leave(cmd_batch_id(argc, argv));

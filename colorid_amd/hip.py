@@ -90,6 +90,15 @@ class Index:
         buf = np.frombuffer(records, np.uint8)
         check(self.lib.cid_index_put_records(self.h, _p(buf), len(records) // rec))
 
+    def put_records_mapped(self, records: bytes, n_colors_file, colour_map):
+        """raw records of a file with n_colors_file colours, OR-ed in with file colour c at index colour colour_map[c] (`colorid merge`)"""
+        rec = 24 + 4 * ((n_colors_file + 31) // 32)
+        assert len(records) % rec == 0
+        buf = np.frombuffer(records, np.uint8)
+        cmap = np.ascontiguousarray(colour_map, np.uint32)
+        assert len(cmap) == n_colors_file
+        check(self.lib.cid_index_put_records_mapped(self.h, _p(buf), len(records) // rec, n_colors_file, _p(cmap)))
+
     def put_dense(self, rows_u32):
         """rows_u32: bloom_size x w32 dense BitVec storage; only non-zero rows are sent (as a .bxi holds them)."""
         rows_u32 = np.ascontiguousarray(rows_u32, np.uint32).reshape(self.m, self.w32)

@@ -37,7 +37,9 @@ extern "C" {
  * the three search calls on k-mers and on k-mer sets, per-read counts — plus what the one-GPU command line runs on (INTEGRATION.md §2-§5:
  * the k-mer set, the FASTQ front end, .bxi records).  Everything else is EXTENDED: device-pointer forms for callers that keep their data in
  * HBM, colour stripes, groups of GPUs, measurement helpers.  The core changes only with cid_abi_version(); extended entry points may gain
- * arguments between rounds.  include/colorid_hip.rs carries the same split as two modules. */
+ * arguments between rounds.  include/colorid_hip.rs carries the same split as two modules.
+ * cid_abi_version() counts changes, not additions: a new entry point (core or extended) leaves it where it is; it is bumped when a
+ * declaration that already exists changes its arguments or its meaning. */
 #define CID_CORE
 #define CID_OK 0
 #define CID_ERR_INVALID (-1)     /* bad argument */
@@ -99,6 +101,13 @@ CID_CORE int cid_index_put_rows(cid_index *, const uint64_t *row_ids, const uint
  * and checked on the device (n_words == W32, n_bits == n_colors, row < bloom_size, no bit beyond n_colors), so a loader
  * only has to read the file: CID_ERR_INVALID for a malformed record (the reference: "can't deserialize" panic, bigsi.rs:61). */
 CID_CORE int cid_index_put_records(cid_index *, const uint8_t *records, size_t n_records);
+/* `colorid merge`: the records of a file with n_colors_file colours (cid_index_put_records' format), OR-ed into this index through a
+ * colour map: file colour c becomes index colour colour_map[c]; colour_map strictly increasing and < the index's n_colors.  The records
+ * are checked as cid_index_put_records checks them, against the FILE's shape; a file holds each row once.  Call it once per input
+ * file (or per chunk of one), then cid_index_finalize.
+ * CID_ERR_INVALID: malformed record (same checks as cid_index_put_records) or bad map; CID_ERR_STATE after finalize. */
+int cid_index_put_records_mapped(cid_index *, const uint8_t *records, size_t n_records, uint32_t n_colors_file,
+                                 const uint32_t *colour_map);
 /* Native device layout: row r at matrix + r*row_stride_words (u64 words, little-endian pairs of the u32 words,
  * zero padded).  Exposed so a caller can generate/fill an index in HBM directly (bits >= n_colors MUST be 0). */
 int cid_index_device_matrix(cid_index *, void **dev_ptr, uint64_t *row_stride_words);
