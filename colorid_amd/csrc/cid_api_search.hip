@@ -184,6 +184,7 @@ int cid::search_count_host_input(cid_ctx *c, const cid_index *ix, const uint8_t 
     const size_t C = ix->n_colors, k = ix->k;
     size_t chunk = (size_t)c->tune.upload_chunk_bytes / (k + 8);
     chunk = (chunk + 63) & ~(size_t)63;          // chunks start on a tile boundary: 64*k bytes keep the 16-byte alignment of the k-mer array
+    if (chunk == 0) chunk = 64;                  // a budget below k + 8 bytes (0 included) still moves a tile per chunk
     if (chunk >= n_kmers || c->stream != c->own_stream) chunk = n_kmers ? n_kmers : 1;   // a borrowed stream: keep everything on it
     void *d_k, *d_f = nullptr, *d_out, *d_uc = nullptr;
     const size_t two = chunk < n_kmers ? 2 : 1;

@@ -1034,8 +1034,8 @@ extern "C" int cid_bgzf_inflate_start(cid_ctx *c, const uint8_t *members, size_t
     rc = cid::slot_reserve(c, S_MISC, n_members * sizeof(cid::BgzfMember), &d_mem); if (rc) return rc;
     rc = cid::slot_reserve(c, S_BASES, text_bytes + 16, &d_out); if (rc) return rc;
     rc = cid::slot_reserve(c, S_FREQ, n_members * 4, &d_st); if (rc) return rc;
-    void *d_scratch = nullptr;   // (refused: the one-lane kernel takes the batch)
-    if (cid::slot_reserve(c, S_ROWIDS, cid::bgzf_inflate_scratch_bytes((uint32_t)n_members), &d_scratch) != CID_OK) d_scratch = nullptr;
+    void *d_scratch = nullptr;   // (refused, or CID_INFLATE_WAVE=0: the one-lane kernel takes the batch and needs none)
+    if (c->tune.inflate_wave && cid::slot_reserve(c, S_ROWIDS, cid::bgzf_inflate_scratch_bytes((uint32_t)n_members), &d_scratch) != CID_OK) d_scratch = nullptr;
     // arena: members | member table | text | status
     const size_t b_mem = (n_bytes + 63) & ~(size_t)63, b_text = b_mem + ((n_members * sizeof(cid::BgzfMember) + 63) & ~(size_t)63),
                  b_st = b_text + ((text_bytes + 63) & ~(size_t)63), b_end = b_st + n_members * 4;

@@ -47,6 +47,53 @@ def test_command_line_asks_cli_env_only():
     assert listed - used == set(), listed - used
 
 
+# switches that no GPU test sets off their default, each for a reason
+EXEMPT = {
+    "alloc_trace": "only prints each scratch allocation on stderr",
+    "fastq_timing": "only prints a reader's host times on stderr when it is destroyed",
+    "search_persist": "absent from the shipped library: test_gpu_group.py tests its refusal",
+    "search_mixed": "absent from the shipped library: test_gpu_group.py tests its refusal",
+    "stripe_reduce": "its peer path is the one repeated device ids take anyway (test_gpu_group_stripes.py)",
+    "warm_dry_run": "only decides whether cid_warmup wakes the queues with a query on a context of its own",
+}
+# where a test sets a switch: (name, value) of tune("name", v) / ctx.tune(...), cid_ctx_tune(h, b"name", v), setenv("ENV", v),
+# {"ENV": v} or {"name": v}, and dict(os.environ, ENV=v)
+_SETTINGS = [r'\btune\(\s*b?["\'](\w+)["\']\s*,\s*([^)\n]+?)\s*\)',
+             r'\bcid_ctx_tune\([^,\n]+,\s*b["\'](\w+)["\']\s*,\s*([^)\n]+?)\s*\)',
+             r'\bsetenv\(\s*["\'](\w+)["\']\s*,\s*([^)\n]+?)\s*\)',
+             r'["\'](\w+)["\']\s*:\s*([^,}\n]+)',
+             r'\b([A-Z][A-Z0-9_]+)\s*=\s*([^,)\n]+)']
+
+
+def _is_default(value, dflt):
+    """a literal equal to the row's default; anything else (another literal, a variable, an expression) counts as set off it"""
+    v = value.strip()
+    m = re.fullmatch(r'b?["\']([^"\']*)["\']', v)
+    if m:
+        v = m.group(1)
+    try:
+        return int(v, 0) == int(dflt)
+    except ValueError:
+        return v == dflt
+
+
+def test_every_switch_is_tested_off_its_default():
+    """every row of cid_switches.def is set to another value than its default somewhere in tests/test_gpu_*.py — by its cid_ctx_tune
+    name or its variable — or is in EXEMPT: a new switch without a test fails here"""
+    rows = _rows(os.path.join(CSRC, "cid_switches.def"), "CID_SWITCH")
+    text = "".join(open(f).read() for f in sorted(glob.glob(os.path.join(ROOT, "tests", "test_gpu_*.py"))))
+    covered = set()
+    for pattern in _SETTINGS:
+        for name, value in re.findall(pattern, text):
+            for nm, env, _, dflt, _ in rows:
+                if name in (nm, env) and not _is_default(value, dflt):
+                    covered.add(nm)
+    names = {nm for nm, _, _, _, _ in rows}
+    assert set(EXEMPT) <= names, set(EXEMPT) - names
+    assert all(reason and "\n" not in reason for reason in EXEMPT.values())
+    assert names - covered - set(EXEMPT) == set(), sorted(names - covered - set(EXEMPT))
+
+
 def test_readme_table_is_generated():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_switch_table.py"), "--check"])
     assert p.returncode == 0, "README.md's switch table is stale: run python3 tools/gen_switch_table.py"
