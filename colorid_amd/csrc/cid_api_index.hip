@@ -198,6 +198,69 @@ int cid_index_put_records_mapped(cid_index *ix, const uint8_t *records, size_t n
     return CID_OK;
 }
 
+// `subset`: the k-th set bit of keep_words (a bitmap over the file's colours) becomes index colour k.  The bitmap becomes a plan once per
+// call: the file words that keep anything, and per output word where its 32 kept bits start among them (k_put_records_subset).  Rows are
+// stored whole, so one file fills the index; only one upload chunk of records is on the device at a time.
+int cid_index_put_records_subset(cid_index *ix, const uint8_t *records, size_t n_records, uint32_t n_colors_file, const uint32_t *keep_words) {
+    if (!ix || (n_records && !records) || !keep_words) return fail(CID_ERR_INVALID, "null argument");
+    if (ix->finalized) return fail(CID_ERR_STATE, "index already finalized");
+    if (n_colors_file == 0) return fail(CID_ERR_INVALID, "a file of 0 colours");
+    const uint32_t w32_rec = (n_colors_file + 31u) / 32u;
+    const uint32_t tail_bits = n_colors_file % 32u;
+    if (tail_bits && (keep_words[w32_rec - 1] >> tail_bits))
+        return fail(CID_ERR_INVALID, "keep bitmap has a bit at or beyond the file's %u colours", n_colors_file);
+    std::vector<cid::SubsetItem> items;
+    std::vector<uint64_t> before;   // kept bits before each item
+    uint64_t kept = 0;
+    for (uint32_t s = 0; s < w32_rec; ++s)
+        if (keep_words[s]) {
+            items.push_back(cid::SubsetItem{s, keep_words[s]});
+            before.push_back(kept);
+            kept += (uint64_t)__builtin_popcount(keep_words[s]);
+        }
+    if (kept != ix->n_colors) return fail(CID_ERR_INVALID, "keep bitmap selects %llu colours, the index has %u", (unsigned long long)kept, ix->n_colors);
+    std::vector<cid::SubsetWord> words(ix->w32);
+    for (uint32_t j = 0, first = 0; j < ix->w32; ++j) {
+        const uint64_t lo = 32ull * j, hi = std::min<uint64_t>(lo + 32u, kept) - 1;   // the word's first and last kept bit
+        while (first + 1 < items.size() && before[first + 1] <= lo) ++first;
+        uint32_t last = first;
+        while (last + 1 < items.size() && before[last + 1] <= hi) ++last;
+        words[j] = cid::SubsetWord{first, (uint32_t)(lo - before[first]), last - first + 1, 0u};
+    }
+    if (n_records == 0) return CID_OK;
+    cid_ctx *c = ix->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t rec_bytes = 24 + 4ull * w32_rec;
+    // records per upload: 256 MiB of them, and no more than 2^30 threads a launch
+    const size_t batch = std::min<size_t>((256u << 20) / rec_bytes, (1ull << 30) / ix->w32);
+    const size_t words_bytes = words.size() * sizeof(cid::SubsetWord), items_bytes = items.size() * sizeof(cid::SubsetItem);
+    void *d_plan;
+    int rc = slot_reserve(c, S_ROWIDS, words_bytes + items_bytes, &d_plan);   // the words (16 B each), then the items (8 B each)
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d_plan, words.data(), words_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync((uint8_t *)d_plan + words_bytes, items.data(), items_bytes, hipMemcpyHostToDevice, c->stream));
+    for (size_t r0 = 0; r0 < n_records; r0 += batch) {
+        const size_t nr = n_records - r0 < batch ? n_records - r0 : batch;
+        void *d_rec, *d_err;
+        rc = slot_reserve(c, S_WORDS, nr * rec_bytes, &d_rec);
+        if (rc) return rc;
+        rc = slot_reserve(c, S_MISC, 16, &d_err);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_rec, records + r0 * rec_bytes, nr * rec_bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(cid::launch_put_records_subset(ix->mat, ix->rs, (const uint32_t *)d_rec, w32_rec, (const cid::SubsetWord *)d_plan,
+                                               (const cid::SubsetItem *)((const uint8_t *)d_plan + words_bytes), ix->w32, nr, ix->m, n_colors_file,
+                                               (uint32_t *)d_err, c->stream));
+        uint32_t err = 0;
+        HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (err)
+            return fail(CID_ERR_INVALID, "malformed row record(s):%s%s%s%s", (err & 1) ? " word count != ceil(n_colors/32)" : "",
+                        (err & 2) ? " bit count != n_colors" : "", (err & 4) ? " row >= bloom_size" : "", (err & 8) ? " bits beyond n_colors" : "");
+    }
+    return CID_OK;
+}
+
 int cid_index_device_matrix(cid_index *ix, void **dev_ptr, uint64_t *row_stride_words) {
     if (!ix || !dev_ptr || !row_stride_words) return fail(CID_ERR_INVALID, "null argument");
     *dev_ptr = ix->mat;

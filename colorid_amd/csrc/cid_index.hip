@@ -81,6 +81,54 @@ __global__ void k_put_records_mapped(uint32_t *mat32, uint32_t rs, const uint32_
     mat32[row * (2ull * rs) + p.w] |= out;
 }
 
+// `subset`: the kept colours of a file with n_colors_file colours, packed into a narrower index — the inverse of the deposit above (a
+// software pext).  One thread per (record, OUTPUT u32 word j): the word's 32 kept bits lie in a run of consecutive plan items (file
+// words with a non-zero keep mask); the thread extracts each item's bits under its mask run by run, drops the `skip` bits of the first
+// item that earlier output words took, and appends the rest where the word is filled so far — until 32 bits or the plan's end.  What
+// overflows the word belongs to thread j + 1, which extracts it again.  Every output word of a put row is written once, by one thread,
+// with a plain store: no atomics, no read-modify-write.  Only kept bits are ever appended, so the bits at and beyond the index's
+// n_colors in the last word are zero.  Word 0's thread checks the record as k_put_records does, against the file's shape.
+__global__ void k_put_records_subset(uint32_t *mat32, uint32_t rs, const uint32_t *rec32, uint32_t w32_rec, const SubsetWord *words,
+                                     const SubsetItem *items, uint32_t w32_out, uint64_t n_records, uint64_t bloom_size,
+                                     uint32_t n_colors_file, uint32_t tail_mask, uint32_t *err) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_records * w32_out) return;
+    const uint64_t r = i / w32_out;
+    const uint32_t j = (uint32_t)(i % w32_out);
+    const uint32_t *rec = rec32 + r * (6ull + w32_rec);
+    const uint64_t row = (uint64_t)rec[0] | ((uint64_t)rec[1] << 32);
+    if (j == 0) {
+        const uint64_t nw = (uint64_t)rec[2] | ((uint64_t)rec[3] << 32);
+        const uint64_t nbits = (uint64_t)rec[4 + w32_rec] | ((uint64_t)rec[5 + w32_rec] << 32);
+        uint32_t e = (nw != w32_rec ? 1u : 0u) | (nbits != n_colors_file ? 2u : 0u) | (row >= bloom_size ? 4u : 0u) |
+                     ((rec[4 + w32_rec - 1] & ~tail_mask) ? 8u : 0u);
+        if (e) atomicOr(err, e);
+    }
+    if (row >= bloom_size) return;
+    const SubsetWord p = words[j];
+    uint32_t out = 0, filled = 0, drop = p.skip;
+    for (uint32_t t = 0; t < p.n_items && filled < 32u; ++t) {
+        const SubsetItem it = items[p.first + t];   // (it.s < w32_rec: the host made the items from the file's own words)
+        const uint32_t v = rec[4 + it.s];
+        uint32_t bits = 0, n = 0, m = it.mask;
+        while (m) {
+            const uint32_t at = __builtin_ctz(m);
+            const uint32_t rest = m >> at;
+            const uint32_t len = rest == 0xFFFFFFFFu ? 32u : (uint32_t)__builtin_ctz(~rest);
+            const uint32_t run = len == 32u ? 0xFFFFFFFFu : (1u << len) - 1u;
+            bits |= ((v >> at) & run) << n;   // (n < 32 while a run is left)
+            n += len;
+            m &= ~(run << at);
+        }
+        bits >>= drop;   // drop < popc(mask) <= 32 for the first item, 0 afterwards
+        n -= drop;
+        drop = 0;
+        out |= bits << filled;
+        filled += n;
+    }
+    mat32[row * (2ull * rs) + j] = out;
+}
+
 __global__ void k_get_rows(const uint32_t *mat32, uint32_t rs, const uint64_t *row_ids, uint32_t *words, uint32_t w32,
                            uint64_t n_rows) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -173,6 +221,18 @@ hipError_t launch_put_records_mapped(uint64_t *mat, uint32_t rs, const uint32_t 
     const uint32_t tail_bits = n_colors_file % 32;
     hipLaunchKernelGGL(k_put_records_mapped, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<uint32_t *>(mat), rs,
                        d_records, w32_rec, d_plan, n_plan, n_records, bloom_size, n_colors_file,
+                       tail_bits ? ((1u << tail_bits) - 1u) : 0xFFFFFFFFu, d_err);
+    return hipGetLastError();
+}
+
+hipError_t launch_put_records_subset(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, const SubsetWord *d_words,
+                                     const SubsetItem *d_items, uint32_t w32_out, uint64_t n_records, uint64_t bloom_size,
+                                     uint32_t n_colors_file, uint32_t *d_err, hipStream_t stream) {
+    const uint64_t n = n_records * w32_out;
+    if (n == 0) return hipSuccess;
+    const uint32_t tail_bits = n_colors_file % 32;
+    hipLaunchKernelGGL(k_put_records_subset, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<uint32_t *>(mat), rs,
+                       d_records, w32_rec, d_words, d_items, w32_out, n_records, bloom_size, n_colors_file,
                        tail_bits ? ((1u << tail_bits) - 1u) : 0xFFFFFFFFu, d_err);
     return hipGetLastError();
 }

@@ -178,6 +178,14 @@ struct MergePlan { uint32_t w, lo, mask, pad; };
 hipError_t launch_put_records_mapped(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, const MergePlan *d_plan,
                                      uint32_t n_plan, uint64_t n_records, uint64_t bloom_size, uint32_t n_colors_file, uint32_t *d_err,
                                      hipStream_t stream);
+// `subset`: the plan of an extraction of kept colours (k_put_records_subset).  Items: the file words that keep anything, ascending.
+// Per output u32 word j: kept bits 32j .. 32j+31 of a row lie in items [first, first + n_items); `skip` kept bits of item `first`
+// belong to earlier output words.
+struct SubsetItem { uint32_t s, mask; };
+struct SubsetWord { uint32_t first, skip, n_items, pad; };
+hipError_t launch_put_records_subset(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, const SubsetWord *d_words,
+                                     const SubsetItem *d_items, uint32_t w32_out, uint64_t n_records, uint64_t bloom_size,
+                                     uint32_t n_colors_file, uint32_t *d_err, hipStream_t stream);
 hipError_t launch_get_rows(const uint64_t *mat, uint32_t rs, const uint64_t *d_row_ids, uint32_t *d_words, uint32_t w32,
                            uint64_t n_rows, hipStream_t stream);
 hipError_t launch_insert_kmers(const InsertParams &p, hipStream_t stream);

@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstring>
 #include <future>
+#include <set>
 #include <thread>
 
 #include <fcntl.h>
@@ -290,11 +291,31 @@ Bigsi read_bigsi(cid_ctx *ctx, const std::string &path, int hash_variant, bool m
     return b;
 }
 
+namespace {
+
+// what `merge` and `subset` (cmd) check alike on an input's header
+bool is_mxi(const std::string &p) { return p.size() >= 4 && p.compare(p.size() - 4, 4, ".mxi") == 0; }
+
+// the row records and the count of the n_ref_kmers tail must fit in the file
+void check_not_truncated(const char *cmd, const std::string &path, uint64_t n_rows, size_t rec, uint64_t header_end, uint64_t file_size) {
+    if (n_rows > file_size / rec || header_end + n_rows * rec + 8 > file_size)
+        die("%s: %s is truncated: %llu row records of %zu bytes from byte %llu do not fit in its %llu bytes", cmd, path.c_str(),
+            (unsigned long long)n_rows, rec, (unsigned long long)header_end, (unsigned long long)file_size);
+}
+
+// build numbers colours in name order (build.rs:105); colour c must not sort before colour c - 1
+void check_name_order_at(const char *cmd, const std::string &path, const std::vector<std::string> &colors, uint64_t c) {
+    if (c && colors[c] < colors[c - 1])
+        die("%s: %s numbers its accessions out of name order (%s before %s): %s takes indices as build writes them", cmd, path.c_str(),
+            colors[c - 1].c_str(), colors[c].c_str(), cmd);
+}
+
+}  // namespace
+
 // merge: no counterpart in the reference.  Every check reads only the inputs' headers and n_ref_kmers tails (the tail lies at
 // header_end + n_rows x (24 + 4 W32)), so a refusal costs no GPU context and no pass over the rows.
 Bigsi merge_check(const std::vector<std::string> &paths, const std::string &out_path, std::vector<MergeInput> &inputs) {
     if (paths.size() < 2) die("merge needs at least two input indices (-i a.bxi b.bxi ...), got %zu", paths.size());
-    auto is_mxi = [](const std::string &p) { return p.size() >= 4 && p.compare(p.size() - 4, 4, ".mxi") == 0; };
     for (const std::string &p : paths)
         if (is_mxi(p) != is_mxi(paths[0]))
             die("merge: %s and %s are not the same kind of index (.bxi / .mxi): inputs must all be .bxi or all .mxi", paths[0].c_str(), p.c_str());
@@ -314,9 +335,7 @@ Bigsi merge_check(const std::vector<std::string> &paths, const std::string &out_
         in.n_rows = read_header(r, in.path, in.meta);
         const uint64_t header_end = r.tell();
         const size_t rec = record_bytes(in.meta);
-        if (in.n_rows > ((uint64_t)st.st_size) / rec || header_end + in.n_rows * rec + 8 > (uint64_t)st.st_size)
-            die("merge: %s is truncated: %llu row records of %zu bytes from byte %llu do not fit in its %llu bytes", in.path.c_str(),
-                (unsigned long long)in.n_rows, rec, (unsigned long long)header_end, (unsigned long long)st.st_size);
+        check_not_truncated("merge", in.path, in.n_rows, rec, header_end, (uint64_t)st.st_size);
         r.seek(header_end + in.n_rows * rec);
         read_tail(r, in.meta);
         const Bigsi &a = inputs[0].meta, &b = in.meta;
@@ -327,10 +346,7 @@ Bigsi merge_check(const std::vector<std::string> &paths, const std::string &out_
                 die("merge: %s differs: %llu in %s, %llu in %s", f.name, (unsigned long long)f.first, inputs[0].path.c_str(), (unsigned long long)f.here,
                     in.path.c_str());
         for (uint64_t c = 0; c < b.colors.size(); ++c) {
-            // build numbers colours in name order (build.rs:105); the deposit needs that order (an increasing colour map)
-            if (c && b.colors[c] < b.colors[c - 1])
-                die("merge: %s numbers its accessions out of name order (%s before %s): merge takes indices as build writes them", in.path.c_str(),
-                    b.colors[c - 1].c_str(), b.colors[c].c_str());
+            check_name_order_at("merge", in.path, b.colors, c);   // the deposit needs that order (an increasing colour map)
             const auto ins = owner.emplace(b.colors[c], std::make_pair(i, c));
             if (!ins.second) {
                 const size_t j = ins.first->second.first;
@@ -368,6 +384,79 @@ void merge_records(cid_ctx *ctx, Bigsi &m, const std::vector<MergeInput> &inputs
             return cid_index_put_records_mapped(m.index, src, nr, nc, in.colour_map.data());
         });
     }
+}
+
+// subset: no counterpart in the reference.  As merge_check, every refusal comes from the header, the n_ref_kmers tail and the list.
+Bigsi subset_check(const std::string &in_path, const std::string &out_path, const std::string &list_path, bool exclude, SubsetInput &in) {
+    in.path = in_path;
+    struct stat st, out_st;
+    if (stat(in.path.c_str(), &st) != 0) die("Can't open index!: %s", in.path.c_str());
+    if (stat(out_path.c_str(), &out_st) == 0 && st.st_dev == out_st.st_dev && st.st_ino == out_st.st_ino)
+        die("subset: the output %s is the input %s: write the subset to another file", out_path.c_str(), in.path.c_str());
+    // the list: the text before the first TAB of every non-empty line (a `build -r` reference list is one); a repeated name counts once
+    std::set<std::string> listed;
+    {
+        FILE *f = fopen(list_path.c_str(), "rb");
+        if (!f) die("subset: can't open the accession list %s", list_path.c_str());
+        std::string text;
+        char buf[1 << 16];
+        for (size_t got; (got = fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, got);
+        fclose(f);
+        for (size_t p = 0; p < text.size();) {
+            size_t e = text.find('\n', p);
+            if (e == std::string::npos) e = text.size();
+            std::string line = text.substr(p, e - p);
+            p = e + 1;
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (line.empty()) continue;
+            listed.insert(line.substr(0, line.find('\t')));
+        }
+    }
+    if (listed.empty()) die("subset: the accession list %s is empty", list_path.c_str());
+    BufReader r(in.path, /*name_in_errors=*/true);
+    in.n_rows = read_header(r, in.path, in.meta);
+    const uint64_t header_end = r.tell();
+    const size_t rec = record_bytes(in.meta);
+    check_not_truncated("subset", in.path, in.n_rows, rec, header_end, (uint64_t)st.st_size);
+    r.seek(header_end + in.n_rows * rec);
+    read_tail(r, in.meta);
+    const Bigsi &a = in.meta;
+    std::map<std::string, uint64_t> colour_of;
+    for (uint64_t c = 0; c < a.colors.size(); ++c) {
+        check_name_order_at("subset", in.path, a.colors, c);   // the kept colours keep their order, and build's order is name order
+        if (!colour_of.emplace(a.colors[c], c).second) die("subset: %s holds accession %s twice", in.path.c_str(), a.colors[c].c_str());
+    }
+    for (const std::string &name : listed)
+        if (!colour_of.count(name))
+            die("subset: accession %s of %s is not in %s", name.c_str(), list_path.c_str(), in.path.c_str());
+    Bigsi out;
+    out.bloom_size = a.bloom_size; out.num_hash = a.num_hash; out.k_size = a.k_size; out.m_size = a.m_size;
+    in.keep_words.assign((a.colors.size() + 31) / 32, 0u);
+    for (uint64_t c = 0; c < a.colors.size(); ++c)
+        if ((listed.count(a.colors[c]) != 0) != exclude) {
+            in.keep_words[c / 32] |= 1u << (c % 32);
+            out.colors.push_back(a.colors[c]);
+            out.n_ref_kmers.push_back(a.n_ref_kmers[c]);
+        }
+    if (out.colors.empty())
+        die("subset: nothing left to keep: %s excludes all %zu accessions of %s", list_path.c_str(), a.colors.size(), in.path.c_str());
+    if (out.colors.size() > (1u << 20))
+        die("subset: %zu accessions kept from %s, more than an index holds (2^20 = 1048576)", out.colors.size(), in.path.c_str());
+    return out;
+}
+
+void subset_records(cid_ctx *ctx, Bigsi &out, const SubsetInput &in) {
+    CID_TRY(cid_index_create(ctx, out.bloom_size, (uint32_t)out.num_hash, (uint32_t)out.k_size, (uint32_t)out.colors.size(), CID_HASH_XXH3_V08, &out.index));
+    if (out.m_size) CID_TRY(cid_index_set_minimizer(out.index, (uint32_t)out.m_size));
+    fprintf(stderr, "Extracting %zu of %zu accessions from %s: %llu rows\n", out.colors.size(), in.meta.colors.size(), in.path.c_str(),
+            (unsigned long long)in.n_rows);
+    BufReader r(in.path, /*name_in_errors=*/true);
+    Bigsi again;
+    if (read_header(r, in.path, again) != in.n_rows || again.colors != in.meta.colors) die("subset: %s changed while it was read", in.path.c_str());
+    const uint32_t nc = (uint32_t)in.meta.colors.size();
+    stream_records(r, in.path, in.n_rows, record_bytes(in.meta), [&](const uint8_t *src, size_t nr) {
+        return cid_index_put_records_subset(out.index, src, nr, nc, in.keep_words.data());
+    });
 }
 
 void save_bigsi(const std::string &path, const Bigsi &b) {

@@ -314,6 +314,19 @@ struct MergeInput {
 };
 Bigsi merge_check(const std::vector<std::string> &paths, const std::string &out_path, std::vector<MergeInput> &inputs);
 void merge_records(cid_ctx *ctx, Bigsi &merged, const std::vector<MergeInput> &inputs);
+// `subset` (no reference counterpart): the accessions of one index that a list names (exclude: all the others) as an index of their
+// own — the file `build` writes over the kept lines of the reference list.  subset_check reads the header, the n_ref_kmers and the list
+// (text, one accession per line up to the first TAB) and refuses before any GPU work, naming file and accession; it returns the output's
+// metadata (no index yet) and the keep bitmap.  subset_records makes the index on ctx and streams the input's records through
+// cid_index_put_records_subset (not finalized): the device holds the OUTPUT index and one upload chunk, never the input's matrix.
+struct SubsetInput {
+    std::string path;
+    Bigsi meta;                        // header, colours and n_ref_kmers; no device index
+    uint64_t n_rows = 0;
+    std::vector<uint32_t> keep_words;  // bitmap over the input's colours, in the rows' bit order
+};
+Bigsi subset_check(const std::string &in_path, const std::string &out_path, const std::string &list_path, bool exclude, SubsetInput &in);
+void subset_records(cid_ctx *ctx, Bigsi &out, const SubsetInput &in);
 Bigsi build_single(cid_ctx *ctx, const std::string &ref_tsv, uint64_t bloom, uint64_t hashes, uint64_t k, uint8_t quality,
                    int64_t cutoff, int hash_variant, uint64_t m_size = 0);   // build.rs:15-130; m_size > 0: build_single_mini :396-492
 

@@ -4,7 +4,8 @@
 // Same flag letters, defaults, stdout/stderr/file formats.  Extra flags: --device N, --gpus N | --devices a,b,.. (search, read_id:
 // the query is sharded over the GPUs), --hash xxh3_v08|xxh3_v07.  Extra commands:
 // hashcheck (which hash variant was an index built with); merge (indices of one shape and disjoint accessions as one index, the
-// file `build` writes over the union of their reference lists).
+// file `build` writes over the union of their reference lists); subset (chosen accessions of an index as an index of their own, the
+// file `build` writes over the kept lines of the reference list).
 // Minimizer indices (.mxi): build -m [-v M], info, read_id, batch_id.  Not provided (outside the query path): read_filter.
 #include <cctype>
 #include <cerrno>
@@ -347,6 +348,48 @@ int cmd_merge(int argc, char **argv) {
     return 0;
 }
 
+// subset: -b OUT -i in.bxi (-a keep.txt | -x drop.txt) writes OUT.bxi (OUT.mxi for an .mxi input): the listed accessions (-x: all the
+// others), colours renumbered in their order, rows and n_ref_kmers as `build` over the kept lines of the reference list writes them.
+// Everything that would refuse it is checked on the header, the n_ref_kmers tail and the list before the GPU is opened; the rows then go
+// to the device one upload chunk at a time: the device holds the output index, never the input's matrix.
+int cmd_subset(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {{'b', "bigsi", true, false}, {'i', "input", true, true}, {'a', "accessions", true, false},
+                                         {'x', "exclude", true, false}, {0, "device", true, false}});
+    for (const char *req : {"bigsi", "input"})
+        if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
+    if (a.has("accessions") == a.has("exclude"))
+        die("subset needs exactly one of -a/--accessions (the accessions to keep) and -x/--exclude (the accessions to drop), got %s",
+            a.has("accessions") ? "both" : "neither");
+    for (const char *k : {"accessions", "exclude"})
+        if (a.has(k) && a.values.at(k).size() != 1) die("subset takes one list file, got %zu for --%s", a.values.at(k).size(), k);
+    const std::vector<std::string> &paths = a.values.at("input");
+    if (paths.size() != 1) die("subset takes exactly one input index (-i in.bxi), got %zu: %s ...", paths.size(), paths[1].c_str());
+    const bool exclude = a.has("exclude");
+    const std::string &list = a.one(exclude ? "exclude" : "accessions");
+    const bool minimizer = ends_with(paths[0], ".mxi");
+    const std::string out = a.one("bigsi") + (minimizer ? ".mxi" : ".bxi");
+    SubsetInput in;
+    Bigsi b = subset_check(paths[0], out, list, exclude, in);
+    phase_done("input checked");
+    printf(" Input index : %s\n Bigsi file : %s\nK-mer size: %llu\nBloom filter parameters: num hashes %llu, filter size %llu\n", in.path.c_str(),
+           out.c_str(), (unsigned long long)b.k_size, (unsigned long long)b.num_hash, (unsigned long long)b.bloom_size);
+    if (minimizer) printf("Build with minimizers, minimizer size: %llu\n", (unsigned long long)b.m_size);
+    printf("Accessions: %zu of %zu kept\n", b.colors.size(), in.meta.colors.size());
+    bigsi_read_ahead(in.path);   // pages come in beside the runtime's start-up, as for `search`
+    cid_ctx *ctx = make_ctx(a);
+    phase_done("GPU context");
+    subset_records(ctx, b, in);
+    phase_done("records streamed and extracted");
+    if (cid_index_finalize(b.index) != CID_OK) die("cid_index_finalize: %s", cid_last_error());
+    phase_done("finalize");
+    printf("Saving BIGSI to file.\n");
+    save_bigsi(out, b);
+    phase_done("index written");
+    cid_index_destroy(b.index);
+    cid_ctx_destroy(ctx);
+    return 0;
+}
+
 int cmd_search(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, with_common({{'b', "bigsi", true, false}, {'q', "query", true, true}, {'r', "reverse", true, true},
                                                      {'f', "filter", true, false}, {'p', "p_shared", true, false}, {'g', "gene_search", false, false},
@@ -632,12 +675,12 @@ int main(int argc, char **argv) {
     // src/main.rs:16-20: init_log() prints this banner on stdout before anything else
     printf("\n ************** initializing logger *****************\n\n");
     if (argc < 2) {
-        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge> [FLAGS]\n");
+        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset> [FLAGS]\n");
         return 1;
     }
     const std::string cmd = argv[1];
     if (cmd == "--help" || cmd == "-h" || cmd == "help") {
-        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
+        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
                "ENVIRONMENT:\n"
                "    COLORID_FAST_EXIT=1      leave without the GPU runtime's teardown once the results are written, closed and flushed\n"
                "                             (-0.05 to -0.15 s per run); =0, or COLORID_FULL_TEARDOWN=1: always the orderly exit\n"
@@ -655,6 +698,7 @@ int main(int argc, char **argv) {
     if (cmd == "read_id") return leave(cmd_read_id(argc, argv));
     if (cmd == "hashcheck") return leave(cmd_hashcheck(argc, argv));
     if (cmd == "merge") return leave(cmd_merge(argc, argv));
+    if (cmd == "subset") return leave(cmd_subset(argc, argv));
     if (cmd == "debug-kmers") return cmd_debug_kmers(argc, argv);
     if (cmd == "debug-records") return cmd_debug_records(argc, argv);
     if (cmd == "batch_id") return leave(cmd_batch_id(argc, argv));

@@ -99,6 +99,22 @@ class Index:
         assert len(cmap) == n_colors_file
         check(self.lib.cid_index_put_records_mapped(self.h, _p(buf), len(records) // rec, n_colors_file, _p(cmap)))
 
+    def put_records_subset(self, records: bytes, n_colors_file, keep):
+        """raw records of a file with n_colors_file colours; the colours where `keep` is set are stored as index colours 0.. in their
+        order (`colorid subset`).  keep: one bool per file colour, or (dtype uint32) the ABI's bitmap words as they are"""
+        rec = 24 + 4 * ((n_colors_file + 31) // 32)
+        assert len(records) % rec == 0
+        buf = np.frombuffer(records, np.uint8)
+        keep = np.asarray(keep)
+        if keep.dtype == np.uint32:
+            words = np.ascontiguousarray(keep)
+        else:
+            assert len(keep) == n_colors_file
+            bits = np.zeros((n_colors_file + 31) // 32 * 32, np.uint8)
+            bits[:n_colors_file] = keep.astype(bool)
+            words = np.ascontiguousarray(np.packbits(bits, bitorder="little").view("<u4"))
+        check(self.lib.cid_index_put_records_subset(self.h, _p(buf), len(records) // rec, n_colors_file, _p(words)))
+
     def put_dense(self, rows_u32):
         """rows_u32: bloom_size x w32 dense BitVec storage; only non-zero rows are sent (as a .bxi holds them)."""
         rows_u32 = np.ascontiguousarray(rows_u32, np.uint32).reshape(self.m, self.w32)

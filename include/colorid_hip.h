@@ -108,6 +108,16 @@ CID_CORE int cid_index_put_records(cid_index *, const uint8_t *records, size_t n
  * CID_ERR_INVALID: malformed record (same checks as cid_index_put_records) or bad map; CID_ERR_STATE after finalize. */
 int cid_index_put_records_mapped(cid_index *, const uint8_t *records, size_t n_records, uint32_t n_colors_file,
                                  const uint32_t *colour_map);
+/* `colorid subset`: the inverse — chosen colours of a file with n_colors_file colours (cid_index_put_records' format) extracted into
+ * this narrower index.  keep_words is a bitmap over the file's colours: ceil(n_colors_file/32) little-endian u32 words in the rows' own
+ * bit order; its population count must equal the index's n_colors, no bit at or beyond n_colors_file may be set; the k-th set bit
+ * becomes index colour k.  The records are checked as cid_index_put_records checks them, against the FILE's shape.  Rows are STORED,
+ * not OR-ed: one file fills the whole index, a file holds each row once, rows never put stay zero.  Call it once per file (or per chunk
+ * of one), then cid_index_finalize.  Device memory: the index and one upload chunk of records, never the file's matrix.
+ * CID_ERR_INVALID: null argument, bad bitmap (wrong popcount, stray bit, n_colors_file 0) or malformed record; CID_ERR_STATE after
+ * finalize. */
+int cid_index_put_records_subset(cid_index *, const uint8_t *records, size_t n_records, uint32_t n_colors_file,
+                                 const uint32_t *keep_words);
 /* Native device layout: row r at matrix + r*row_stride_words (u64 words, little-endian pairs of the u32 words,
  * zero padded).  Exposed so a caller can generate/fill an index in HBM directly (bits >= n_colors MUST be 0). */
 int cid_index_device_matrix(cid_index *, void **dev_ptr, uint64_t *row_stride_words);
