@@ -42,6 +42,11 @@ SIGNATURES = {
     "cid_index_insert_kmers_dev": (C.c_int, [vp, vp, vp, C.c_size_t]),
     "cid_index_insert_kmers": (C.c_int, [vp, vp, C.c_uint32, C.c_size_t]),
     "cid_index_destroy": (None, [vp]),
+    "cid_pairs_create": (C.c_int, [vp, C.c_uint64, C.c_uint32, C.POINTER(vp)]),
+    "cid_pairs_add_records": (C.c_int, [vp, vp, C.c_size_t]),
+    "cid_pairs_add_index": (C.c_int, [vp, vp]),
+    "cid_pairs_fetch": (C.c_int, [vp, vp]),
+    "cid_pairs_destroy": (None, [vp]),
     "cid_search_count": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp]),
     "cid_search_count_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp]),
     "cid_search_perfect": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.POINTER(C.c_int)]),

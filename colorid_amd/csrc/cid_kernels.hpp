@@ -186,6 +186,22 @@ struct SubsetWord { uint32_t first, skip, n_items, pad; };
 hipError_t launch_put_records_subset(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, const SubsetWord *d_words,
                                      const SubsetItem *d_items, uint32_t w32_out, uint64_t n_records, uint64_t bloom_size,
                                      uint32_t n_colors_file, uint32_t *d_err, hipStream_t stream);
+// `compare`: shared[i][j] += popcount(column i & column j) over the rows of one source (k_pairs).  The rows are w32 u32 words at
+// rows + row*stride + off (u32 units): a chunk of file records (stride 6 + w32, off 4) or a resident index's matrix (stride 2*rs, off 0).
+// shared: n_colors x n_colors u64 counters, row-major; only i <= j is added to.  The launcher fills in the grid fields.
+struct PairsParams {
+    const uint32_t *rows;
+    uint64_t stride;
+    uint32_t off, w32;
+    uint64_t n_rows;
+    uint32_t n_colors;
+    unsigned long long *shared;
+    uint32_t n_blocks, n_pair_groups, tiles_per_block;   // 64-colour blocks; groups of four block pairs; row tiles per workgroup
+    uint64_t n_pairs, chunk0;                            // block pairs I <= J; the launch's first row chunk
+};
+hipError_t launch_pairs_check(const uint32_t *d_records, uint32_t w32_rec, uint64_t n_records, uint64_t bloom_size, uint32_t n_colors,
+                              uint32_t *d_err, hipStream_t stream);
+hipError_t launch_pairs(PairsParams p, int n_cu, hipStream_t stream);
 hipError_t launch_get_rows(const uint64_t *mat, uint32_t rs, const uint64_t *d_row_ids, uint32_t *d_words, uint32_t w32,
                            uint64_t n_rows, hipStream_t stream);
 hipError_t launch_insert_kmers(const InsertParams &p, hipStream_t stream);

@@ -75,6 +75,14 @@ struct cid_index {
     cid::ModMagic mod{};
 };
 
+// `compare`: the pair counters of one index shape (cid_pairs_*): shared[i][j] for i <= j, the rest of the matrix stays zero on the device
+struct cid_pairs {
+    cid_ctx *ctx = nullptr;
+    uint64_t m = 0;
+    uint32_t n_colors = 0, w32 = 0;
+    unsigned long long *shared = nullptr;   // n_colors x n_colors, row-major
+};
+
 namespace cid {
 // grow-only per-role device buffers of a ctx
 int slot_reserve(cid_ctx *c, int s, size_t bytes, void **out);

@@ -459,6 +459,41 @@ void subset_records(cid_ctx *ctx, Bigsi &out, const SubsetInput &in) {
     });
 }
 
+// compare: no counterpart in the reference.  As subset_check, every refusal but one comes from the header and the n_ref_kmers tail.
+void compare_check(const std::string &in_path, CompareInput &in) {
+    in.path = in_path;
+    struct stat st;
+    if (stat(in.path.c_str(), &st) != 0) die("Can't open index!: %s", in.path.c_str());
+    BufReader r(in.path, /*name_in_errors=*/true);
+    in.n_rows = read_header(r, in.path, in.meta);
+    const uint64_t header_end = r.tell();
+    const size_t rec = record_bytes(in.meta);
+    check_not_truncated("compare", in.path, in.n_rows, rec, header_end, (uint64_t)st.st_size);
+    r.seek(header_end + in.n_rows * rec);
+    read_tail(r, in.meta);
+    std::set<std::string> seen;
+    for (const std::string &name : in.meta.colors)
+        if (!seen.insert(name).second) die("compare: %s holds accession %s twice", in.path.c_str(), name.c_str());
+    if (in.meta.colors.size() > (1u << 20))
+        die("compare: %s holds %zu accessions, more than the pair counters take (2^20 = 1048576)", in.path.c_str(), in.meta.colors.size());
+}
+
+// the one refusal that needs the device: counters that do not fit in its memory (cid_pairs_create says how many bytes)
+std::vector<uint64_t> compare_records(cid_ctx *ctx, const CompareInput &in) {
+    const size_t nc = in.meta.colors.size();
+    cid_pairs *pairs = nullptr;
+    if (cid_pairs_create(ctx, in.meta.bloom_size, (uint32_t)nc, &pairs) != CID_OK) die("compare: %s: %s", in.path.c_str(), cid_last_error());
+    fprintf(stderr, "Comparing %zu accessions of %s: %llu rows\n", nc, in.path.c_str(), (unsigned long long)in.n_rows);
+    BufReader r(in.path, /*name_in_errors=*/true);
+    Bigsi again;
+    if (read_header(r, in.path, again) != in.n_rows || again.colors != in.meta.colors) die("compare: %s changed while it was read", in.path.c_str());
+    stream_records(r, in.path, in.n_rows, record_bytes(in.meta), [&](const uint8_t *src, size_t nr) { return cid_pairs_add_records(pairs, src, nr); });
+    std::vector<uint64_t> shared(nc * nc);
+    CID_TRY(cid_pairs_fetch(pairs, shared.data()));
+    cid_pairs_destroy(pairs);
+    return shared;
+}
+
 void save_bigsi(const std::string &path, const Bigsi &b) {
     FILE *f = fopen(path.c_str(), "wb");
     if (!f) die("problems preparing serialized data for writing: %s", path.c_str());

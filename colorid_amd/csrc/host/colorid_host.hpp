@@ -327,6 +327,17 @@ struct SubsetInput {
 };
 Bigsi subset_check(const std::string &in_path, const std::string &out_path, const std::string &list_path, bool exclude, SubsetInput &in);
 void subset_records(cid_ctx *ctx, Bigsi &out, const SubsetInput &in);
+// `compare` (no reference counterpart): which accessions of an index are (nearly) the same Bloom filter.  compare_check reads the header
+// and the n_ref_kmers tail and refuses before any GPU work (file missing, truncated, an accession twice).  compare_records makes the pair
+// counters on ctx, streams the input's records through cid_pairs_add_records and returns the symmetric n x n matrix shared[i][j] =
+// popcount(column i & column j): the device holds the counters and one upload chunk, never the input's matrix.
+struct CompareInput {
+    std::string path;
+    Bigsi meta;          // header, colours and n_ref_kmers; no device index
+    uint64_t n_rows = 0;
+};
+void compare_check(const std::string &in_path, CompareInput &in);
+std::vector<uint64_t> compare_records(cid_ctx *ctx, const CompareInput &in);
 Bigsi build_single(cid_ctx *ctx, const std::string &ref_tsv, uint64_t bloom, uint64_t hashes, uint64_t k, uint8_t quality,
                    int64_t cutoff, int hash_variant, uint64_t m_size = 0);   // build.rs:15-130; m_size > 0: build_single_mini :396-492
 

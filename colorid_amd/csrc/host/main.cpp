@@ -5,7 +5,8 @@
 // the query is sharded over the GPUs), --hash xxh3_v08|xxh3_v07.  Extra commands:
 // hashcheck (which hash variant was an index built with); merge (indices of one shape and disjoint accessions as one index, the
 // file `build` writes over the union of their reference lists); subset (chosen accessions of an index as an index of their own, the
-// file `build` writes over the kept lines of the reference list).
+// file `build` writes over the kept lines of the reference list); compare (all-pairs similarity of an index's accessions: which of
+// them are duplicates — the question before `subset -x`).
 // Minimizer indices (.mxi): build -m [-v M], info, read_id, batch_id.  Not provided (outside the query path): read_filter.
 #include <cctype>
 #include <cerrno>
@@ -390,6 +391,117 @@ int cmd_subset(int argc, char **argv) {
     return 0;
 }
 
+// compare: -i idx.bxi|idx.mxi -o PREFIX [-t MIN_JACCARD] [-d DUP_JACCARD]: every accession's Bloom filter against every other's, from the
+// index alone.  shared[i][j] = popcount(column i & column j) is counted on the GPU (cid_pairs_*) while the records stream through it one
+// upload chunk at a time; the reports follow from it in double arithmetic.  With a = bits[i], b = bits[j], s = shared[i][j], u = a + b - s:
+//   PREFIX_accessions.tsv  accession, n_ref_kmers, bits, fill = bits/M, fp_stated = false_prob(M, N, n_ref_kmers) (as `info`), fp_measured = fill^N
+//   PREFIX_pairs.tsv       a, b, shared, jaccard_bits = s/u, jaccard_kmers — every i < j with jaccard_bits >= -t (default 0: all), by (i, j).
+//                          jaccard_kmers takes the Bloom cardinality estimate card(x) = -(M/N) ln(1 - x/M): max(0, card(a) + card(b) - card(u)) / card(u)
+//                          (0 when card(u) = 0; `nan` when u = M, a saturated union)
+//   PREFIX_duplicates.txt  (-d T) colour j is a duplicate when an earlier colour that is not itself one has jaccard_bits >= T: a `subset -x` list
+// Everything that would refuse it is checked on the header and the n_ref_kmers tail before the GPU is opened, but counters that do not fit.
+namespace {
+double compare_threshold(const Args &a, const char *key, char letter, double dflt) {
+    if (!a.has(key)) return dflt;
+    const std::string &s = a.one(key);
+    char *end = nullptr;
+    const double v = strtod(s.c_str(), &end);
+    if (s.empty() || *end || !(v >= 0.0 && v <= 1.0)) die("compare: -%c/--%s expects a number in [0, 1], got '%s'", letter, key, s.c_str());
+    return v;
+}
+FILE *compare_out(const std::string &path) {
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) die("compare: could not create %s", path.c_str());
+    setvbuf(f, nullptr, _IOFBF, 1u << 20);
+    return f;
+}
+void compare_close(FILE *f, const std::string &path) {
+    if (fclose(f) != 0) die("compare: writing %s failed", path.c_str());
+}
+}  // namespace
+
+int cmd_compare(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {{'i', "input", true, true}, {'o', "output", true, false}, {'t', "min_jaccard", true, false},
+                                         {'d', "duplicates", true, false}, {0, "device", true, false}});
+    for (const char *req : {"input", "output"})
+        if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
+    const std::vector<std::string> &paths = a.values.at("input");
+    if (paths.size() != 1) die("compare takes exactly one input index (-i idx.bxi), got %zu: %s ...", paths.size(), paths[1].c_str());
+    const double min_jaccard = compare_threshold(a, "min_jaccard", 't', 0.0);
+    const bool want_dups = a.has("duplicates");
+    const double dup_jaccard = compare_threshold(a, "duplicates", 'd', 1.0);
+    const std::string &prefix = a.one("output");
+    CompareInput in;
+    compare_check(paths[0], in);
+    phase_done("input checked");
+    const Bigsi &b = in.meta;
+    printf(" Input index : %s\nK-mer size: %llu\nBloom filter parameters: num hashes %llu, filter size %llu\n", in.path.c_str(),
+           (unsigned long long)b.k_size, (unsigned long long)b.num_hash, (unsigned long long)b.bloom_size);
+    if (b.m_size) printf("Build with minimizers, minimizer size: %llu\n", (unsigned long long)b.m_size);
+    const size_t nc = b.colors.size();
+    printf("Accessions: %zu, rows: %llu\n", nc, (unsigned long long)in.n_rows);
+    bigsi_read_ahead(in.path);   // pages come in beside the runtime's start-up, as for `search`
+    cid_ctx *ctx = make_ctx(a);
+    phase_done("GPU context");
+    const std::vector<uint64_t> shared = compare_records(ctx, in);
+    phase_done("records streamed and counted");
+    const double M = (double)b.bloom_size, N = (double)b.num_hash;
+    auto jaccard_bits = [&](size_t i, size_t j) {
+        const double s = (double)shared[i * nc + j], u = (double)shared[i * nc + i] + (double)shared[j * nc + j] - s;
+        return u == 0.0 ? 0.0 : s / u;
+    };
+    auto card = [&](double x) { return -(M / N) * std::log(1.0 - x / M); };
+    {
+        const std::string path = prefix + "_accessions.tsv";
+        FILE *f = compare_out(path);
+        fprintf(f, "accession\tn_ref_kmers\tbits\tfill\tfp_stated\tfp_measured\n");
+        for (size_t c = 0; c < nc; ++c) {
+            const double fill = (double)shared[c * nc + c] / M;
+            fprintf(f, "%s\t%llu\t%llu\t%.6f\t%.6f\t%.6f\n", b.colors[c].c_str(), (unsigned long long)b.n_ref_kmers[c],
+                    (unsigned long long)shared[c * nc + c], fill, false_prob(M, N, (double)b.n_ref_kmers[c]), std::pow(fill, N));
+        }
+        compare_close(f, path);
+    }
+    uint64_t reported = 0;
+    {
+        const std::string path = prefix + "_pairs.tsv";
+        FILE *f = compare_out(path);
+        fprintf(f, "a\tb\tshared\tjaccard_bits\tjaccard_kmers\n");
+        for (size_t i = 0; i < nc; ++i)
+            for (size_t j = i + 1; j < nc; ++j) {
+                const double jb = jaccard_bits(i, j);
+                if (!(jb >= min_jaccard)) continue;
+                const double x = (double)shared[i * nc + i], y = (double)shared[j * nc + j], s = (double)shared[i * nc + j], u = x + y - s;
+                ++reported;
+                if (u == M) {   // a saturated union: its cardinality estimate is infinite
+                    fprintf(f, "%s\t%s\t%llu\t%.6f\tnan\n", b.colors[i].c_str(), b.colors[j].c_str(), (unsigned long long)shared[i * nc + j], jb);
+                    continue;
+                }
+                const double cu = card(u);
+                const double jk = cu == 0.0 ? 0.0 : std::max(0.0, card(x) + card(y) - cu) / cu;
+                fprintf(f, "%s\t%s\t%llu\t%.6f\t%.6f\n", b.colors[i].c_str(), b.colors[j].c_str(), (unsigned long long)shared[i * nc + j], jb, jk);
+            }
+        compare_close(f, path);
+    }
+    printf("Pairs reported: %llu of %llu\n", (unsigned long long)reported, (unsigned long long)((uint64_t)nc * (nc - 1) / 2));
+    if (want_dups) {
+        std::vector<char> dup(nc, 0);
+        size_t n_dup = 0;
+        const std::string path = prefix + "_duplicates.txt";
+        FILE *f = compare_out(path);
+        for (size_t j = 0; j < nc; ++j) {
+            for (size_t i = 0; i < j && !dup[j]; ++i)
+                if (!dup[i] && jaccard_bits(i, j) >= dup_jaccard) dup[j] = 1;
+            if (dup[j]) { ++n_dup; fprintf(f, "%s\n", b.colors[j].c_str()); }
+        }
+        compare_close(f, path);
+        printf("Duplicates: %zu of %zu accessions\n", n_dup, nc);
+    }
+    phase_done("reports written");
+    cid_ctx_destroy(ctx);
+    return 0;
+}
+
 int cmd_search(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, with_common({{'b', "bigsi", true, false}, {'q', "query", true, true}, {'r', "reverse", true, true},
                                                      {'f', "filter", true, false}, {'p', "p_shared", true, false}, {'g', "gene_search", false, false},
@@ -675,12 +787,12 @@ int main(int argc, char **argv) {
     // src/main.rs:16-20: init_log() prints this banner on stdout before anything else
     printf("\n ************** initializing logger *****************\n\n");
     if (argc < 2) {
-        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset> [FLAGS]\n");
+        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|compare> [FLAGS]\n");
         return 1;
     }
     const std::string cmd = argv[1];
     if (cmd == "--help" || cmd == "-h" || cmd == "help") {
-        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
+        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|compare> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
                "ENVIRONMENT:\n"
                "    COLORID_FAST_EXIT=1      leave without the GPU runtime's teardown once the results are written, closed and flushed\n"
                "                             (-0.05 to -0.15 s per run); =0, or COLORID_FULL_TEARDOWN=1: always the orderly exit\n"
@@ -699,6 +811,7 @@ int main(int argc, char **argv) {
     if (cmd == "hashcheck") return leave(cmd_hashcheck(argc, argv));
     if (cmd == "merge") return leave(cmd_merge(argc, argv));
     if (cmd == "subset") return leave(cmd_subset(argc, argv));
+    if (cmd == "compare") return leave(cmd_compare(argc, argv));
     if (cmd == "debug-kmers") return cmd_debug_kmers(argc, argv);
     if (cmd == "debug-records") return cmd_debug_records(argc, argv);
     if (cmd == "batch_id") return leave(cmd_batch_id(argc, argv));

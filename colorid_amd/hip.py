@@ -223,6 +223,43 @@ class Index:
         self.close()
 
 
+class Pairs:
+    """All-pairs accession similarity of one index shape (cid_pairs, `colorid compare`): shared[i][j] = popcount(column i & column j)."""
+
+    def __init__(self, ctx, bloom_size, n_colors):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.m, self.n_colors = bloom_size, n_colors
+        self.w32 = (n_colors + 31) // 32
+        h = vp()
+        check(self.lib.cid_pairs_create(ctx.h, bloom_size, n_colors, C.byref(h)))
+        self.h = h
+        ctx._children.add(self)
+
+    def add_records(self, records: bytes):
+        """raw .bxi records of this shape (one chunk of a file), added to the counters"""
+        rec = 24 + 4 * self.w32
+        assert len(records) % rec == 0
+        buf = np.frombuffer(records, np.uint8) if len(records) else np.zeros(1, np.uint8)
+        check(self.lib.cid_pairs_add_records(self.h, _p(buf), len(records) // rec))
+
+    def add_index(self, index):
+        """a finalized resident Index of the same shape, added to the counters"""
+        check(self.lib.cid_pairs_add_index(self.h, index.h))
+
+    def fetch(self):
+        out = np.zeros((self.n_colors, self.n_colors), np.uint64)
+        check(self.lib.cid_pairs_fetch(self.h, _p(out)))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.cid_pairs_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
 class KmerSet:
     """Device-resident distinct canonical k-mers with multiplicities (cid_kmerset, k <= 32)."""
 

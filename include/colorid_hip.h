@@ -137,6 +137,28 @@ int cid_index_insert_kmers_dev(cid_index *, const uint8_t *d_kmers, const uint32
 CID_CORE int cid_index_insert_kmers(cid_index *, const uint8_t *kmers, uint32_t colour, size_t n_kmers);
 CID_CORE void cid_index_destroy(cid_index *);
 
+/* ---- `colorid compare` (no reference counterpart): all-pairs similarity of an index's accessions.  Column c of the bloom_size x
+ *      n_colors bit matrix is accession c's Bloom filter; the counters are its Gram matrix, shared[i][j] = popcount(column i & column j):
+ *      the diagonal is the filter's population count, and fill, measured false-positive rate and the Jaccard index of any two filters
+ *      follow from it.  Integer sums: exact and independent of scheduling. ---- */
+typedef struct cid_pairs cid_pairs; /* device-resident n_colors x n_colors u64 counters of one index shape, zero when created */
+/* CID_ERR_UNSUPPORTED (the message states the byte count) when the 8 * n_colors^2 bytes of counters do not fit in free device memory
+ * beside one 256 MiB upload chunk of records; CID_ERR_INVALID for a null argument or a zero parameter. */
+int cid_pairs_create(cid_ctx *, uint64_t bloom_size, uint32_t n_colors, cid_pairs **out);
+/* Rows as they sit in a .bxi/.mxi file of this shape (cid_index_put_records' format), ADDED to the counters: one chunk of a file, any
+ * record count from 0 up; a file holds each row once, so the chunks of one file in any order and any split count the file.  The
+ * records are taken as cid_index_put_records_subset takes them (256 MiB pieces through the ctx's upload buffer) and checked as
+ * cid_index_put_records checks them, on the device, before a piece is counted: a refused piece adds nothing.  Device memory: the
+ * counters and one upload chunk, never the file's matrix.
+ * CID_ERR_INVALID: null argument or malformed record (cid_index_put_records' message). */
+int cid_pairs_add_records(cid_pairs *, const uint8_t *records, size_t n_records);
+/* The same from a resident index of the same bloom_size and n_colors on the same device (its all-zero rows add nothing).
+ * CID_ERR_INVALID: null argument, an index of another shape, or one that is not finalized. */
+int cid_pairs_add_index(cid_pairs *, const cid_index *);
+/* shared: n_colors x n_colors u64, row-major, symmetric (the device counts i <= j; the other triangle is mirrored here). */
+int cid_pairs_fetch(cid_pairs *, uint64_t *shared);
+void cid_pairs_destroy(cid_pairs *);
+
 /* ---- a5: proportional search, the hot loop of batch_search_pe::batch_search
  *      (src/batch_search_pe.rs:45-84 and :125-164).  For each distinct k-mer: n hashes -> n rows -> AND;
  *      hits[c] += 1 for every set colour c; if exactly one colour is set: n_unique[c] += 1,
