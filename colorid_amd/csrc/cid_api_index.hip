@@ -6,6 +6,7 @@ using cid::aligned16;
 using cid::fail;
 using cid::pick_tiles_per_block;
 using cid::slot_reserve;
+using cid::stage_records;
 using namespace cid::slots;
 
 namespace cid {
@@ -27,6 +28,14 @@ int check_ready(const cid_ctx *c, const cid_index *ix) {
 // function", src/main.rs:569-573)
 int check_not_mini(const cid_index *ix) {
     return ix->m_size ? fail(CID_ERR_UNSUPPORTED, "search on a minimizer (.mxi) index is not defined by the reference") : CID_OK;
+}
+// a Bloom insert of n_kmers k-mers into ix; the caller names the k-mers (kmers or codes) and their colour (colour or colour_of_kmer)
+static InsertParams insert_params(const cid_index *ix, size_t n_kmers) {
+    InsertParams p{};
+    p.mat = ix->mat; p.rs = ix->rs; p.n_hash = ix->n_hash; p.k = ix->k; p.n_colors = ix->n_colors;
+    p.tiles_per_block = pick_tiles_per_block(ix->ctx, n_kmers);
+    p.m_size = ix->m_size; p.mod = ix->mod; p.n_kmers = n_kmers;
+    return p;
 }
 }  // namespace cid
 
@@ -86,8 +95,7 @@ int cid_index_put_rows(cid_index *ix, const uint64_t *row_ids, const uint32_t *w
     if (ix->finalized) return fail(CID_ERR_STATE, "index already finalized");
     cid_ctx *c = ix->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    const uint32_t tail_bits = ix->n_colors % 32;
-    const uint32_t tail_mask = tail_bits ? ((1u << tail_bits) - 1u) : 0xFFFFFFFFu;
+    const uint32_t tail_mask = cid::tail_mask(ix->n_colors);
     for (size_t i = 0; i < n_rows; ++i) {
         if (row_ids[i] >= ix->m) return fail(CID_ERR_INVALID, "row id %llu >= bloom_size", (unsigned long long)row_ids[i]);
         if (words_le[i * ix->w32 + ix->w32 - 1] & ~tail_mask) return fail(CID_ERR_INVALID, "row %llu has bits beyond n_colors", (unsigned long long)row_ids[i]);
@@ -120,27 +128,9 @@ int cid::index_put_records_slice(cid_index *ix, const uint8_t *records, size_t n
     cid_ctx *c = ix->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t w32_rec = (n_colors_total + 31u) / 32u;
-    const size_t rec_bytes = 24 + 4ull * w32_rec;
-    const size_t batch = (256u << 20) / rec_bytes;   // records per upload
-    for (size_t r0 = 0; r0 < n_records; r0 += batch) {
-        const size_t nr = n_records - r0 < batch ? n_records - r0 : batch;
-        void *d_rec, *d_err;
-        int rc = slot_reserve(c, S_WORDS, nr * rec_bytes, &d_rec);
-        if (rc) return rc;
-        rc = slot_reserve(c, S_MISC, 16, &d_err);
-        if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_rec, records + r0 * rec_bytes, nr * rec_bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(cid::launch_put_records(ix->mat, ix->rs, (const uint32_t *)d_rec, w32_rec, colour_base / 32u, ix->w32, nr, ix->m, n_colors_total,
-                                        (uint32_t *)d_err, c->stream));
-        uint32_t err = 0;
-        HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (err)
-            return fail(CID_ERR_INVALID, "malformed row record(s):%s%s%s%s", (err & 1) ? " word count != ceil(n_colors/32)" : "",
-                        (err & 2) ? " bit count != n_colors" : "", (err & 4) ? " row >= bloom_size" : "", (err & 8) ? " bits beyond n_colors" : "");
-    }
-    return CID_OK;
+    return stage_records(c, records, n_records, w32_rec, ix->w32, [&](const uint32_t *d_rec, size_t nr, uint32_t *d_err) {
+        return cid::launch_put_records(ix->mat, ix->rs, d_rec, w32_rec, colour_base / 32u, ix->w32, nr, ix->m, n_colors_total, d_err, c->stream);
+    });
 }
 
 extern "C" {
@@ -169,33 +159,15 @@ int cid_index_put_records_mapped(cid_index *ix, const uint8_t *records, size_t n
     cid_ctx *c = ix->ctx;
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t w32_rec = (n_colors_file + 31u) / 32u;
-    const size_t rec_bytes = 24 + 4ull * w32_rec;
     const uint32_t n_plan = (uint32_t)plan.size();
-    // records per upload: 256 MiB of them, and no more than 2^30 threads a launch
-    const size_t batch = std::min<size_t>((256u << 20) / rec_bytes, (1ull << 30) / n_plan);
     void *d_plan;
     int rc = slot_reserve(c, S_ROWIDS, plan.size() * sizeof(cid::MergePlan), &d_plan);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(d_plan, plan.data(), plan.size() * sizeof(cid::MergePlan), hipMemcpyHostToDevice, c->stream));
-    for (size_t r0 = 0; r0 < n_records; r0 += batch) {
-        const size_t nr = n_records - r0 < batch ? n_records - r0 : batch;
-        void *d_rec, *d_err;
-        rc = slot_reserve(c, S_WORDS, nr * rec_bytes, &d_rec);
-        if (rc) return rc;
-        rc = slot_reserve(c, S_MISC, 16, &d_err);
-        if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_rec, records + r0 * rec_bytes, nr * rec_bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(cid::launch_put_records_mapped(ix->mat, ix->rs, (const uint32_t *)d_rec, w32_rec, (const cid::MergePlan *)d_plan, n_plan, nr, ix->m,
-                                               n_colors_file, (uint32_t *)d_err, c->stream));
-        uint32_t err = 0;
-        HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (err)
-            return fail(CID_ERR_INVALID, "malformed row record(s):%s%s%s%s", (err & 1) ? " word count != ceil(n_colors/32)" : "",
-                        (err & 2) ? " bit count != n_colors" : "", (err & 4) ? " row >= bloom_size" : "", (err & 8) ? " bits beyond n_colors" : "");
-    }
-    return CID_OK;
+    return stage_records(c, records, n_records, w32_rec, n_plan, [&](const uint32_t *d_rec, size_t nr, uint32_t *d_err) {
+        return cid::launch_put_records_mapped(ix->mat, ix->rs, d_rec, w32_rec, (const cid::MergePlan *)d_plan, n_plan, nr, ix->m, n_colors_file,
+                                              d_err, c->stream);
+    });
 }
 
 // `subset`: the k-th set bit of keep_words (a bitmap over the file's colours) becomes index colour k.  The bitmap becomes a plan once per
@@ -206,8 +178,7 @@ int cid_index_put_records_subset(cid_index *ix, const uint8_t *records, size_t n
     if (ix->finalized) return fail(CID_ERR_STATE, "index already finalized");
     if (n_colors_file == 0) return fail(CID_ERR_INVALID, "a file of 0 colours");
     const uint32_t w32_rec = (n_colors_file + 31u) / 32u;
-    const uint32_t tail_bits = n_colors_file % 32u;
-    if (tail_bits && (keep_words[w32_rec - 1] >> tail_bits))
+    if (keep_words[w32_rec - 1] & ~cid::tail_mask(n_colors_file))
         return fail(CID_ERR_INVALID, "keep bitmap has a bit at or beyond the file's %u colours", n_colors_file);
     std::vector<cid::SubsetItem> items;
     std::vector<uint64_t> before;   // kept bits before each item
@@ -230,35 +201,17 @@ int cid_index_put_records_subset(cid_index *ix, const uint8_t *records, size_t n
     if (n_records == 0) return CID_OK;
     cid_ctx *c = ix->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t rec_bytes = 24 + 4ull * w32_rec;
-    // records per upload: 256 MiB of them, and no more than 2^30 threads a launch
-    const size_t batch = std::min<size_t>((256u << 20) / rec_bytes, (1ull << 30) / ix->w32);
     const size_t words_bytes = words.size() * sizeof(cid::SubsetWord), items_bytes = items.size() * sizeof(cid::SubsetItem);
     void *d_plan;
     int rc = slot_reserve(c, S_ROWIDS, words_bytes + items_bytes, &d_plan);   // the words (16 B each), then the items (8 B each)
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(d_plan, words.data(), words_bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync((uint8_t *)d_plan + words_bytes, items.data(), items_bytes, hipMemcpyHostToDevice, c->stream));
-    for (size_t r0 = 0; r0 < n_records; r0 += batch) {
-        const size_t nr = n_records - r0 < batch ? n_records - r0 : batch;
-        void *d_rec, *d_err;
-        rc = slot_reserve(c, S_WORDS, nr * rec_bytes, &d_rec);
-        if (rc) return rc;
-        rc = slot_reserve(c, S_MISC, 16, &d_err);
-        if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_rec, records + r0 * rec_bytes, nr * rec_bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(cid::launch_put_records_subset(ix->mat, ix->rs, (const uint32_t *)d_rec, w32_rec, (const cid::SubsetWord *)d_plan,
-                                               (const cid::SubsetItem *)((const uint8_t *)d_plan + words_bytes), ix->w32, nr, ix->m, n_colors_file,
-                                               (uint32_t *)d_err, c->stream));
-        uint32_t err = 0;
-        HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (err)
-            return fail(CID_ERR_INVALID, "malformed row record(s):%s%s%s%s", (err & 1) ? " word count != ceil(n_colors/32)" : "",
-                        (err & 2) ? " bit count != n_colors" : "", (err & 4) ? " row >= bloom_size" : "", (err & 8) ? " bits beyond n_colors" : "");
-    }
-    return CID_OK;
+    return stage_records(c, records, n_records, w32_rec, ix->w32, [&](const uint32_t *d_rec, size_t nr, uint32_t *d_err) {
+        return cid::launch_put_records_subset(ix->mat, ix->rs, d_rec, w32_rec, (const cid::SubsetWord *)d_plan,
+                                              (const cid::SubsetItem *)((const uint8_t *)d_plan + words_bytes), ix->w32, nr, ix->m, n_colors_file,
+                                              d_err, c->stream);
+    });
 }
 
 int cid_index_device_matrix(cid_index *ix, void **dev_ptr, uint64_t *row_stride_words) {
@@ -308,11 +261,8 @@ int cid_index_insert_kmers_dev(cid_index *ix, const uint8_t *d_kmers, const uint
     if (!aligned16(d_kmers)) return fail(CID_ERR_INVALID, "d_kmers must be 16-byte aligned");
     cid_ctx *c = ix->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    cid::InsertParams p{};
-    p.mat = ix->mat; p.rs = ix->rs; p.n_hash = ix->n_hash; p.k = ix->k; p.n_colors = ix->n_colors;
-    p.tiles_per_block = pick_tiles_per_block(c, n_kmers);
-    p.m_size = ix->m_size;
-    p.mod = ix->mod; p.kmers = d_kmers; p.colour_of_kmer = d_colour_of_kmer; p.n_kmers = n_kmers;
+    cid::InsertParams p = cid::insert_params(ix, n_kmers);
+    p.kmers = d_kmers; p.colour_of_kmer = d_colour_of_kmer;
     HIP_TRY(cid::launch_insert_kmers(p, c->stream));
     return CID_OK;
 }
@@ -327,11 +277,8 @@ int cid_index_insert_kmers(cid_index *ix, const uint8_t *kmers, uint32_t colour,
     int rc = slot_reserve(c, S_KMERS, n_kmers * ix->k, &d_k);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(d_k, kmers, n_kmers * ix->k, hipMemcpyHostToDevice, c->stream));
-    cid::InsertParams p{};
-    p.mat = ix->mat; p.rs = ix->rs; p.n_hash = ix->n_hash; p.k = ix->k; p.n_colors = ix->n_colors;
-    p.tiles_per_block = pick_tiles_per_block(c, n_kmers);
-    p.colour = colour; p.m_size = ix->m_size;
-    p.mod = ix->mod; p.kmers = (const uint8_t *)d_k; p.colour_of_kmer = nullptr; p.n_kmers = n_kmers;
+    cid::InsertParams p = cid::insert_params(ix, n_kmers);
+    p.kmers = (const uint8_t *)d_k; p.colour = colour;
     HIP_TRY(cid::launch_insert_kmers(p, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CID_OK;
@@ -361,10 +308,8 @@ int index_insert_codes(cid_index *ix, const uint64_t *d_codes, size_t n, uint32_
     if (colour >= ix->n_colors) return fail(CID_ERR_INVALID, "colour %u >= n_colors", colour);
     cid_ctx *c = ix->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    cid::InsertParams p{};
-    p.mat = ix->mat; p.rs = ix->rs; p.n_hash = ix->n_hash; p.k = ix->k; p.n_colors = ix->n_colors;
-    p.tiles_per_block = pick_tiles_per_block(c, n);
-    p.colour = colour; p.m_size = ix->m_size; p.mod = ix->mod; p.codes = d_codes; p.n_kmers = n;
+    InsertParams p = insert_params(ix, n);
+    p.codes = d_codes; p.colour = colour;
     HIP_TRY(cid::launch_insert_kmers(p, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CID_OK;
@@ -376,10 +321,8 @@ int index_insert_ascii(cid_index *ix, const uint8_t *d_ascii, size_t n, uint32_t
     if (colour >= ix->n_colors) return fail(CID_ERR_INVALID, "colour %u >= n_colors", colour);
     cid_ctx *c = ix->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    cid::InsertParams p{};
-    p.mat = ix->mat; p.rs = ix->rs; p.n_hash = ix->n_hash; p.k = ix->k; p.n_colors = ix->n_colors;
-    p.tiles_per_block = pick_tiles_per_block(c, n);
-    p.colour = colour; p.m_size = ix->m_size; p.mod = ix->mod; p.kmers = d_ascii; p.n_kmers = n;
+    InsertParams p = insert_params(ix, n);
+    p.kmers = d_ascii; p.colour = colour;
     HIP_TRY(cid::launch_insert_kmers(p, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CID_OK;

@@ -3,8 +3,6 @@
 #include "cid_api_common.hpp"
 
 using cid::fail;
-using cid::slot_reserve;
-using namespace cid::slots;
 
 extern "C" {
 
@@ -34,38 +32,26 @@ int cid_pairs_create(cid_ctx *c, uint64_t bloom_size, uint32_t n_colors, cid_pai
     return CID_OK;
 }
 
-// One call's records, staged as cid_index_put_records_subset stages them: 256 MiB pieces through the ctx's upload slot, each checked on
-// the device (k_pairs_check) before it is counted (k_pairs), so a refused piece adds nothing.
+// One call's records through cid::stage_records: each piece is checked on the device (k_pairs_check) before it is counted (k_pairs), so a
+// refused piece adds nothing.
 int cid_pairs_add_records(cid_pairs *pr, const uint8_t *records, size_t n_records) {
     if (!pr || (n_records && !records)) return fail(CID_ERR_INVALID, "null argument");
     if (n_records == 0) return CID_OK;
     cid_ctx *c = pr->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t rec_bytes = 24 + 4ull * pr->w32;
-    const size_t batch = std::max<size_t>(1, (256u << 20) / rec_bytes);   // records per upload
-    for (size_t r0 = 0; r0 < n_records; r0 += batch) {
-        const size_t nr = n_records - r0 < batch ? n_records - r0 : batch;
-        void *d_rec, *d_err;
-        int rc = slot_reserve(c, S_WORDS, nr * rec_bytes, &d_rec);
-        if (rc) return rc;
-        rc = slot_reserve(c, S_MISC, 16, &d_err);
-        if (rc) return rc;
-        HIP_TRY(hipMemsetAsync(d_err, 0, 4, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_rec, records + r0 * rec_bytes, nr * rec_bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(cid::launch_pairs_check((const uint32_t *)d_rec, pr->w32, nr, pr->m, pr->n_colors, (uint32_t *)d_err, c->stream));
-        uint32_t err = 0;
-        HIP_TRY(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (err)
-            return fail(CID_ERR_INVALID, "malformed row record(s):%s%s%s%s", (err & 1) ? " word count != ceil(n_colors/32)" : "",
-                        (err & 2) ? " bit count != n_colors" : "", (err & 4) ? " row >= bloom_size" : "", (err & 8) ? " bits beyond n_colors" : "");
-        cid::PairsParams p{};
-        p.rows = (const uint32_t *)d_rec; p.stride = 6ull + pr->w32; p.off = 4; p.w32 = pr->w32; p.n_rows = nr;
-        p.n_colors = pr->n_colors; p.shared = pr->shared;
-        HIP_TRY(cid::launch_pairs(p, c->n_cu, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));   // the slot is the next piece's (and the next call's) upload buffer
-    }
-    return CID_OK;
+    return cid::stage_records(
+        c, records, n_records, pr->w32, 1,
+        [&](const uint32_t *d_rec, size_t nr, uint32_t *d_err) {
+            return cid::launch_pairs_check(d_rec, pr->w32, nr, pr->m, pr->n_colors, d_err, c->stream);
+        },
+        [&](const uint32_t *d_rec, size_t nr) {
+            cid::PairsParams p{};
+            p.rows = d_rec; p.stride = cid::record_words(pr->w32); p.off = cid::kRecordPayload; p.w32 = pr->w32; p.n_rows = nr;
+            p.n_colors = pr->n_colors; p.shared = pr->shared;
+            HIP_TRY(cid::launch_pairs(p, c->n_cu, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            return (int)CID_OK;
+        });
 }
 
 int cid_pairs_add_index(cid_pairs *pr, const cid_index *ix) {

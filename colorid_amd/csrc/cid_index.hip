@@ -1,5 +1,6 @@
 // Index maintenance kernels for MI355X (gfx950): .bxi rows <-> dense matrix, Bloom insert (simple_bloom.rs:19-26).
 #include "cid_gather.hpp"
+#include "cid_records.hpp"
 
 namespace cid {
 
@@ -15,27 +16,23 @@ __global__ void k_put_rows(uint32_t *mat32, uint32_t rs, const uint64_t *row_ids
     mat32[row_ids[r] * (2ull * rs) + w] = words[i];
 }
 
-// The same from the file's own bytes: record i = { u64 row ; u64 n_words ; n_words x u32 ; u64 n_bits } (bincode of
-// (usize, BitVec)), rec_bytes = 24 + 4*w32_rec, every field 4-byte aligned.  The index takes the record's
+// The same from the file's own bytes, record by record (layout and check: cid_records.hpp).  The index takes the record's
 // words [w_off, w_off + w32_take) — all of them, or its colour stripe of a wider file (cid_group_stripes_put_records).  One
 // thread per (record, taken word); word 0's thread also checks the record against the FILE's shape (w32_rec words, n_colors
-// bits).  err[0] |= 1 bad word count, 2 bad bit count, 4 row >= bloom_size, 8 bits past n_colors.
+// bits): err[0] |= check_record's bits.
 __global__ void k_put_records(uint32_t *mat32, uint32_t rs, const uint32_t *rec32, uint32_t w32_rec, uint32_t w_off, uint32_t w32_take,
                               uint64_t n_records, uint64_t bloom_size, uint32_t n_colors, uint32_t tail_mask, uint32_t *err) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_records * w32_take) return;
     const uint64_t r = i / w32_take;
     const uint32_t w = (uint32_t)(i % w32_take);
-    const uint32_t *rec = rec32 + r * (6ull + w32_rec);
-    const uint64_t row = (uint64_t)rec[0] | ((uint64_t)rec[1] << 32);
+    const uint32_t *rec = rec32 + r * record_words(w32_rec);
+    const uint64_t row = record_row(rec);
     if (w == 0) {
-        const uint64_t nw = (uint64_t)rec[2] | ((uint64_t)rec[3] << 32);
-        const uint64_t nbits = (uint64_t)rec[4 + w32_rec] | ((uint64_t)rec[5 + w32_rec] << 32);
-        uint32_t e = (nw != w32_rec ? 1u : 0u) | (nbits != n_colors ? 2u : 0u) | (row >= bloom_size ? 4u : 0u) |
-                     ((rec[4 + w32_rec - 1] & ~tail_mask) ? 8u : 0u);
+        const uint32_t e = check_record(rec, row, w32_rec, n_colors, bloom_size, tail_mask);
         if (e) atomicOr(err, e);
     }
-    if (row < bloom_size) mat32[row * (2ull * rs) + w] = rec[4 + w_off + w];
+    if (row < bloom_size) mat32[row * (2ull * rs) + w] = rec[kRecordPayload + w_off + w];
 }
 
 // `merge`: the records of a file with n_colors_file colours OR-ed into a wider index through an increasing colour map.  The file
@@ -50,35 +47,22 @@ __global__ void k_put_records_mapped(uint32_t *mat32, uint32_t rs, const uint32_
     if (i >= n_records * n_plan) return;
     const uint64_t r = i / n_plan;
     const uint32_t j = (uint32_t)(i % n_plan);
-    const uint32_t *rec = rec32 + r * (6ull + w32_rec);
-    const uint64_t row = (uint64_t)rec[0] | ((uint64_t)rec[1] << 32);
+    const uint32_t *rec = rec32 + r * record_words(w32_rec);
+    const uint64_t row = record_row(rec);
     if (j == 0) {
-        const uint64_t nw = (uint64_t)rec[2] | ((uint64_t)rec[3] << 32);
-        const uint64_t nbits = (uint64_t)rec[4 + w32_rec] | ((uint64_t)rec[5 + w32_rec] << 32);
-        uint32_t e = (nw != w32_rec ? 1u : 0u) | (nbits != n_colors_file ? 2u : 0u) | (row >= bloom_size ? 4u : 0u) |
-                     ((rec[4 + w32_rec - 1] & ~tail_mask) ? 8u : 0u);
+        const uint32_t e = check_record(rec, row, w32_rec, n_colors_file, bloom_size, tail_mask);
         if (e) atomicOr(err, e);
     }
     if (row >= bloom_size) return;
     const MergePlan p = plan[j];
     const uint32_t n = __builtin_popcount(p.mask);
     const uint32_t s0 = p.lo >> 5, sh = p.lo & 31u;
-    const uint32_t lo_word = rec[4 + s0];
-    const uint32_t hi_word = sh + n > 32u ? rec[4 + s0 + 1] : 0u;   // (the run ends inside the file's colours: s0 + 1 < w32_rec)
+    const uint32_t lo_word = rec[kRecordPayload + s0];
+    const uint32_t hi_word = sh + n > 32u ? rec[kRecordPayload + s0 + 1] : 0u;   // (the run ends inside the file's colours: s0 + 1 < w32_rec)
     uint32_t bits = __builtin_amdgcn_alignbit(hi_word, lo_word, sh);   // (hi:lo) >> sh
-    if (n < 32u) bits &= (1u << n) - 1u;
+    bits &= low_bits(n);
     if (bits == 0) return;
-    uint32_t out = 0, m = p.mask;
-    while (m) {
-        const uint32_t at = __builtin_ctz(m);
-        const uint32_t rest = m >> at;
-        const uint32_t len = rest == 0xFFFFFFFFu ? 32u : (uint32_t)__builtin_ctz(~rest);
-        const uint32_t run = len == 32u ? 0xFFFFFFFFu : (1u << len) - 1u;
-        out |= (bits & run) << at;
-        bits = len == 32u ? 0u : bits >> len;
-        m &= ~(run << at);
-    }
-    mat32[row * (2ull * rs) + p.w] |= out;
+    mat32[row * (2ull * rs) + p.w] |= deposit_bits(bits, p.mask);
 }
 
 // `subset`: the kept colours of a file with n_colors_file colours, packed into a narrower index — the inverse of the deposit above (a
@@ -95,13 +79,10 @@ __global__ void k_put_records_subset(uint32_t *mat32, uint32_t rs, const uint32_
     if (i >= n_records * w32_out) return;
     const uint64_t r = i / w32_out;
     const uint32_t j = (uint32_t)(i % w32_out);
-    const uint32_t *rec = rec32 + r * (6ull + w32_rec);
-    const uint64_t row = (uint64_t)rec[0] | ((uint64_t)rec[1] << 32);
+    const uint32_t *rec = rec32 + r * record_words(w32_rec);
+    const uint64_t row = record_row(rec);
     if (j == 0) {
-        const uint64_t nw = (uint64_t)rec[2] | ((uint64_t)rec[3] << 32);
-        const uint64_t nbits = (uint64_t)rec[4 + w32_rec] | ((uint64_t)rec[5 + w32_rec] << 32);
-        uint32_t e = (nw != w32_rec ? 1u : 0u) | (nbits != n_colors_file ? 2u : 0u) | (row >= bloom_size ? 4u : 0u) |
-                     ((rec[4 + w32_rec - 1] & ~tail_mask) ? 8u : 0u);
+        const uint32_t e = check_record(rec, row, w32_rec, n_colors_file, bloom_size, tail_mask);
         if (e) atomicOr(err, e);
     }
     if (row >= bloom_size) return;
@@ -109,22 +90,11 @@ __global__ void k_put_records_subset(uint32_t *mat32, uint32_t rs, const uint32_
     uint32_t out = 0, filled = 0, drop = p.skip;
     for (uint32_t t = 0; t < p.n_items && filled < 32u; ++t) {
         const SubsetItem it = items[p.first + t];   // (it.s < w32_rec: the host made the items from the file's own words)
-        const uint32_t v = rec[4 + it.s];
-        uint32_t bits = 0, n = 0, m = it.mask;
-        while (m) {
-            const uint32_t at = __builtin_ctz(m);
-            const uint32_t rest = m >> at;
-            const uint32_t len = rest == 0xFFFFFFFFu ? 32u : (uint32_t)__builtin_ctz(~rest);
-            const uint32_t run = len == 32u ? 0xFFFFFFFFu : (1u << len) - 1u;
-            bits |= ((v >> at) & run) << n;   // (n < 32 while a run is left)
-            n += len;
-            m &= ~(run << at);
-        }
-        bits >>= drop;   // drop < popc(mask) <= 32 for the first item, 0 afterwards
-        n -= drop;
-        drop = 0;
+        uint32_t n;
+        const uint32_t bits = extract_bits(rec[kRecordPayload + it.s], it.mask, n) >> drop;   // drop < n <= 32 for the first item, 0 afterwards
         out |= bits << filled;
-        filled += n;
+        filled += n - drop;
+        drop = 0;
     }
     mat32[row * (2ull * rs) + j] = out;
 }
@@ -207,9 +177,8 @@ hipError_t launch_put_records(uint64_t *mat, uint32_t rs, const uint32_t *d_reco
                               uint64_t n_records, uint64_t bloom_size, uint32_t n_colors, uint32_t *d_err, hipStream_t stream) {
     const uint64_t n = n_records * w32_take;
     if (n == 0) return hipSuccess;
-    const uint32_t tail_bits = n_colors % 32;
     hipLaunchKernelGGL(k_put_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<uint32_t *>(mat), rs, d_records,
-                       w32_rec, w_off, w32_take, n_records, bloom_size, n_colors, tail_bits ? ((1u << tail_bits) - 1u) : 0xFFFFFFFFu, d_err);
+                       w32_rec, w_off, w32_take, n_records, bloom_size, n_colors, tail_mask(n_colors), d_err);
     return hipGetLastError();
 }
 
@@ -218,10 +187,8 @@ hipError_t launch_put_records_mapped(uint64_t *mat, uint32_t rs, const uint32_t 
                                      hipStream_t stream) {
     const uint64_t n = n_records * n_plan;
     if (n == 0) return hipSuccess;
-    const uint32_t tail_bits = n_colors_file % 32;
     hipLaunchKernelGGL(k_put_records_mapped, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<uint32_t *>(mat), rs,
-                       d_records, w32_rec, d_plan, n_plan, n_records, bloom_size, n_colors_file,
-                       tail_bits ? ((1u << tail_bits) - 1u) : 0xFFFFFFFFu, d_err);
+                       d_records, w32_rec, d_plan, n_plan, n_records, bloom_size, n_colors_file, tail_mask(n_colors_file), d_err);
     return hipGetLastError();
 }
 
@@ -230,10 +197,8 @@ hipError_t launch_put_records_subset(uint64_t *mat, uint32_t rs, const uint32_t 
                                      uint32_t n_colors_file, uint32_t *d_err, hipStream_t stream) {
     const uint64_t n = n_records * w32_out;
     if (n == 0) return hipSuccess;
-    const uint32_t tail_bits = n_colors_file % 32;
     hipLaunchKernelGGL(k_put_records_subset, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<uint32_t *>(mat), rs,
-                       d_records, w32_rec, d_words, d_items, w32_out, n_records, bloom_size, n_colors_file,
-                       tail_bits ? ((1u << tail_bits) - 1u) : 0xFFFFFFFFu, d_err);
+                       d_records, w32_rec, d_words, d_items, w32_out, n_records, bloom_size, n_colors_file, tail_mask(n_colors_file), d_err);
     return hipGetLastError();
 }
 

@@ -3,21 +3,18 @@
 #include <algorithm>
 
 #include "cid_kernels.hpp"
+#include "cid_records.hpp"
 
 namespace cid {
 
-// The records of one upload chunk against the file's shape, one thread per record: the checks and the err bits of k_put_records
-// (1 bad word count, 2 bad bit count, 4 row >= bloom_size, 8 bits past n_colors).  Run before k_pairs, so a refused chunk adds nothing.
+// The records of one upload chunk against the file's shape, one thread per record: err[0] |= check_record's bits (cid_records.hpp), as
+// the put kernels do.  Run before k_pairs, so a refused chunk adds nothing.
 __global__ void k_pairs_check(const uint32_t *rec32, uint32_t w32_rec, uint64_t n_records, uint64_t bloom_size, uint32_t n_colors,
                               uint32_t tail_mask, uint32_t *err) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_records) return;
-    const uint32_t *rec = rec32 + r * (6ull + w32_rec);
-    const uint64_t row = (uint64_t)rec[0] | ((uint64_t)rec[1] << 32);
-    const uint64_t nw = (uint64_t)rec[2] | ((uint64_t)rec[3] << 32);
-    const uint64_t nbits = (uint64_t)rec[4 + w32_rec] | ((uint64_t)rec[5 + w32_rec] << 32);
-    const uint32_t e = (nw != w32_rec ? 1u : 0u) | (nbits != n_colors ? 2u : 0u) | (row >= bloom_size ? 4u : 0u) |
-                       ((rec[4 + w32_rec - 1] & ~tail_mask) ? 8u : 0u);
+    const uint32_t *rec = rec32 + r * record_words(w32_rec);
+    const uint32_t e = check_record(rec, record_row(rec), w32_rec, n_colors, bloom_size, tail_mask);
     if (e) atomicOr(err, e);
 }
 
@@ -106,9 +103,8 @@ __global__ __launch_bounds__(kBlock) void k_pairs(PairsParams p) {
 hipError_t launch_pairs_check(const uint32_t *d_records, uint32_t w32_rec, uint64_t n_records, uint64_t bloom_size, uint32_t n_colors,
                               uint32_t *d_err, hipStream_t stream) {
     if (n_records == 0) return hipSuccess;
-    const uint32_t tail_bits = n_colors % 32;
     hipLaunchKernelGGL(k_pairs_check, dim3((unsigned)((n_records + 255) / 256)), dim3(256), 0, stream, d_records, w32_rec, n_records, bloom_size,
-                       n_colors, tail_bits ? ((1u << tail_bits) - 1u) : 0xFFFFFFFFu, d_err);
+                       n_colors, tail_mask(n_colors), d_err);
     return hipGetLastError();
 }
 

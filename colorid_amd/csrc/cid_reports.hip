@@ -14,6 +14,7 @@
 
 #include "../../include/colorid_hip.h"
 #include "cid_internal.hpp"
+#include "cid_records.hpp"
 #include "cid_scan.hpp"
 #include "cid_devbuf.hpp"
 
@@ -192,12 +193,12 @@ __global__ void k_emit_records(const uint32_t *mat32, uint32_t rs, uint32_t w32,
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || !flags[i]) return;
     const uint64_t row = row_begin + i;
-    uint32_t *rec = out32 + (uint64_t)pos[i] * (6ull + w32);
+    uint32_t *rec = out32 + (uint64_t)pos[i] * record_words(w32);
     rec[0] = (uint32_t)row; rec[1] = (uint32_t)(row >> 32);
     rec[2] = w32; rec[3] = 0;
     const uint32_t *src = mat32 + row * (2ull * rs);
-    for (uint32_t w = 0; w < w32; ++w) rec[4 + w] = src[w];
-    rec[4 + w32] = n_colors; rec[5 + w32] = 0;
+    for (uint32_t w = 0; w < w32; ++w) rec[kRecordPayload + w] = src[w];
+    rec[kRecordPayload + w32] = n_colors; rec[kRecordPayload + w32 + 1] = 0;
 }
 
 // host buffer `records` holds up to n_rows records; *n_records = the number written
@@ -207,7 +208,7 @@ int index_get_records(cid_ctx *c, const cid_index *ix, uint64_t row_begin, uint6
     if (n_rows >= (1ull << 32)) return fail(CID_ERR_INVALID, "at most 2^32-1 rows per call");
     hipStream_t st = ctx_stream(c);
     const uint32_t w32 = (index_n_colors(ix) + 31) / 32, rs = index_rs(ix);
-    const size_t rec = 24 + 4ull * w32;
+    const size_t rec = record_bytes(index_n_colors(ix));
     DevBuf<uint32_t> flags(c), pos(c);
     DevBuf<uint8_t> out(c), tmp(c);
     int rc;

@@ -13,6 +13,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "../cid_records.hpp"
 #include "colorid_host.hpp"
 
 namespace colorid {
@@ -187,7 +188,7 @@ uint64_t read_header(BufReader &r, const std::string &path, Bigsi &b) {
     return r.u64();
 }
 
-size_t record_bytes(const Bigsi &b) { return 24 + 4ull * ((b.colors.size() + 31) / 32); }
+size_t record_bytes(const Bigsi &b) { return cid::record_bytes(b.colors.size()); }
 
 // The file after its row records: n_ref_kmers by accession name, kept in colour order
 void read_tail(BufReader &r, Bigsi &b) {
@@ -293,14 +294,47 @@ Bigsi read_bigsi(cid_ctx *ctx, const std::string &path, int hash_variant, bool m
 
 namespace {
 
-// what `merge` and `subset` (cmd) check alike on an input's header
+// What `merge`, `subset` and `compare` (cmd) have in common: the input index of a command that streams row records.  Its checks read only
+// the header and the n_ref_kmers tail (the tail lies at header_end + n_rows x record_bytes), so a refusal costs no GPU context and no
+// pass over the rows.
 bool is_mxi(const std::string &p) { return p.size() >= 4 && p.compare(p.size() - 4, 4, ".mxi") == 0; }
 
-// the row records and the count of the n_ref_kmers tail must fit in the file
-void check_not_truncated(const char *cmd, const std::string &path, uint64_t n_rows, size_t rec, uint64_t header_end, uint64_t file_size) {
-    if (n_rows > file_size / rec || header_end + n_rows * rec + 8 > file_size)
-        die("%s: %s is truncated: %llu row records of %zu bytes from byte %llu do not fit in its %llu bytes", cmd, path.c_str(),
-            (unsigned long long)n_rows, rec, (unsigned long long)header_end, (unsigned long long)file_size);
+// The input exists and is not the file the command is about to write (out_path; `instead`: what to write elsewhere; null: the command
+// writes no index).  Returns the input's size in bytes.
+uint64_t stat_input(const char *cmd, const std::string &path, const std::string *out_path = nullptr, const char *instead = nullptr) {
+    struct stat st, out_st;
+    if (stat(path.c_str(), &st) != 0) die("Can't open index!: %s", path.c_str());
+    if (out_path && stat(out_path->c_str(), &out_st) == 0 && st.st_dev == out_st.st_dev && st.st_ino == out_st.st_ino)
+        die("%s: the output %s is the input %s: write the %s to another file", cmd, out_path->c_str(), path.c_str(), instead);
+    return (uint64_t)st.st_size;
+}
+
+// in.path's header and n_ref_kmers tail into in.meta, its number of row records into in.n_rows; the records and the count of the tail
+// must fit in the file's file_size bytes
+void read_input_meta(const char *cmd, IndexInput &in, uint64_t file_size) {
+    BufReader r(in.path, /*name_in_errors=*/true);
+    in.n_rows = read_header(r, in.path, in.meta);
+    const uint64_t header_end = r.tell();
+    const size_t rec = record_bytes(in.meta);
+    if (in.n_rows > file_size / rec || header_end + in.n_rows * rec + 8 > file_size)
+        die("%s: %s is truncated: %llu row records of %zu bytes from byte %llu do not fit in its %llu bytes", cmd, in.path.c_str(),
+            (unsigned long long)in.n_rows, rec, (unsigned long long)header_end, (unsigned long long)file_size);
+    r.seek(header_end + in.n_rows * rec);
+    read_tail(r, in.meta);
+}
+
+// The checked input's row records to `put`: the file is opened again and must still be what read_input_meta saw (how: "merged" / "read")
+void stream_input(const char *cmd, const char *how, const IndexInput &in, const std::function<int(const uint8_t *, size_t)> &put) {
+    BufReader r(in.path, /*name_in_errors=*/true);
+    Bigsi again;
+    if (read_header(r, in.path, again) != in.n_rows || again.colors != in.meta.colors) die("%s: %s changed while it was %s", cmd, in.path.c_str(), how);
+    stream_records(r, in.path, in.n_rows, record_bytes(in.meta), put);
+}
+
+// the index a command writes, made on ctx from its metadata: empty, not finalized
+void create_output_index(cid_ctx *ctx, Bigsi &out) {
+    CID_TRY(cid_index_create(ctx, out.bloom_size, (uint32_t)out.num_hash, (uint32_t)out.k_size, (uint32_t)out.colors.size(), CID_HASH_XXH3_V08, &out.index));
+    if (out.m_size) CID_TRY(cid_index_set_minimizer(out.index, (uint32_t)out.m_size));
 }
 
 // build numbers colours in name order (build.rs:105); colour c must not sort before colour c - 1
@@ -310,34 +344,25 @@ void check_name_order_at(const char *cmd, const std::string &path, const std::ve
             colors[c - 1].c_str(), colors[c].c_str(), cmd);
 }
 
+[[noreturn]] void die_accession_twice(const char *cmd, const std::string &path, const std::string &name) {
+    die("%s: %s holds accession %s twice", cmd, path.c_str(), name.c_str());
+}
+
 }  // namespace
 
-// merge: no counterpart in the reference.  Every check reads only the inputs' headers and n_ref_kmers tails (the tail lies at
-// header_end + n_rows x (24 + 4 W32)), so a refusal costs no GPU context and no pass over the rows.
+// merge: no counterpart in the reference.
 Bigsi merge_check(const std::vector<std::string> &paths, const std::string &out_path, std::vector<MergeInput> &inputs) {
     if (paths.size() < 2) die("merge needs at least two input indices (-i a.bxi b.bxi ...), got %zu", paths.size());
     for (const std::string &p : paths)
         if (is_mxi(p) != is_mxi(paths[0]))
             die("merge: %s and %s are not the same kind of index (.bxi / .mxi): inputs must all be .bxi or all .mxi", paths[0].c_str(), p.c_str());
-    struct stat out_st;
-    const bool out_exists = stat(out_path.c_str(), &out_st) == 0;
     inputs.assign(paths.size(), MergeInput());
     std::map<std::string, std::pair<size_t, uint64_t>> owner;   // accession -> (input, colour in it); iterates in byte order, as tab_to_map
     uint64_t total = 0;
     for (size_t i = 0; i < paths.size(); ++i) {
         MergeInput &in = inputs[i];
         in.path = paths[i];
-        struct stat st;
-        if (stat(in.path.c_str(), &st) != 0) die("Can't open index!: %s", in.path.c_str());
-        if (out_exists && st.st_dev == out_st.st_dev && st.st_ino == out_st.st_ino)
-            die("merge: the output %s is the input %s: write the merged index to another file", out_path.c_str(), in.path.c_str());
-        BufReader r(in.path, /*name_in_errors=*/true);
-        in.n_rows = read_header(r, in.path, in.meta);
-        const uint64_t header_end = r.tell();
-        const size_t rec = record_bytes(in.meta);
-        check_not_truncated("merge", in.path, in.n_rows, rec, header_end, (uint64_t)st.st_size);
-        r.seek(header_end + in.n_rows * rec);
-        read_tail(r, in.meta);
+        read_input_meta("merge", in, stat_input("merge", in.path, &out_path, "merged index"));
         const Bigsi &a = inputs[0].meta, &b = in.meta;
         const struct { const char *name; uint64_t first, here; } fields[] = {
             {"bloom_size", a.bloom_size, b.bloom_size}, {"num_hash", a.num_hash, b.num_hash}, {"k_size", a.k_size, b.k_size}, {"m_size", a.m_size, b.m_size}};
@@ -350,7 +375,7 @@ Bigsi merge_check(const std::vector<std::string> &paths, const std::string &out_
             const auto ins = owner.emplace(b.colors[c], std::make_pair(i, c));
             if (!ins.second) {
                 const size_t j = ins.first->second.first;
-                if (j == i) die("merge: %s holds accession %s twice", in.path.c_str(), b.colors[c].c_str());
+                if (j == i) die_accession_twice("merge", in.path, b.colors[c]);
                 die("merge: accession %s is in both %s and %s", b.colors[c].c_str(), inputs[j].path.c_str(), in.path.c_str());
             }
         }
@@ -370,29 +395,21 @@ Bigsi merge_check(const std::vector<std::string> &paths, const std::string &out_
 }
 
 void merge_records(cid_ctx *ctx, Bigsi &m, const std::vector<MergeInput> &inputs) {
-    CID_TRY(cid_index_create(ctx, m.bloom_size, (uint32_t)m.num_hash, (uint32_t)m.k_size, (uint32_t)m.colors.size(), CID_HASH_XXH3_V08, &m.index));
-    if (m.m_size) CID_TRY(cid_index_set_minimizer(m.index, (uint32_t)m.m_size));
+    create_output_index(ctx, m);
     for (size_t i = 0; i < inputs.size(); ++i) {
         const MergeInput &in = inputs[i];
         fprintf(stderr, "Merging %s into index (%zu/%zu): %zu accessions, %llu rows\n", in.path.c_str(), i + 1, inputs.size(), in.meta.colors.size(),
                 (unsigned long long)in.n_rows);
-        BufReader r(in.path, /*name_in_errors=*/true);
-        Bigsi again;
-        if (read_header(r, in.path, again) != in.n_rows || again.colors != in.meta.colors) die("merge: %s changed while it was merged", in.path.c_str());
-        const uint32_t nc = (uint32_t)in.meta.colors.size();
-        stream_records(r, in.path, in.n_rows, record_bytes(in.meta), [&](const uint8_t *src, size_t nr) {
-            return cid_index_put_records_mapped(m.index, src, nr, nc, in.colour_map.data());
+        stream_input("merge", "merged", in, [&](const uint8_t *src, size_t nr) {
+            return cid_index_put_records_mapped(m.index, src, nr, (uint32_t)in.meta.colors.size(), in.colour_map.data());
         });
     }
 }
 
-// subset: no counterpart in the reference.  As merge_check, every refusal comes from the header, the n_ref_kmers tail and the list.
+// subset: no counterpart in the reference.  Beside the input's own checks, every refusal comes from the list.
 Bigsi subset_check(const std::string &in_path, const std::string &out_path, const std::string &list_path, bool exclude, SubsetInput &in) {
     in.path = in_path;
-    struct stat st, out_st;
-    if (stat(in.path.c_str(), &st) != 0) die("Can't open index!: %s", in.path.c_str());
-    if (stat(out_path.c_str(), &out_st) == 0 && st.st_dev == out_st.st_dev && st.st_ino == out_st.st_ino)
-        die("subset: the output %s is the input %s: write the subset to another file", out_path.c_str(), in.path.c_str());
+    const uint64_t file_size = stat_input("subset", in.path, &out_path, "subset");
     // the list: the text before the first TAB of every non-empty line (a `build -r` reference list is one); a repeated name counts once
     std::set<std::string> listed;
     {
@@ -413,18 +430,12 @@ Bigsi subset_check(const std::string &in_path, const std::string &out_path, cons
         }
     }
     if (listed.empty()) die("subset: the accession list %s is empty", list_path.c_str());
-    BufReader r(in.path, /*name_in_errors=*/true);
-    in.n_rows = read_header(r, in.path, in.meta);
-    const uint64_t header_end = r.tell();
-    const size_t rec = record_bytes(in.meta);
-    check_not_truncated("subset", in.path, in.n_rows, rec, header_end, (uint64_t)st.st_size);
-    r.seek(header_end + in.n_rows * rec);
-    read_tail(r, in.meta);
+    read_input_meta("subset", in, file_size);
     const Bigsi &a = in.meta;
     std::map<std::string, uint64_t> colour_of;
     for (uint64_t c = 0; c < a.colors.size(); ++c) {
         check_name_order_at("subset", in.path, a.colors, c);   // the kept colours keep their order, and build's order is name order
-        if (!colour_of.emplace(a.colors[c], c).second) die("subset: %s holds accession %s twice", in.path.c_str(), a.colors[c].c_str());
+        if (!colour_of.emplace(a.colors[c], c).second) die_accession_twice("subset", in.path, a.colors[c]);
     }
     for (const std::string &name : listed)
         if (!colour_of.count(name))
@@ -446,34 +457,21 @@ Bigsi subset_check(const std::string &in_path, const std::string &out_path, cons
 }
 
 void subset_records(cid_ctx *ctx, Bigsi &out, const SubsetInput &in) {
-    CID_TRY(cid_index_create(ctx, out.bloom_size, (uint32_t)out.num_hash, (uint32_t)out.k_size, (uint32_t)out.colors.size(), CID_HASH_XXH3_V08, &out.index));
-    if (out.m_size) CID_TRY(cid_index_set_minimizer(out.index, (uint32_t)out.m_size));
+    create_output_index(ctx, out);
     fprintf(stderr, "Extracting %zu of %zu accessions from %s: %llu rows\n", out.colors.size(), in.meta.colors.size(), in.path.c_str(),
             (unsigned long long)in.n_rows);
-    BufReader r(in.path, /*name_in_errors=*/true);
-    Bigsi again;
-    if (read_header(r, in.path, again) != in.n_rows || again.colors != in.meta.colors) die("subset: %s changed while it was read", in.path.c_str());
-    const uint32_t nc = (uint32_t)in.meta.colors.size();
-    stream_records(r, in.path, in.n_rows, record_bytes(in.meta), [&](const uint8_t *src, size_t nr) {
-        return cid_index_put_records_subset(out.index, src, nr, nc, in.keep_words.data());
+    stream_input("subset", "read", in, [&](const uint8_t *src, size_t nr) {
+        return cid_index_put_records_subset(out.index, src, nr, (uint32_t)in.meta.colors.size(), in.keep_words.data());
     });
 }
 
-// compare: no counterpart in the reference.  As subset_check, every refusal but one comes from the header and the n_ref_kmers tail.
+// compare: no counterpart in the reference.  Every refusal but one comes from the input's own checks.
 void compare_check(const std::string &in_path, CompareInput &in) {
     in.path = in_path;
-    struct stat st;
-    if (stat(in.path.c_str(), &st) != 0) die("Can't open index!: %s", in.path.c_str());
-    BufReader r(in.path, /*name_in_errors=*/true);
-    in.n_rows = read_header(r, in.path, in.meta);
-    const uint64_t header_end = r.tell();
-    const size_t rec = record_bytes(in.meta);
-    check_not_truncated("compare", in.path, in.n_rows, rec, header_end, (uint64_t)st.st_size);
-    r.seek(header_end + in.n_rows * rec);
-    read_tail(r, in.meta);
+    read_input_meta("compare", in, stat_input("compare", in.path));
     std::set<std::string> seen;
     for (const std::string &name : in.meta.colors)
-        if (!seen.insert(name).second) die("compare: %s holds accession %s twice", in.path.c_str(), name.c_str());
+        if (!seen.insert(name).second) die_accession_twice("compare", in.path, name);
     if (in.meta.colors.size() > (1u << 20))
         die("compare: %s holds %zu accessions, more than the pair counters take (2^20 = 1048576)", in.path.c_str(), in.meta.colors.size());
 }
@@ -484,10 +482,7 @@ std::vector<uint64_t> compare_records(cid_ctx *ctx, const CompareInput &in) {
     cid_pairs *pairs = nullptr;
     if (cid_pairs_create(ctx, in.meta.bloom_size, (uint32_t)nc, &pairs) != CID_OK) die("compare: %s: %s", in.path.c_str(), cid_last_error());
     fprintf(stderr, "Comparing %zu accessions of %s: %llu rows\n", nc, in.path.c_str(), (unsigned long long)in.n_rows);
-    BufReader r(in.path, /*name_in_errors=*/true);
-    Bigsi again;
-    if (read_header(r, in.path, again) != in.n_rows || again.colors != in.meta.colors) die("compare: %s changed while it was read", in.path.c_str());
-    stream_records(r, in.path, in.n_rows, record_bytes(in.meta), [&](const uint8_t *src, size_t nr) { return cid_pairs_add_records(pairs, src, nr); });
+    stream_input("compare", "read", in, [&](const uint8_t *src, size_t nr) { return cid_pairs_add_records(pairs, src, nr); });
     std::vector<uint64_t> shared(nc * nc);
     CID_TRY(cid_pairs_fetch(pairs, shared.data()));
     cid_pairs_destroy(pairs);

@@ -302,14 +302,17 @@ Bigsi read_bigsi(cid_ctx *ctx, const std::string &path, int hash_variant, bool m
 // map the index file and start touching its pages — call it before the GPU context is made; read_bigsi then uploads from the mapping
 void bigsi_read_ahead(const std::string &path);
 void save_bigsi(const std::string &path, const Bigsi &b);                                           // bigsi.rs:51-57
+// The input index of a command that streams row records (`merge`, `subset`, `compare`), as the command's _check read it
+struct IndexInput {
+    std::string path;
+    Bigsi meta;          // header, colours and n_ref_kmers; no device index
+    uint64_t n_rows = 0;
+};
 // `merge` (no reference counterpart): indices of one shape and disjoint accessions as one index over the union of their accessions,
 // colours in name order as `build` numbers them.  merge_check reads every input's header and n_ref_kmers (not its rows) and refuses,
 // naming field or accession and files, what cannot be merged — before any GPU work; it returns the merged metadata (no index yet) and
 // each input's colour map.  merge_records makes the index on ctx and ORs every input's row records into it (not finalized).
-struct MergeInput {
-    std::string path;
-    Bigsi meta;                        // header, colours and n_ref_kmers; no device index
-    uint64_t n_rows = 0;
+struct MergeInput : IndexInput {
     std::vector<uint32_t> colour_map;  // input colour -> merged colour (increasing)
 };
 Bigsi merge_check(const std::vector<std::string> &paths, const std::string &out_path, std::vector<MergeInput> &inputs);
@@ -319,10 +322,7 @@ void merge_records(cid_ctx *ctx, Bigsi &merged, const std::vector<MergeInput> &i
 // (text, one accession per line up to the first TAB) and refuses before any GPU work, naming file and accession; it returns the output's
 // metadata (no index yet) and the keep bitmap.  subset_records makes the index on ctx and streams the input's records through
 // cid_index_put_records_subset (not finalized): the device holds the OUTPUT index and one upload chunk, never the input's matrix.
-struct SubsetInput {
-    std::string path;
-    Bigsi meta;                        // header, colours and n_ref_kmers; no device index
-    uint64_t n_rows = 0;
+struct SubsetInput : IndexInput {
     std::vector<uint32_t> keep_words;  // bitmap over the input's colours, in the rows' bit order
 };
 Bigsi subset_check(const std::string &in_path, const std::string &out_path, const std::string &list_path, bool exclude, SubsetInput &in);
@@ -331,11 +331,7 @@ void subset_records(cid_ctx *ctx, Bigsi &out, const SubsetInput &in);
 // and the n_ref_kmers tail and refuses before any GPU work (file missing, truncated, an accession twice).  compare_records makes the pair
 // counters on ctx, streams the input's records through cid_pairs_add_records and returns the symmetric n x n matrix shared[i][j] =
 // popcount(column i & column j): the device holds the counters and one upload chunk, never the input's matrix.
-struct CompareInput {
-    std::string path;
-    Bigsi meta;          // header, colours and n_ref_kmers; no device index
-    uint64_t n_rows = 0;
-};
+using CompareInput = IndexInput;
 void compare_check(const std::string &in_path, CompareInput &in);
 std::vector<uint64_t> compare_records(cid_ctx *ctx, const CompareInput &in);
 Bigsi build_single(cid_ctx *ctx, const std::string &ref_tsv, uint64_t bloom, uint64_t hashes, uint64_t k, uint8_t quality,

@@ -1,11 +1,12 @@
 // CPU unit-test harness (g++) for the integer arithmetic the gfx950 kernels run: includes the SAME
-// colorid_amd/csrc/cid_hash.hpp + cid_host_math.hpp the HIP build compiles, with the two HIP builtins
-// replaced by their plain-C definitions.  Test infrastructure only; never linked into the product.
+// colorid_amd/csrc/cid_hash.hpp + cid_host_math.hpp + cid_records.hpp the HIP build compiles, with the two HIP
+// builtins replaced by their plain-C definitions.  Test infrastructure only; never linked into the product.
 #include <cstring>
 #include <vector>
 
 #include "../../colorid_amd/csrc/cid_hash.hpp"
 #include "../../colorid_amd/csrc/cid_host_math.hpp"
+#include "../../colorid_amd/csrc/cid_records.hpp"
 
 extern "C" {
 
@@ -51,4 +52,14 @@ uint64_t shim_mod(uint64_t h, uint64_t m) {
 }
 
 uint32_t shim_row_stride_words(uint32_t n_colors) { return cid::row_stride_words(n_colors); }
+
+// the .bxi row record (cid_records.hpp): layout, tail mask, the check the put kernels and k_pairs_check run, the mask-run walk
+uint64_t shim_record_words(uint32_t w32) { return cid::record_words(w32); }
+uint64_t shim_record_bytes(uint64_t n_colors) { return cid::record_bytes(n_colors); }
+uint32_t shim_tail_mask(uint32_t n_colors) { return cid::tail_mask(n_colors); }
+uint32_t shim_check_record(const uint32_t *rec, uint32_t w32_rec, uint32_t n_colors, uint64_t bloom_size) {
+    return cid::check_record(rec, cid::record_row(rec), w32_rec, n_colors, bloom_size, cid::tail_mask(n_colors));
+}
+uint32_t shim_deposit_bits(uint32_t bits, uint32_t mask) { return cid::deposit_bits(bits, mask); }
+uint32_t shim_extract_bits(uint32_t word, uint32_t mask, uint32_t *n) { return cid::extract_bits(word, mask, *n); }
 }

@@ -1,5 +1,6 @@
 """CPU check of the integer arithmetic the gfx950 kernels execute (same headers, compiled with g++):
-XXH3-64 seeds 0..n-1 out of a byte image at arbitrary alignment, and the exact `% bloom_size`."""
+XXH3-64 seeds 0..n-1 out of a byte image at arbitrary alignment, the exact `% bloom_size`, and the .bxi row record (its check, its
+tail mask, the mask-run deposit and extract of `merge` and `subset`)."""
 import ctypes as C
 import json
 import os
@@ -25,6 +26,18 @@ def shim(tmp_path_factory):
     L.shim_mod.argtypes = [C.c_uint64, C.c_uint64]
     L.shim_row_stride_words.restype = C.c_uint32
     L.shim_row_stride_words.argtypes = [C.c_uint32]
+    L.shim_record_words.restype = C.c_uint64
+    L.shim_record_words.argtypes = [C.c_uint32]
+    L.shim_record_bytes.restype = C.c_uint64
+    L.shim_record_bytes.argtypes = [C.c_uint64]
+    L.shim_tail_mask.restype = C.c_uint32
+    L.shim_tail_mask.argtypes = [C.c_uint32]
+    L.shim_check_record.restype = C.c_uint32
+    L.shim_check_record.argtypes = [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_uint64]
+    L.shim_deposit_bits.restype = C.c_uint32
+    L.shim_deposit_bits.argtypes = [C.c_uint32, C.c_uint32]
+    L.shim_extract_bits.restype = C.c_uint32
+    L.shim_extract_bits.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
     return L
 
 
@@ -65,6 +78,80 @@ def test_row_stride_rule(shim):
             4096: 64, 8192: 128, 8193: 256, 16384: 256, 16385: 384, 20000: 384, 65536: 1024}
     for c, rs in want.items():
         assert shim.shim_row_stride_words(c) == rs
+
+
+RECORD_COLOURS = (1, 31, 32, 33, 64, 8300)
+
+
+def test_mask_run_deposit_and_extract(shim):
+    """deposit_bits / extract_bits (cid_records.hpp: the software pdep of k_put_records_mapped, the software pext of
+    k_put_records_subset) against a bit-by-bit loop, and extract(deposit(x, m), m) == the low popcount(m) bits of x"""
+    def naive_deposit(bits, mask):
+        out, k = 0, 0
+        for b in range(32):
+            if mask >> b & 1:
+                out |= (bits >> k & 1) << b
+                k += 1
+        return out
+
+    def naive_extract(word, mask):
+        out, k = 0, 0
+        for b in range(32):
+            if mask >> b & 1:
+                out |= (word >> b & 1) << k
+                k += 1
+        return out
+
+    rnd = random.Random(17)
+    masks = [0, 1, 0x80000000, 0xFFFFFFFF, 0x55555555, 0xAAAAAAAA, 0x0000FFFF, 0xFFFF0000, 0x00000007, 0xE0000000, 0x7FFFFFFF,
+             0xFFFFFFFE, 0x80000001] + [rnd.getrandbits(32) for _ in range(3000)]
+    masks += [rnd.getrandbits(32) & rnd.getrandbits(32) for _ in range(500)] + [rnd.getrandbits(32) | rnd.getrandbits(32) for _ in range(500)]
+    for m in masks:
+        pop = bin(m).count("1")
+        for x in (0, 0xFFFFFFFF, 1, 0x80000000, rnd.getrandbits(32), rnd.getrandbits(32)):
+            d = shim.shim_deposit_bits(x, m)
+            assert d == naive_deposit(x, m), (hex(x), hex(m))
+            n = C.c_uint32(99)
+            assert shim.shim_extract_bits(x, m, C.byref(n)) == naive_extract(x, m), (hex(x), hex(m))
+            assert n.value == pop, hex(m)
+            assert shim.shim_extract_bits(d, m, C.byref(n)) == x & ((1 << pop) - 1), (hex(x), hex(m))
+
+
+def test_record_layout_and_tail_mask(shim):
+    for nc in RECORD_COLOURS:
+        w32 = (nc + 31) // 32
+        assert shim.shim_record_words(w32) == 6 + w32
+        assert shim.shim_record_bytes(nc) == 24 + 4 * w32 == 4 * shim.shim_record_words(w32)
+        assert shim.shim_tail_mask(nc) == ((1 << (nc % 32)) - 1 if nc % 32 else 0xFFFFFFFF), nc
+
+
+def test_check_record_names_each_malformation(shim):
+    """check_record (the put kernels' word-0 thread, k_pairs_check): 0 for a well-formed record; 1 word count, 2 bit count,
+    4 row >= bloom_size, 8 bits beyond n_colors — each alone and every combination.  A file whose n_colors is a multiple of 32
+    has no bit beyond n_colors in its last word: there the fourth malformation cannot be written, and an all-ones last word
+    must not raise it."""
+    rnd = random.Random(23)
+    bloom = 100_003
+    for nc in RECORD_COLOURS:
+        w32 = (nc + 31) // 32
+        tail = (1 << (nc % 32)) - 1 if nc % 32 else 0xFFFFFFFF
+        for trial in range(8):
+            words = [rnd.getrandbits(32) for _ in range(w32)]
+            if trial == 0:
+                words = [0xFFFFFFFF] * w32
+            words[-1] &= tail
+            for bad in range(16):
+                if bad & 8 and tail == 0xFFFFFFFF:
+                    continue
+                row = bloom + rnd.randrange(3) * (1 << 33) if bad & 4 else rnd.choice((0, bloom - 1, rnd.randrange(bloom)))
+                nw = rnd.choice((w32 + 1, w32 - 1, 0, w32 + (1 << 32))) if bad & 1 else w32
+                nbits = rnd.choice((nc + 1, nc - 1, 32 * w32 + 32, nc + (1 << 32))) if bad & 2 else nc
+                last = words[-1] | (rnd.choice((1 << (nc % 32), 0x80000000, ~tail & 0xFFFFFFFF)) if bad & 8 else 0)
+                body = words[:-1] + [last]
+                rec = [row & 0xFFFFFFFF, row >> 32, nw & 0xFFFFFFFF, nw >> 32] + body + [nbits & 0xFFFFFFFF, nbits >> 32]
+                assert len(rec) == shim.shim_record_words(w32)
+                arr = (C.c_uint32 * len(rec))(*rec)
+                assert shim.shim_check_record(arr, w32, nc, bloom) == bad, (nc, trial, bad)
 
 
 def test_packed_code_path_matches_string_path(shim, orc):
