@@ -214,6 +214,47 @@ int cid_index_put_records_subset(cid_index *ix, const uint8_t *records, size_t n
     });
 }
 
+// `fold`: bloom_size_file = factor x the index's bloom_size.  Each piece is checked on the device against the FILE's shape (k_pairs_check:
+// row < bloom_size_file, word count, bit count, tail bits) before k_put_records_folded ORs it in, so a refused piece changes nothing.
+int cid_index_put_records_folded(cid_index *ix, const uint8_t *records, size_t n_records, uint64_t bloom_size_file) {
+    if (!ix || (n_records && !records)) return fail(CID_ERR_INVALID, "null argument");
+    if (ix->finalized) return fail(CID_ERR_STATE, "index already finalized");
+    if (cid::fold_factor(bloom_size_file, ix->m) == 0)
+        return fail(CID_ERR_INVALID, "a file of bloom_size %llu does not fold onto %llu rows: not a multiple", (unsigned long long)bloom_size_file,
+                    (unsigned long long)ix->m);
+    if (n_records == 0) return CID_OK;
+    cid_ctx *c = ix->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    return stage_records(
+        c, records, n_records, ix->w32, 1,
+        [&](const uint32_t *d_rec, size_t nr, uint32_t *d_err) {
+            return cid::launch_pairs_check(d_rec, ix->w32, nr, bloom_size_file, ix->n_colors, d_err, c->stream);
+        },
+        [&](const uint32_t *d_rec, size_t nr) {
+            HIP_TRY(cid::launch_put_records_folded(ix->mat, ix->rs, d_rec, ix->w32, nr, ix->mod, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));   // the slot is the next piece's upload buffer
+            return (int)CID_OK;
+        });
+}
+
+int cid_index_put_index_folded(cid_index *dst, const cid_index *src) {
+    if (!dst || !src) return fail(CID_ERR_INVALID, "null argument");
+    if (dst->finalized) return fail(CID_ERR_STATE, "index already finalized");
+    if (!src->finalized) return fail(CID_ERR_INVALID, "source index not finalized");
+    if (src->n_colors != dst->n_colors) return fail(CID_ERR_INVALID, "a source of %u colours into an index of %u", src->n_colors, dst->n_colors);
+    cid_ctx *c = dst->ctx;
+    if (src->ctx->device != c->device) return fail(CID_ERR_INVALID, "source index lives on device %d, the index on %d", src->ctx->device, c->device);
+    const uint64_t factor = cid::fold_factor(src->m, dst->m);
+    if (factor == 0)
+        return fail(CID_ERR_INVALID, "a source of bloom_size %llu does not fold onto %llu rows: not a multiple", (unsigned long long)src->m,
+                    (unsigned long long)dst->m);
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(src->ctx->stream));   // (another ctx of the device may have filled the source)
+    HIP_TRY(cid::launch_fold_rows(dst->mat, src->mat, dst->rs, dst->w32, dst->m, factor, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CID_OK;
+}
+
 int cid_index_device_matrix(cid_index *ix, void **dev_ptr, uint64_t *row_stride_words) {
     if (!ix || !dev_ptr || !row_stride_words) return fail(CID_ERR_INVALID, "null argument");
     *dev_ptr = ix->mat;

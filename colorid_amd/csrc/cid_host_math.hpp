@@ -1,6 +1,9 @@
-// Host-side integer helpers (no HIP types): the exact-modulo constants and the row-stride rule.
+// Host-side integer helpers (no HIP types): the exact-modulo constants, the row-stride rule and the divisor rule of `fold`.
 #pragma once
 #include <stdint.h>
+
+#include <algorithm>
+#include <vector>
 
 namespace cid {
 
@@ -39,6 +42,31 @@ inline uint32_t row_stride_words(uint32_t n_colors) {
     uint32_t rs = 2;
     while (rs < w64) rs <<= 1;
     return rs;
+}
+
+// `fold`: the rows of an index of m rows fold onto m2 rows when m2 divides m — (h % m) % m2 == h % m2 for every hash h then, so
+// OR-ing row r into row r % m2 gives the matrix `build` makes at m2.  The factor m / m2, or 0 when m2 is 0 or does not divide m.
+inline uint64_t fold_factor(uint64_t m, uint64_t m2) { return m && m2 && m % m2 == 0 ? m / m2 : 0; }
+
+// The divisors of m, ascending (m >= 1): trial division up to sqrt(m) — at most 65536 steps for a Bloom size (<= 2^32).
+inline std::vector<uint64_t> divisors_of(uint64_t m) {
+    std::vector<uint64_t> lo, hi;
+    for (uint64_t d = 1; d <= m / d; ++d)
+        if (m % d == 0) {
+            lo.push_back(d);
+            if (d != m / d) hi.push_back(m / d);
+        }
+    lo.insert(lo.end(), hi.rbegin(), hi.rend());
+    return lo;
+}
+
+// The divisors of m next to s: the largest one <= s (0: there is none, s == 0) and the smallest one >= s (0: none, s > m).
+inline void nearest_divisors(uint64_t m, uint64_t s, uint64_t &below, uint64_t &above) {
+    below = above = 0;
+    for (const uint64_t d : divisors_of(m)) {
+        if (d <= s) below = d;
+        if (d >= s && !above) above = d;
+    }
 }
 
 }  // namespace cid

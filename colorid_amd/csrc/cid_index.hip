@@ -1,4 +1,6 @@
 // Index maintenance kernels for MI355X (gfx950): .bxi rows <-> dense matrix, Bloom insert (simple_bloom.rs:19-26).
+#include <algorithm>
+
 #include "cid_gather.hpp"
 #include "cid_records.hpp"
 
@@ -97,6 +99,56 @@ __global__ void k_put_records_subset(uint32_t *mat32, uint32_t rs, const uint32_
         drop = 0;
     }
     mat32[row * (2ull * rs) + j] = out;
+}
+
+// `fold`: the records of a file whose Bloom size is a multiple of the index's, OR-ed into row (record's row) % bloom_size of the index —
+// (h % m) % m' == h % m' when m' divides m, so this is the matrix `build` makes at the smaller size.  The piece was checked against the
+// FILE's shape before this runs (k_pairs_check under stage_records: a refused piece leaves the matrix as it was), so nothing is checked
+// here.  A workgroup takes recs_per_block consecutive records (at most 256): thread t reduces record t's row — the one 64-bit modulo of
+// the record — into LDS; then the workgroup walks the tile's u32 words front to back, one coalesced load per payload word (the header
+// and bit-count words share its lines and are stepped over), (record, word in record) advanced by the stride 256 without a division.
+// Records r, r + m', r + 2m', ... of one piece land on one output row, in any order (a file written by the reference is in hash-map
+// order): the OR is a no-return atomicOr on the matrix word; all-zero words are skipped.
+constexpr uint32_t kFoldBlock = 256;
+__global__ __launch_bounds__(kFoldBlock) void k_put_records_folded(uint32_t *mat32, uint32_t rs, const uint32_t *rec32, uint32_t w32_rec,
+                                                                   uint32_t recs_per_block, uint64_t n_records, ModMagic mod) {
+    __shared__ uint32_t dst_row[kFoldBlock];   // < bloom_size <= 2^32
+    const uint64_t r0 = (uint64_t)blockIdx.x * recs_per_block;
+    const uint32_t nr = n_records - r0 < recs_per_block ? (uint32_t)(n_records - r0) : recs_per_block;
+    const uint32_t rw = (uint32_t)record_words(w32_rec);
+    const uint32_t *tile = rec32 + r0 * rw;
+    if (threadIdx.x < nr) dst_row[threadIdx.x] = (uint32_t)mod_m(record_row(tile + (uint64_t)threadIdx.x * rw), mod);
+    __syncthreads();
+    const uint32_t n_words = nr * rw;   // <= 256 * (6 + 32768)
+    const uint32_t dq = kFoldBlock / rw, dr = kFoldBlock % rw;
+    uint32_t r = threadIdx.x / rw, p = threadIdx.x % rw;
+    for (uint32_t i = threadIdx.x; i < n_words; i += kFoldBlock) {
+        if (p >= kRecordPayload && p < kRecordPayload + w32_rec) {
+            const uint32_t v = tile[i];
+            if (v) atomicOr(&mat32[(uint64_t)dst_row[r] * (2ull * rs) + (p - kRecordPayload)], v);
+        }
+        p += dr;
+        r += dq;
+        if (p >= rw) { p -= rw; ++r; }
+    }
+}
+
+// The same from a resident index of factor * m_dst rows and the same colours: one thread per (output row, u32 word) ORs the word of the
+// source rows row, row + m_dst, row + 2 m_dst, ... in registers — neighbouring threads read neighbouring words of every source slice — and
+// ORs the result into the output once; zero results (all-zero source rows) touch nothing.  With one chunk (gridDim.y == 1) each output
+// word has one writer: a plain read-modify-write.  A small output with a large factor is split over gridDim.y chunks of the slices
+// (chunk c takes slices c, c + gridDim.y, ...), whose threads share output words: atomicOr then.
+__global__ void k_fold_rows(uint32_t *dst32, const uint32_t *src32, uint32_t rs, uint32_t w32, uint64_t m_dst, uint64_t factor) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m_dst * w32) return;
+    const uint64_t row = i / w32;
+    const uint32_t w = (uint32_t)(i % w32);
+    uint32_t acc = 0;
+    for (uint64_t s = blockIdx.y; s < factor; s += gridDim.y) acc |= src32[(s * m_dst + row) * (2ull * rs) + w];
+    if (acc == 0) return;
+    uint32_t *d = &dst32[row * (2ull * rs) + w];
+    if (gridDim.y == 1) *d |= acc;
+    else atomicOr(d, acc);
 }
 
 __global__ void k_get_rows(const uint32_t *mat32, uint32_t rs, const uint64_t *row_ids, uint32_t *words, uint32_t w32,
@@ -199,6 +251,30 @@ hipError_t launch_put_records_subset(uint64_t *mat, uint32_t rs, const uint32_t 
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_put_records_subset, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<uint32_t *>(mat), rs,
                        d_records, w32_rec, d_words, d_items, w32_out, n_records, bloom_size, n_colors_file, tail_mask(n_colors_file), d_err);
+    return hipGetLastError();
+}
+
+// A workgroup's tile: about 8192 u32 words of records, at least one record and at most one per thread
+hipError_t launch_put_records_folded(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, uint64_t n_records,
+                                     const ModMagic &mod, hipStream_t stream) {
+    if (n_records == 0) return hipSuccess;
+    const uint64_t rpb = std::min<uint64_t>(kFoldBlock, std::max<uint64_t>(1, 8192u / record_words(w32_rec)));
+    const uint64_t grid = (n_records + rpb - 1) / rpb;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;   // (a piece of stage_records is 256 MiB: at most 2^24 records)
+    hipLaunchKernelGGL(k_put_records_folded, dim3((unsigned)grid), dim3(kFoldBlock), 0, stream, reinterpret_cast<uint32_t *>(mat), rs, d_records,
+                       w32_rec, (uint32_t)rpb, n_records, mod);
+    return hipGetLastError();
+}
+
+// About 2^20 threads at least: an output smaller than that takes its slices in several chunks (never more chunks than slices)
+hipError_t launch_fold_rows(uint64_t *dst, const uint64_t *src, uint32_t rs, uint32_t w32, uint64_t m_dst, uint64_t factor, hipStream_t stream) {
+    const uint64_t n = m_dst * w32;
+    if (n == 0 || factor == 0) return hipSuccess;
+    const uint64_t grid = (n + 255) / 256;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const uint64_t chunks = std::min<uint64_t>(std::min<uint64_t>(factor, 65535), std::max<uint64_t>(1, (1ull << 20) / n));
+    hipLaunchKernelGGL(k_fold_rows, dim3((unsigned)grid, (unsigned)chunks), dim3(256), 0, stream, reinterpret_cast<uint32_t *>(dst),
+                       reinterpret_cast<const uint32_t *>(src), rs, w32, m_dst, factor);
     return hipGetLastError();
 }
 

@@ -186,6 +186,11 @@ struct SubsetWord { uint32_t first, skip, n_items, pad; };
 hipError_t launch_put_records_subset(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, const SubsetWord *d_words,
                                      const SubsetItem *d_items, uint32_t w32_out, uint64_t n_records, uint64_t bloom_size,
                                      uint32_t n_colors_file, uint32_t *d_err, hipStream_t stream);
+// `fold`: checked records of a file whose Bloom size is a multiple of mod.m, OR-ed into row (record's row) % mod.m (k_put_records_folded);
+// and the rows of a resident matrix of factor * m_dst rows with the same row stride, OR-ed into dst's row % m_dst (k_fold_rows).
+hipError_t launch_put_records_folded(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, uint64_t n_records,
+                                     const ModMagic &mod, hipStream_t stream);
+hipError_t launch_fold_rows(uint64_t *dst, const uint64_t *src, uint32_t rs, uint32_t w32, uint64_t m_dst, uint64_t factor, hipStream_t stream);
 // `compare`: shared[i][j] += popcount(column i & column j) over the rows of one source (k_pairs).  The rows are w32 u32 words at
 // rows + row*stride + off (u32 units): a chunk of file records (stride 6 + w32, off 4) or a resident index's matrix (stride 2*rs, off 0).
 // shared: n_colors x n_colors u64 counters, row-major; only i <= j is added to.  The launcher fills in the grid fields.

@@ -1,6 +1,7 @@
 // .bxi (bincode 1.x of BigsyMapNew, src/bigsi.rs:19-27 / SURVEY.md App. A) <-> device-resident index,
 // and the index builder (src/build.rs:15-130) with the Bloom inserts done on the GPU.
 #include <algorithm>
+#include <cerrno>
 #include <cstdarg>
 #include <cstring>
 #include <future>
@@ -13,6 +14,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "../cid_host_math.hpp"
 #include "../cid_records.hpp"
 #include "colorid_host.hpp"
 
@@ -294,7 +296,7 @@ Bigsi read_bigsi(cid_ctx *ctx, const std::string &path, int hash_variant, bool m
 
 namespace {
 
-// What `merge`, `subset` and `compare` (cmd) have in common: the input index of a command that streams row records.  Its checks read only
+// What `merge`, `subset`, `compare` and `fold` (cmd) have in common: the input index of a command that streams row records.  Its checks read only
 // the header and the n_ref_kmers tail (the tail lies at header_end + n_rows x record_bytes), so a refusal costs no GPU context and no
 // pass over the rows.
 bool is_mxi(const std::string &p) { return p.size() >= 4 && p.compare(p.size() - 4, 4, ".mxi") == 0; }
@@ -462,6 +464,77 @@ void subset_records(cid_ctx *ctx, Bigsi &out, const SubsetInput &in) {
             (unsigned long long)in.n_rows);
     stream_input("subset", "read", in, [&](const uint8_t *src, size_t nr) {
         return cid_index_put_records_subset(out.index, src, nr, (uint32_t)in.meta.colors.size(), in.keep_words.data());
+    });
+}
+
+// fold: no counterpart in the reference.  Beside the input's own checks, every refusal comes from the requested size.
+Bigsi fold_check(const std::string &in_path, const std::string &out_path, char by, const std::string &value, FoldInput &in) {
+    in.path = in_path;
+    read_input_meta("fold", in, stat_input("fold", in.path, &out_path, "folded index"));
+    const Bigsi &a = in.meta;
+    const uint64_t m = a.bloom_size;
+    if (m == 0) die("fold: %s states a Bloom size of 0", in.path.c_str());
+    auto worst_at = [&](uint64_t size, size_t &worst) {   // the highest false_prob over the accessions at `size` rows (the first of equals)
+        double fp = -1.0;
+        for (size_t c = 0; c < a.colors.size(); ++c) {
+            const double v = false_prob((double)size, (double)a.num_hash, (double)a.n_ref_kmers[c]);
+            if (v > fp) { fp = v; worst = c; }
+        }
+        return fp;
+    };
+    uint64_t new_size = 0;
+    char *end = nullptr;
+    if (by == 'p') {
+        const double bound = strtod(value.c_str(), &end);
+        if (value.empty() || *end || !(bound > 0.0 && bound < 1.0))
+            die("fold: -p %s: the false-positive bound must be a number above 0 and below 1", value.c_str());
+        size_t worst = 0;
+        const double own = worst_at(m, worst);
+        if (!(own <= bound))
+            die("fold: -p %s: %s misses the bound at its own size %llu already: accession %s (%llu k-mers) predicts %.6g; nothing to fold",
+                value.c_str(), in.path.c_str(), (unsigned long long)m, a.colors[worst].c_str(), (unsigned long long)a.n_ref_kmers[worst], own);
+        const size_t heavy = worst;   // most sizes fail on the accession that is worst at the input's size: ask it first
+        for (const uint64_t d : cid::divisors_of(m)) {   // ascending: the first that holds every accession under the bound
+            if (!(false_prob((double)d, (double)a.num_hash, (double)a.n_ref_kmers[heavy]) <= bound)) continue;
+            if (worst_at(d, worst) <= bound) { new_size = d; break; }
+        }
+    } else {
+        errno = 0;
+        const unsigned long long v = strtoull(value.c_str(), &end, 10);
+        if (value.empty() || value[0] < '0' || value[0] > '9' || *end || (v == ~0ull && errno == ERANGE))
+            die("fold: -%c %s: expected a whole number", by, value.c_str());
+        if (by == 's') {
+            if (v == 0 || v > m)
+                die("fold: -s %llu: the new Bloom size must be between 1 and the %llu of %s", v, (unsigned long long)m, in.path.c_str());
+            if (cid::fold_factor(m, v) == 0) {
+                uint64_t below, above;
+                cid::nearest_divisors(m, v, below, above);
+                die("fold: -s %llu does not divide the Bloom size %llu of %s: the nearest sizes that do are %llu and %llu", v, (unsigned long long)m,
+                    in.path.c_str(), (unsigned long long)below, (unsigned long long)above);
+            }
+            new_size = v;
+        } else {
+            if (cid::fold_factor(m, v) == 0)
+                die("fold: -f %llu: the factor must be a divisor of the Bloom size %llu of %s", v, (unsigned long long)m, in.path.c_str());
+            new_size = m / v;
+        }
+    }
+    in.factor = m / new_size;
+    in.worst_fp = worst_at(new_size, in.worst);
+    Bigsi out;
+    out.bloom_size = new_size; out.num_hash = a.num_hash; out.k_size = a.k_size; out.m_size = a.m_size;
+    out.colors = a.colors;
+    out.n_ref_kmers = a.n_ref_kmers;
+    if (out.colors.size() > (1u << 20))
+        die("fold: %s holds %zu accessions, more than an index holds (2^20 = 1048576)", in.path.c_str(), out.colors.size());
+    return out;
+}
+
+void fold_records(cid_ctx *ctx, Bigsi &out, const FoldInput &in) {
+    create_output_index(ctx, out);
+    fprintf(stderr, "Folding %s: %llu rows into %llu\n", in.path.c_str(), (unsigned long long)in.n_rows, (unsigned long long)out.bloom_size);
+    stream_input("fold", "read", in, [&](const uint8_t *src, size_t nr) {
+        return cid_index_put_records_folded(out.index, src, nr, in.meta.bloom_size);
     });
 }
 

@@ -302,7 +302,7 @@ Bigsi read_bigsi(cid_ctx *ctx, const std::string &path, int hash_variant, bool m
 // map the index file and start touching its pages — call it before the GPU context is made; read_bigsi then uploads from the mapping
 void bigsi_read_ahead(const std::string &path);
 void save_bigsi(const std::string &path, const Bigsi &b);                                           // bigsi.rs:51-57
-// The input index of a command that streams row records (`merge`, `subset`, `compare`), as the command's _check read it
+// The input index of a command that streams row records (`merge`, `subset`, `compare`, `fold`), as the command's _check read it
 struct IndexInput {
     std::string path;
     Bigsi meta;          // header, colours and n_ref_kmers; no device index
@@ -334,6 +334,20 @@ void subset_records(cid_ctx *ctx, Bigsi &out, const SubsetInput &in);
 using CompareInput = IndexInput;
 void compare_check(const std::string &in_path, CompareInput &in);
 std::vector<uint64_t> compare_records(cid_ctx *ctx, const CompareInput &in);
+// `fold` (no reference counterpart): one index at a smaller Bloom size that divides its own — the file `build -s NEW` writes over the same
+// reference list, made from the index alone (every row is hash % bloom_size, so row r of the input is OR-ed into row r % NEW).  The new
+// size is given (by = 's'), or as the factor to divide by ('f'), or as the largest false-positive rate any accession may have ('p': the
+// smallest divisor of the input's size at which false_prob, as `info` prints it, stays at or under the bound for every accession).
+// fold_check reads the header and the n_ref_kmers tail and refuses before any GPU work, naming file and numbers; it returns the output's
+// metadata (no index yet).  fold_records makes the index on ctx and streams the input's records through cid_index_put_records_folded
+// (not finalized): the device holds the OUTPUT index and one upload chunk, never the input's matrix.
+struct FoldInput : IndexInput {
+    uint64_t factor = 0;      // input's bloom_size / the output's
+    size_t worst = 0;         // the accession with the highest predicted false-positive rate at the output's size, and that rate
+    double worst_fp = 0.0;
+};
+Bigsi fold_check(const std::string &in_path, const std::string &out_path, char by, const std::string &value, FoldInput &in);
+void fold_records(cid_ctx *ctx, Bigsi &out, const FoldInput &in);
 Bigsi build_single(cid_ctx *ctx, const std::string &ref_tsv, uint64_t bloom, uint64_t hashes, uint64_t k, uint8_t quality,
                    int64_t cutoff, int hash_variant, uint64_t m_size = 0);   // build.rs:15-130; m_size > 0: build_single_mini :396-492
 

@@ -6,7 +6,8 @@
 // hashcheck (which hash variant was an index built with); merge (indices of one shape and disjoint accessions as one index, the
 // file `build` writes over the union of their reference lists); subset (chosen accessions of an index as an index of their own, the
 // file `build` writes over the kept lines of the reference list); compare (all-pairs similarity of an index's accessions: which of
-// them are duplicates — the question before `subset -x`).
+// them are duplicates — the question before `subset -x`); fold (an index at a smaller Bloom size that divides its own, the file
+// `build -s` writes at that size: an over-sized index shrunk, or two indices brought to one size before `merge`).
 // Minimizer indices (.mxi): build -m [-v M], info, read_id, batch_id.  Not provided (outside the query path): read_filter.
 #include <cctype>
 #include <cerrno>
@@ -381,6 +382,62 @@ int cmd_subset(int argc, char **argv) {
     phase_done("GPU context");
     subset_records(ctx, b, in);
     phase_done("records streamed and extracted");
+    if (cid_index_finalize(b.index) != CID_OK) die("cid_index_finalize: %s", cid_last_error());
+    phase_done("finalize");
+    printf("Saving BIGSI to file.\n");
+    save_bigsi(out, b);
+    phase_done("index written");
+    cid_index_destroy(b.index);
+    cid_ctx_destroy(ctx);
+    return 0;
+}
+
+// fold: -b OUT -i in.bxi (-s NEW_BLOOM_SIZE | -f FACTOR | -p MAX_FALSE_POSITIVE) writes OUT.bxi (OUT.mxi for an .mxi input): the index
+// `build -s NEW_BLOOM_SIZE` writes over the same reference list — same header but for the size, same colours, same n_ref_kmers — made
+// from the index alone: NEW_BLOOM_SIZE must divide the input's size (-f F: the input's size / F; -p P: the smallest divisor at which no
+// accession's predicted false-positive rate, as `info` prints it, exceeds P).  Everything that would refuse it is checked on the header
+// and the n_ref_kmers tail before the GPU is opened; the rows then go to the device one upload chunk at a time: the device holds the
+// output index, never the input's matrix.
+int cmd_fold(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {{'b', "bigsi", true, false}, {'i', "input", true, true}, {'s', "bloom", true, false},
+                                         {'f', "factor", true, false}, {'p', "max_false_positive", true, false}, {0, "device", true, false}});
+    for (const char *req : {"bigsi", "input"})
+        if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
+    const struct { char by; const char *key; } ways[] = {{'s', "bloom"}, {'f', "factor"}, {'p', "max_false_positive"}};
+    std::string given;
+    char by = 0;
+    const char *key = nullptr;
+    for (const auto &w : ways)
+        if (a.has(w.key)) {
+            given += std::string(given.empty() ? "-" : ", -") + w.by;
+            by = w.by;
+            key = w.key;
+            if (a.values.at(w.key).size() != 1) die("fold takes one value for -%c/--%s, got %zu", w.by, w.key, a.values.at(w.key).size());
+        }
+    if (given.size() != 2)
+        die("fold needs exactly one of -s/--bloom (the new Bloom size), -f/--factor (the divisor of the size) and -p/--max_false_positive "
+            "(the highest predicted false-positive rate of any accession), got %s", given.empty() ? "none" : given.c_str());
+    const std::vector<std::string> &paths = a.values.at("input");
+    if (paths.size() != 1) die("fold takes exactly one input index (-i in.bxi), got %zu: %s ...", paths.size(), paths[1].c_str());
+    const bool minimizer = ends_with(paths[0], ".mxi");
+    const std::string out = a.one("bigsi") + (minimizer ? ".mxi" : ".bxi");
+    FoldInput in;
+    Bigsi b = fold_check(paths[0], out, by, a.one(key), in);
+    phase_done("input checked");
+    printf(" Input index : %s\n Bigsi file : %s\nK-mer size: %llu\nBloom filter parameters: num hashes %llu, filter size %llu\n", in.path.c_str(),
+           out.c_str(), (unsigned long long)b.k_size, (unsigned long long)b.num_hash, (unsigned long long)b.bloom_size);
+    if (minimizer) printf("Build with minimizers, minimizer size: %llu\n", (unsigned long long)b.m_size);
+    printf("Filter size: %llu of %llu (factor %llu)\n", (unsigned long long)b.bloom_size, (unsigned long long)in.meta.bloom_size,
+           (unsigned long long)in.factor);
+    if (by == 'p')
+        printf("False positive bound %s: accession %s predicts %.6g at filter size %llu, the highest of %zu\n", a.one(key).c_str(),
+               b.colors[in.worst].c_str(), in.worst_fp, (unsigned long long)b.bloom_size, b.colors.size());
+    fflush(stdout);              // the choice is on record whatever becomes of the GPU
+    bigsi_read_ahead(in.path);   // pages come in beside the runtime's start-up, as for `search`
+    cid_ctx *ctx = make_ctx(a);
+    phase_done("GPU context");
+    fold_records(ctx, b, in);
+    phase_done("records streamed and folded");
     if (cid_index_finalize(b.index) != CID_OK) die("cid_index_finalize: %s", cid_last_error());
     phase_done("finalize");
     printf("Saving BIGSI to file.\n");
@@ -787,12 +844,12 @@ int main(int argc, char **argv) {
     // src/main.rs:16-20: init_log() prints this banner on stdout before anything else
     printf("\n ************** initializing logger *****************\n\n");
     if (argc < 2) {
-        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|compare> [FLAGS]\n");
+        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare> [FLAGS]\n");
         return 1;
     }
     const std::string cmd = argv[1];
     if (cmd == "--help" || cmd == "-h" || cmd == "help") {
-        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|compare> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
+        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
                "ENVIRONMENT:\n"
                "    COLORID_FAST_EXIT=1      leave without the GPU runtime's teardown once the results are written, closed and flushed\n"
                "                             (-0.05 to -0.15 s per run); =0, or COLORID_FULL_TEARDOWN=1: always the orderly exit\n"
@@ -811,6 +868,7 @@ int main(int argc, char **argv) {
     if (cmd == "hashcheck") return leave(cmd_hashcheck(argc, argv));
     if (cmd == "merge") return leave(cmd_merge(argc, argv));
     if (cmd == "subset") return leave(cmd_subset(argc, argv));
+    if (cmd == "fold") return leave(cmd_fold(argc, argv));
     if (cmd == "compare") return leave(cmd_compare(argc, argv));
     if (cmd == "debug-kmers") return cmd_debug_kmers(argc, argv);
     if (cmd == "debug-records") return cmd_debug_records(argc, argv);

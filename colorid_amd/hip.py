@@ -115,6 +115,18 @@ class Index:
             words = np.ascontiguousarray(np.packbits(bits, bitorder="little").view("<u4"))
         check(self.lib.cid_index_put_records_subset(self.h, _p(buf), len(records) // rec, n_colors_file, _p(words)))
 
+    def put_records_folded(self, records: bytes, bloom_size_file):
+        """raw records of a file of this index's colours whose Bloom size is a multiple of the index's, OR-ed into row % bloom_size
+        (`colorid fold`)"""
+        rec = 24 + 4 * self.w32
+        assert len(records) % rec == 0
+        buf = np.frombuffer(records, np.uint8)
+        check(self.lib.cid_index_put_records_folded(self.h, _p(buf), len(records) // rec, bloom_size_file))
+
+    def put_index_folded(self, src):
+        """the rows of a finalized index of the same colours whose Bloom size is a multiple of this one's, OR-ed into row % bloom_size"""
+        check(self.lib.cid_index_put_index_folded(self.h, src.h))
+
     def put_dense(self, rows_u32):
         """rows_u32: bloom_size x w32 dense BitVec storage; only non-zero rows are sent (as a .bxi holds them)."""
         rows_u32 = np.ascontiguousarray(rows_u32, np.uint32).reshape(self.m, self.w32)

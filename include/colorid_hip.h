@@ -118,6 +118,22 @@ int cid_index_put_records_mapped(cid_index *, const uint8_t *records, size_t n_r
  * finalize. */
 int cid_index_put_records_subset(cid_index *, const uint8_t *records, size_t n_records, uint32_t n_colors_file,
                                  const uint32_t *keep_words);
+/* `colorid fold`: an index re-made at a smaller Bloom size without its genomes.  Every row is hash % bloom_size, so when the index's
+ * bloom_size divides bloom_size_file, OR-ing row r of the file into row r % bloom_size gives, bit for bit, the matrix a build at the
+ * smaller size makes; num_hash, k_size and the colours stay.  The records (cid_index_put_records' format, this index's n_colors) are
+ * taken as cid_index_put_records_subset takes them (256 MiB pieces through the ctx's upload buffer) and checked as cid_index_put_records
+ * checks them, on the device, against the FILE's shape — row < bloom_size_file — before a piece is applied: a refused piece changes
+ * nothing.  Rows are OR-ED, not stored: several rows of a file share an output row.  Call it once per chunk of a file, in any order
+ * and any split, then cid_index_finalize.  A factor of 1 is a plain OR-put.  Device memory: the index (at the SMALLER size) and one
+ * upload chunk of records, never the file's matrix — an index too large for the device can be folded down to one that fits.
+ * CID_ERR_INVALID: null argument, bloom_size_file 0 or not a multiple of the index's bloom_size, or a malformed record
+ * (cid_index_put_records' message); CID_ERR_STATE after finalize. */
+int cid_index_put_records_folded(cid_index *, const uint8_t *records, size_t n_records, uint64_t bloom_size_file);
+/* The same from a resident, finalized index `src` of the same n_colors on the same device (its all-zero rows contribute nothing), OR-ed
+ * into `dst`.  Device memory: both indices, nothing else.
+ * CID_ERR_INVALID: null argument, a source that is not finalized, of another n_colors, on another device, or whose bloom_size is not a
+ * multiple of dst's; CID_ERR_STATE when dst is finalized. */
+int cid_index_put_index_folded(cid_index *dst, const cid_index *src);
 /* Native device layout: row r at matrix + r*row_stride_words (u64 words, little-endian pairs of the u32 words,
  * zero padded).  Exposed so a caller can generate/fill an index in HBM directly (bits >= n_colors MUST be 0). */
 int cid_index_device_matrix(cid_index *, void **dev_ptr, uint64_t *row_stride_words);
