@@ -345,3 +345,114 @@ int search_perfect_codes(cid_ctx *c, const cid_index *ix, const uint64_t *d_code
 }  // extern "C++"
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ segmented search (cid_segments.hip)
+
+namespace {
+int check_segments_index(const cid_ctx *c, const cid_index *ix) {
+    int rc = check_ready(c, ix);
+    if (rc) return rc;
+    if ((rc = check_not_mini(ix))) return rc;
+    if (ix->rs > 128)
+        return fail(CID_ERR_UNSUPPORTED, "segmented search needs at most 8192 colours (index has %u): one cid_search_count per segment instead", ix->n_colors);
+    return CID_OK;
+}
+
+// device-resident inputs and outputs; `zero`: clear the outputs first (else they are added to); asynchronous on the ctx stream
+int search_segments_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs, uint64_t n_kmers,
+                           uint32_t *d_hits, uint8_t *d_missing, bool zero) {
+    if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
+    if (!d_seg_off || !d_hits || (n_kmers && !d_kmers)) return fail(CID_ERR_INVALID, "null argument");
+    if (d_kmers && !aligned16(d_kmers)) return fail(CID_ERR_INVALID, "d_kmers must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    cid::SegmentParams q;
+    int rc = fill_search_params(c, ix, q.s);
+    if (rc) return rc;
+    q.s.kmers = d_kmers; q.s.n_kmers = n_kmers;
+    q.s.tiles_per_block = pick_tiles_per_block(c, n_kmers);
+    q.seg_off = d_seg_off; q.n_segs = n_segs; q.hits = d_hits; q.missing = d_missing;
+    if (zero) {
+        HIP_TRY(hipMemsetAsync(d_hits, 0, n_segs * (size_t)ix->n_colors * 4, c->stream));
+        if (d_missing) HIP_TRY(hipMemsetAsync(d_missing, 0, n_segs, c->stream));
+    }
+    HIP_TRY(cid::launch_search_segments(q, c->stream));
+    return CID_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int cid_search_segments_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs, uint64_t n_kmers,
+                            uint32_t *d_hits, uint8_t *d_any_row_missing) {
+    int rc = check_segments_index(c, ix);
+    if (rc) return rc;
+    if (n_segs == 0) return CID_OK;
+    return search_segments_launch(c, ix, d_kmers, d_seg_off, n_segs, n_kmers, d_hits, d_any_row_missing, true);
+}
+
+// Host-pointer form.  The device copy of `hits` holds a slice of segments (dense_report_bytes); a slice's k-mers go up in chunks of
+// upload_chunk_bytes, each with its own offsets: the slice's segments clipped to the chunk, so a segment cut by a chunk boundary is
+// counted in two launches that add into the same row.
+int cid_search_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint64_t *seg_off, size_t n_segs, uint32_t *hits,
+                        uint8_t *any_row_missing) {
+    int rc = check_segments_index(c, ix);
+    if (rc) return rc;
+    if (n_segs == 0) return CID_OK;
+    if (!seg_off || !hits) return fail(CID_ERR_INVALID, "null argument");
+    if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
+    if (seg_off[0] != 0) return fail(CID_ERR_INVALID, "seg_off[0] must be 0");
+    for (size_t s = 0; s < n_segs; ++s) {
+        if (seg_off[s + 1] < seg_off[s]) return fail(CID_ERR_INVALID, "seg_off decreases at segment %zu", s);
+        if (seg_off[s + 1] - seg_off[s] >= (1ull << 32)) return fail(CID_ERR_INVALID, "segment %zu has 2^32 k-mers or more", s);
+    }
+    const uint64_t n_kmers = seg_off[n_segs];
+    if (n_kmers && !kmers) return fail(CID_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t C = ix->n_colors, k = ix->k;
+    size_t chunk = (size_t)c->tune.upload_chunk_bytes / (k + 8);
+    chunk = (chunk + 63) & ~(size_t)63;
+    if (chunk == 0) chunk = 64;                  // a budget below k + 8 bytes (0 included) still moves a tile per chunk
+    if (chunk > n_kmers) chunk = n_kmers ? (size_t)n_kmers : 1;
+    size_t per_slice = (size_t)(c->tune.dense_report_bytes / (C * 4));
+    if (per_slice == 0) per_slice = 1;
+    if (per_slice > n_segs) per_slice = n_segs;
+    void *d_k, *d_hits, *d_miss, *d_off;
+    rc = slot_reserve(c, S_KMERS, chunk * k, &d_k); if (rc) return rc;
+    rc = slot_reserve(c, S_REPORT, per_slice * C * 4, &d_hits); if (rc) return rc;
+    rc = slot_reserve(c, S_NK, per_slice, &d_miss); if (rc) return rc;
+    std::vector<uint64_t> loc;   // the slice's chunks' offset arrays, one after the other
+    struct Piece { size_t k0, nk, sa, n_loc, loc0; };
+    std::vector<Piece> pieces;
+    for (size_t s0 = 0; s0 < n_segs; s0 += per_slice) {
+        const size_t s1 = std::min(n_segs, s0 + per_slice);
+        loc.clear();
+        pieces.clear();
+        size_t sa = s0;
+        for (uint64_t k0 = seg_off[s0]; k0 < seg_off[s1]; k0 += chunk) {
+            const uint64_t k1 = std::min<uint64_t>(seg_off[s1], k0 + chunk);
+            while (seg_off[sa + 1] <= k0) ++sa;          // the segment that holds k-mer k0
+            size_t sb = sa;
+            while (seg_off[sb + 1] < k1) ++sb;           // the one that holds k-mer k1 - 1
+            pieces.push_back(Piece{(size_t)k0, (size_t)(k1 - k0), sa, sb - sa + 1, loc.size()});
+            for (size_t s = sa; s <= sb + 1; ++s) loc.push_back(std::min(std::max(seg_off[s], k0), k1) - k0);
+        }
+        HIP_TRY(hipMemsetAsync(d_hits, 0, (s1 - s0) * C * 4, c->stream));
+        HIP_TRY(hipMemsetAsync(d_miss, 0, s1 - s0, c->stream));
+        if (!pieces.empty()) {
+            rc = slot_reserve(c, S_SEQOFF, loc.size() * 8, &d_off); if (rc) return rc;
+            HIP_TRY(hipMemcpyAsync(d_off, loc.data(), loc.size() * 8, hipMemcpyHostToDevice, c->stream));
+        }
+        for (const Piece &pc : pieces) {
+            HIP_TRY(hipMemcpyAsync(d_k, kmers + pc.k0 * k, pc.nk * k, hipMemcpyHostToDevice, c->stream));
+            rc = search_segments_launch(c, ix, (const uint8_t *)d_k, (const uint64_t *)d_off + pc.loc0, pc.n_loc, pc.nk,
+                                        (uint32_t *)d_hits + (pc.sa - s0) * C, (uint8_t *)d_miss + (pc.sa - s0), false);
+            if (rc) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(hits + s0 * C, d_hits, (s1 - s0) * C * 4, hipMemcpyDeviceToHost, c->stream));
+        if (any_row_missing) HIP_TRY(hipMemcpyAsync(any_row_missing + s0, d_miss, s1 - s0, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return CID_OK;
+}
+
+}  // extern "C"

@@ -168,6 +168,16 @@ int grid_for(uint64_t n_kmers, uint32_t tiles_per_block);
 hipError_t launch_search_count(const SearchParams &p, hipStream_t stream);
 int search_count_blocks_per_cu(const SearchParams &p);
 hipError_t launch_search_perfect(const SearchParams &p, hipStream_t stream);
+// Segmented search (cid_segments.hip): segment s = k-mers [seg_off[s], seg_off[s+1]) of s.kmers; hits[s * n_colors + c] and missing[s]
+// are added to / set (caller zeroes).  Of `s` the a5 / a4 outputs and the stripe fields are unused; rows of at most 128 words.
+struct SegmentParams {
+    SearchParams s;
+    const uint64_t *seg_off;   // [n_segs + 1], non-decreasing, seg_off[0] = 0, seg_off[n_segs] = s.n_kmers
+    uint64_t n_segs;           // < 2^32
+    uint32_t *hits;            // [n_segs][n_colors]
+    uint8_t *missing;          // [n_segs], or nullptr
+};
+hipError_t launch_search_segments(const SegmentParams &p, hipStream_t stream);
 hipError_t launch_put_rows(uint64_t *mat, uint32_t rs, const uint64_t *d_row_ids, const uint32_t *d_words, uint32_t w32,
                            uint64_t n_rows, hipStream_t stream);
 hipError_t launch_put_records(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, uint32_t w_off, uint32_t w32_take,

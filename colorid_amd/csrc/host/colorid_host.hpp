@@ -380,6 +380,7 @@ void batch_search_mf(cid_ctx *, const std::vector<std::string> &files, const Big
 namespace batch_search_pe {
 void batch_search(cid_ctx *, const std::vector<std::string> &files1, const std::vector<std::string> &files2, const Bigsi &b,
                   int64_t filter, double cov, bool gene_search, uint8_t qual_offset);     // batch_search_pe.rs:9-179
+void batch_search_mf(cid_ctx *, const std::vector<std::string> &files, const Bigsi &b, double cov);   // -g -m: every FASTA record its own query
 }
 namespace read_id_mt_pe {
 // block-gzip (BGZF) fastq input on one GPU takes the device front end (cid_fastq_*) unless COLORID_DEVICE_FASTQ=0

@@ -341,6 +341,9 @@ void perfect_search::batch_search(cid_ctx *ctx, const std::vector<std::string> &
     }
 }
 
+// One cid_search_perfect call per record.  cid_search_segments could answer a batch of records in one launch (a colour is a perfect hit
+// of a segment iff its counter equals the segment's length; the flag is per segment), but that route has not been timed against
+// this one on a scheme-sized input, so `-s -m` stays here until it has ("Segmented search").
 void perfect_search::batch_search_mf(cid_ctx *ctx, const std::vector<std::string> &files, const Bigsi &b) {
     for (const std::string &file : files) {
         std::vector<std::string> labels, seqs;
@@ -433,6 +436,73 @@ void batch_search_pe::batch_search(cid_ctx *ctx, const std::vector<std::string> 
         if (!gene_search) generate_report(file1, b, hits, n_unique, sum_freq, uc, counts.data(), n_kmers, cov, have_modes ? &modes : nullptr);
         else generate_report_gene(file1, b, hits, n_kmers, cov);
     }
+}
+
+// ---------------------------------------------------------------------------------------------- every record its own query
+// `search -g -m`: the records of the query files, each with its own k-mer map, go to the GPU in batches — one
+// cid_search_segments call per batch, one segment per record — instead of one call per record.  One GPU and at most 8192 colours;
+// groups of GPUs, colour stripes and wider indices keep one call per record.
+static bool segments_route(const Bigsi &b) { return !g_group && b.colors.size() <= 8192; }
+
+struct SegmentBatch {
+    static constexpr size_t kKmerBytes = 32u << 20;    // k-mers of a batch
+    static constexpr size_t kHitsBytes = 256u << 20;   // its counters on the host: records x colours x 4 bytes
+    std::vector<uint8_t> keys;
+    std::vector<uint64_t> off{0};
+    std::vector<std::string> labels;
+    void push(const std::string &label, const KmerMap &km) {   // a record without k-mers is an empty segment
+        labels.push_back(label);
+        keys.insert(keys.end(), km.keys(), km.keys() + km.size() * km.k());
+        off.push_back(off.back() + km.size());
+    }
+    bool full(size_t n_colors) const { return keys.size() >= kKmerBytes || labels.size() * n_colors * 4 >= kHitsBytes; }
+    // emit(label, n_kmers, hits row) per record, in the order they were pushed
+    template <typename Emit>
+    void flush(cid_ctx *ctx, const Bigsi &b, Emit &&emit) {
+        const size_t n = labels.size(), C = b.colors.size();
+        if (n == 0) return;
+        std::vector<uint32_t> hits(n * C);
+        CID_TRY(cid_search_segments(ctx, b.index, keys.data(), off.data(), n, hits.data(), nullptr));
+        for (size_t i = 0; i < n; ++i) emit(labels[i], (size_t)(off[i + 1] - off[i]), hits.data() + i * C);
+        keys.clear();
+        off.assign(1, 0);
+        labels.clear();
+    }
+};
+
+// `search -g -m` on FASTA queries: every record is its own gene — the rows `search -g` prints for a file holding that record alone, with
+// the record's label in the first column.  (The reference offers -m "currently only with the -s option".)
+void batch_search_pe::batch_search_mf(cid_ctx *ctx, const std::vector<std::string> &files, const Bigsi &b, double cov) {
+    const bool segments = segments_route(b);
+    const size_t C = b.colors.size();
+    SegmentBatch batch;
+    std::vector<uint64_t> hits(C);
+    auto warn = [](const std::string &label) {
+        fprintf(stderr, "Warning! no kmers in query '%s'; maybe your kmer length is larger than your query length?\n", label.c_str());
+    };
+    auto emit = [&](const std::string &label, size_t n_kmers, const uint32_t *row) {
+        if (n_kmers == 0) return warn(label);
+        hits.assign(row, row + C);
+        generate_report_gene(label, b, hits, n_kmers, cov);
+    };
+    for (const std::string &file : files) {
+        fprintf(stderr, "%s\nCounting k-mers, this may take a while!\n", file.c_str());
+        std::vector<std::string> labels, seqs;
+        read_fasta_mf(file, labels, seqs);
+        for (size_t i = 0; i < labels.size(); ++i) {
+            KmerMap km((uint32_t)b.k_size);
+            if (i < seqs.size()) kmerize_vector({seqs[i]}, 1, km);   // -g's FASTA producer, cutoff 0 (batch_search_pe.rs:112-113)
+            if (segments) {
+                batch.push(labels[i], km);
+                if (batch.full(C)) batch.flush(ctx, b, emit);
+                continue;
+            }
+            if (km.size() == 0) { warn(labels[i]); continue; }
+            CID_TRY(hot_search_count(ctx, b, km.keys(), km.counts().data(), km.size(), hits.data(), nullptr, nullptr, nullptr));
+            generate_report_gene(labels[i], b, hits, km.size(), cov);
+        }
+    }
+    batch.flush(ctx, b, emit);
 }
 
 }  // namespace colorid

@@ -9,6 +9,7 @@
 // them are duplicates — the question before `subset -x`); fold (an index at a smaller Bloom size that divides its own, the file
 // `build -s` writes at that size: an over-sized index shrunk, or two indices brought to one size before `merge`).
 // Minimizer indices (.mxi): build -m [-v M], info, read_id, batch_id.  Not provided (outside the query path): read_filter.
+#include <algorithm>
 #include <cctype>
 #include <cerrno>
 #include <chrono>
@@ -604,6 +605,9 @@ int cmd_search(int argc, char **argv) {
     if (a.flags.count("perfect_search")) {
         if (a.flags.count("multi_fasta")) perfect_search::batch_search_mf(ctx, files1, b);
         else perfect_search::batch_search(ctx, files1, b);
+    } else if (a.flags.count("gene_search") && a.flags.count("multi_fasta") &&
+               std::none_of(files1.begin(), files1.end(), [](const std::string &f) { return ends_with(f, "gz"); })) {
+        batch_search_pe::batch_search_mf(ctx, files1, b, cov);   // -g -m: every FASTA record is its own query
     } else {
         batch_search_pe::batch_search(ctx, files1, files2, b, filter, cov, a.flags.count("gene_search") > 0, quality);
     }

@@ -184,6 +184,21 @@ class Index:
         check(self.lib.cid_search_perfect(self.ctx.h, self.h, _p(kmers), kmers.shape[0], _p(words), C.byref(missing)))
         return words, bool(missing.value)
 
+    # ---- segmented search: one row of counters per query
+    def search_segments(self, kmers, seg_off, want_missing=True):
+        """segment s = k-mers [seg_off[s], seg_off[s+1]) -> (hits[n_segs, n_colors] uint32, missing[n_segs] bool or None)"""
+        kmers = np.ascontiguousarray(kmers, np.uint8).reshape(-1, self.k)
+        seg_off = np.ascontiguousarray(seg_off, np.uint64)
+        n_segs = len(seg_off) - 1
+        hits = np.zeros((n_segs, self.n_colors), np.uint32)
+        missing = np.zeros(n_segs, np.uint8) if want_missing else None
+        check(self.lib.cid_search_segments(self.ctx.h, self.h, _p(kmers), _p(seg_off), n_segs, _p(hits), _p(missing)))
+        return hits, (missing.astype(bool) if want_missing else None)
+
+    def search_segments_dev(self, d_kmers, d_seg_off, n_segs, n_kmers, d_hits, d_missing=None):
+        check(self.lib.cid_search_segments_dev(self.ctx.h, self.h, vp(d_kmers), vp(d_seg_off), n_segs, n_kmers, vp(d_hits),
+                                               vp(d_missing) if d_missing else None))
+
     # ---- a6/a7/a9/a10
     def readid_count(self, bases, seq_off, read_seq0, d=1, start_sample=3):
         bases = np.ascontiguousarray(bases, np.uint8)

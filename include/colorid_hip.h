@@ -186,6 +186,24 @@ int cid_search_count_dev(cid_ctx *, const cid_index *, const uint8_t *d_kmers, c
                          size_t n_kmers, uint64_t *d_hits, uint64_t *d_n_unique, uint64_t *d_sum_unique_freq,
                          uint32_t *d_unique_colour);
 
+/* ---- Segmented search (EXTENDED): many queries in one launch — the records of a gene panel (`search -g -m`) or the alleles of a
+ *      scheme (`search -s -m`).  Segment s = k-mers [seg_off[s], seg_off[s+1]) of `kmers` (ASCII, k_size bytes each, distinct within a
+ *      segment: the caller's map, as for cid_search_count); seg_off has n_segs + 1 entries, seg_off[0] = 0.
+ *      hits[s * n_colors + c] = how many k-mers of segment s have colour c set in the AND of their n rows
+ *      (src/batch_search_pe.rs:125-164 per segment).  any_row_missing[s] (may be NULL) = 1 iff some k-mer of s has an all-zero row:
+ *      cid_search_perfect's flag per segment (src/perfect_search.rs:83-110).  Colour c is a perfect hit of s iff
+ *      seg_len > 0 && hits[s][c] == seg_len.  An empty segment gives a zero row and flag 0; n_segs == 0 is CID_OK.
+ *      CID_ERR_INVALID: a null argument, seg_off[0] != 0, a decreasing seg_off, a segment of 2^32 k-mers or more (host form);
+ *      CID_ERR_STATE: index not finalized; CID_ERR_UNSUPPORTED: a minimizer index, or more than 8192 colours (callers then make one
+ *      cid_search_count / cid_search_perfect call per segment).
+ *      _dev: everything in device memory, d_kmers 16-byte aligned, n_kmers = d_seg_off[n_segs]; asynchronous on the ctx stream; zeroes
+ *      its outputs.  The host form uploads in chunks of "upload_chunk_bytes" and keeps at most "dense_report_bytes" of `hits` on the
+ *      device at a time. ---- */
+int cid_search_segments(cid_ctx *, const cid_index *, const uint8_t *kmers, const uint64_t *seg_off, size_t n_segs,
+                        uint32_t *hits, uint8_t *any_row_missing);
+int cid_search_segments_dev(cid_ctx *, const cid_index *, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs,
+                            uint64_t n_kmers, uint32_t *d_hits, uint8_t *d_any_row_missing);
+
 /* Same, for k-mers given as 2-bit codes (k_size <= 32): one u64 per canonical UPPER-CASE k-mer, base 0 in the most
  * significant of the 2*k_size low bits, A,C,G,T = 0..3 (8 bytes of input per k-mer instead of k_size). */
 int cid_search_count_codes_dev(cid_ctx *, const cid_index *, const uint64_t *d_codes, const uint32_t *d_freq,
