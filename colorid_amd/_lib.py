@@ -14,6 +14,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("COLORID_HIP_LIB") or os.path.join(_HERE, "libcolorid_hip.so")  # override: A/B experiments
 _LIB = None
 
+# the return codes of include/colorid_hip.h
+CID_OK = 0
+CID_ERR_INVALID = -1
+CID_ERR_HIP = -2
+CID_ERR_NOMEM = -3
+CID_ERR_UNSUPPORTED = -4
+CID_ERR_STATE = -5
+
 u8p, u32p, u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 vp = C.c_void_p
 
@@ -70,6 +78,9 @@ SIGNATURES = {
     "cid_bgzf_inflate": (C.c_int, [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "cid_bgzf_inflate_start": (C.c_int, [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t, C.c_size_t]),
     "cid_bgzf_inflate_finish": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "cid_bgzf_deflate_bound": (C.c_size_t, [C.c_size_t]),
+    "cid_bgzf_deflate": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.POINTER(C.c_size_t)]),
+    "cid_bgzf_deflate_dev": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(C.c_size_t)]),
     "cid_kmerset_create": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
     "cid_kmerset_add_seqs": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_int]),
     "cid_kmerset_add_seqs_dev": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_uint64, C.c_int]),
@@ -139,6 +150,8 @@ SIGNATURES = {
     "cid_fastq_classify_begin": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_int]),
     "cid_fastq_classify_end": (C.c_int, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "cid_fastq_fetch": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "cid_fastq_keep_steps": (C.c_int, [vp, C.c_int]),
+    "cid_fastq_filter": (C.c_int, [vp, vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     "cid_fastq_destroy": (None, [vp]),
     "cid_timer_start": (C.c_int, [vp]),
     "cid_timer_stop_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
@@ -180,5 +193,5 @@ def load_library():
 
 
 def check(rc):
-    if rc != 0:
+    if rc != CID_OK:
         raise CidError(rc, load_library().cid_last_error().decode(errors="replace"))

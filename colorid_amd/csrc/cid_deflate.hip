@@ -1,0 +1,468 @@
+// Block-gzip (BGZF) members WRITTEN on the device: the mirror image of cid_inflate.hip, for read_id --taxon (the kept reads leave the
+// GPU compressed; gzip at the default level on the host's cores would cost several times the classification).
+//   text in HBM, cut every 65 280 bytes (htslib's block size: a stored block always fits a 64 KiB member)
+//     --k_bgzf_deflate, one wave per piece--> a whole member in a fixed slot: gzip header with the "BC" field | DEFLATE | CRC-32 | ISIZE
+//     --one scan over the members' lengths, k_bgzf_gather--> the members back to back.
+// The DEFLATE stream is ONE dynamic-Huffman block over literals and end-of-block (no LZ77 matches: DESIGN.md §5 says what that costs
+// against zlib), or one stored block when that would not be smaller — so no member is longer than its text + 31 bytes:
+//   histogram of the piece's bytes in LDS -> Huffman code lengths (rank sort by all lanes, the two-queue merge by one lane, depths by
+//   all lanes), limited to 15 bits by moving leaves down until the Kraft sum is exactly one (zlib refuses an incomplete or
+//   over-subscribed literal/length set) -> canonical codes -> the same for the code-length alphabet (7 bits) -> every size is known
+//   before a bit is written, BSIZE included -> the literals coded 1 KiB a round: a lane looks up its 16 bytes, a wave prefix sum over
+//   the lanes' bit counts gives every lane its bit offset, the lanes OR their bits into a ring of 512 words in LDS, and the words a
+//   round completes leave as one coalesced store.
+// The output is a function of the text alone: LDS atomics only add counts and OR disjoint bits, no atomic decides a byte's position.
+#include "cid_api_common.hpp"
+#include "cid_scan.hpp"
+
+using cid::fail;
+
+namespace cid {
+
+constexpr uint32_t kDefBlock = 65280;            // text bytes per member
+constexpr uint32_t kDefSlot = kDefBlock + 32;    // a member's slot: text + 31 at most, rounded up to whole words
+constexpr uint32_t kDefStage = 512;              // ring of output words in LDS: a round adds 64 lanes x 16 bytes x 15 bits = 480 words at most
+constexpr uint32_t kDefLit = 257;                // literals + end-of-block
+constexpr uint32_t kDefLens = kDefLit + 2;       // + two distance codes of one bit (never used; a complete set, as zlib writes it)
+
+struct CrcShift1K { uint32_t m[32]; };   // column j: the CRC register 1 << j after 1024 zero bytes
+
+struct DefLds {
+    uint32_t freq[kDefLit + 3];
+    uint32_t tab[kDefLit + 3];     // per literal: its code, bit-reversed (DEFLATE packs Huffman codes from the top bit) | length << 16
+    uint8_t len[kDefLens + 5];
+    uint32_t clfreq[20], cltab[20];
+    uint8_t cllen[20];
+    uint32_t blc[17], next[17];
+    uint32_t stage[kDefStage];
+    union {
+        uint32_t crc[1024];                                              // slicing-by-4 tables
+        struct { uint32_t w[520]; uint16_t parent[520], order[264]; } b;   // the tree: leaves by ascending weight, then the merged nodes
+    } u;
+};
+
+__device__ __forceinline__ uint32_t def_wave_sum(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Code lengths (<= maxbits) and canonical codes of the symbols with freq != 0; false when fewer than two symbols are used (no caller
+// here can get there: a piece holds a literal and the end-of-block; the lengths hold a zero or two values).  The whole wave calls it.
+__device__ bool def_huffman(const uint32_t *freq, uint32_t n, uint32_t maxbits, uint8_t *len, uint32_t *tab, DefLds &S, uint32_t lane) {
+    uint32_t cnt = 0;
+    for (uint32_t s = lane; s < n; s += 64) cnt += freq[s] != 0;
+    cnt = def_wave_sum(cnt);
+    if (cnt < 2) return false;
+    // rank of every used symbol by (weight, symbol)
+    for (uint32_t s = lane; s < n; s += 64) {
+        const uint32_t f = freq[s];
+        len[s] = 0;
+        if (!f) continue;
+        uint32_t r = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            const uint32_t g = freq[j];
+            r += (g != 0) && (g < f || (g == f && j < s));
+        }
+        S.u.b.order[r] = (uint16_t)s;
+        S.u.b.w[r] = f;
+    }
+    if (lane < 17) S.blc[lane] = 0;
+    __syncthreads();
+    // the two-queue merge: leaves and merged nodes are both in ascending weight, the two lightest heads make the next node
+    const uint32_t root = 2 * cnt - 2;
+    if (lane == 0) {
+        uint32_t i = 0, j = cnt;
+        for (uint32_t k = cnt; k <= root; ++k) {
+            uint32_t pick[2];
+            for (int t = 0; t < 2; ++t) pick[t] = (i < cnt && (j >= k || S.u.b.w[i] <= S.u.b.w[j])) ? i++ : j++;
+            S.u.b.w[k] = S.u.b.w[pick[0]] + S.u.b.w[pick[1]];
+            S.u.b.parent[pick[0]] = (uint16_t)k;
+            S.u.b.parent[pick[1]] = (uint16_t)k;
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = lane; i < cnt; i += 64) {
+        uint32_t d = 0;
+        for (uint32_t node = i; node != root; node = S.u.b.parent[node]) ++d;
+        atomicAdd(&S.blc[d < maxbits ? d : maxbits], 1u);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        // leaves deeper than maxbits were counted AT maxbits: the set is over-subscribed by `total - 2^maxbits` codes of that length.
+        // Each turn takes one leaf off the deepest level, moves a leaf of the nearest shallower level one down and hangs the first
+        // beside it: the Kraft sum falls by 2^-maxbits, until it is exactly one.
+        uint32_t total = 0;
+        for (uint32_t l = 1; l <= maxbits; ++l) total += S.blc[l] << (maxbits - l);
+        while (total > (1u << maxbits)) {
+            S.blc[maxbits] -= 1;
+            for (uint32_t l = maxbits - 1; l > 0; --l)
+                if (S.blc[l]) { S.blc[l] -= 1; S.blc[l + 1] += 2; break; }
+            --total;
+        }
+        uint32_t code = 0;
+        S.blc[0] = 0;
+        for (uint32_t l = 1; l <= maxbits; ++l) { code = (code + S.blc[l - 1]) << 1; S.next[l] = code; }
+    }
+    __syncthreads();
+    // the heaviest symbol takes the shortest length
+    for (uint32_t i = lane; i < cnt; i += 64) {
+        const uint32_t p = cnt - 1 - i;
+        uint32_t acc = 0, l = 1;
+        for (; l < maxbits; ++l) { acc += S.blc[l]; if (p < acc) break; }
+        len[S.u.b.order[i]] = (uint8_t)l;
+    }
+    __syncthreads();
+    // canonical codes: symbols of one length count up in symbol order
+    for (uint32_t base = 0; base < n; base += 64) {
+        const uint32_t s = base + lane, L = s < n ? len[s] : 0u;
+        uint64_t todo = __ballot(L != 0);
+        uint32_t code = 0;
+        while (todo) {
+            const uint32_t Lf = (uint32_t)__shfl((int)L, __builtin_ctzll(todo), 64);
+            const uint64_t m = __ballot(L == Lf);
+            const uint32_t nx = S.next[Lf];
+            if (L == Lf) code = nx + (uint32_t)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+            __syncthreads();
+            if (lane == 0) S.next[Lf] = nx + (uint32_t)__builtin_popcountll(m);
+            __syncthreads();
+            todo &= ~m;
+        }
+        if (s < n) tab[s] = L ? ((__brev(code) >> (32 - L)) | (L << 16)) : 0u;
+    }
+    __syncthreads();
+    return true;
+}
+
+struct DefSink {
+    uint32_t *stage, *outw;
+    uint32_t bitpos, flushed;   // bits written so far; words already in the slot
+};
+// `v` (no bit set at or above its length) at bit `pos` of the member
+__device__ __forceinline__ void def_deposit(uint32_t *stage, uint64_t v, uint32_t pos) {
+    const uint32_t sh = pos & 31u, w = pos >> 5;
+    const uint64_t lo = v << sh;
+    const uint32_t a = (uint32_t)lo, b = (uint32_t)(lo >> 32), hi = sh ? (uint32_t)(v >> (64 - sh)) : 0u;
+    if (a) atomicOr(&stage[w & (kDefStage - 1)], a);
+    if (b) atomicOr(&stage[(w + 1) & (kDefStage - 1)], b);
+    if (hi) atomicOr(&stage[(w + 2) & (kDefStage - 1)], hi);
+}
+// every lane appends up to four pieces of bits, lane 0's first; at most 480 words a call
+__device__ __forceinline__ void def_put(DefSink &k, uint32_t lane, const uint64_t v[4], const uint32_t nb[4]) {
+    const uint32_t tot = nb[0] + nb[1] + nb[2] + nb[3];
+    uint32_t incl = tot;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t up = __shfl_up(incl, d, 64);
+        if ((int)lane >= d) incl += up;
+    }
+    uint32_t pos = k.bitpos + incl - tot;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (nb[q]) def_deposit(k.stage, v[q], pos);
+        pos += nb[q];
+    }
+    k.bitpos += (uint32_t)__shfl((int)incl, 63, 64);
+    __syncthreads();
+    const uint32_t wend = k.bitpos >> 5;
+    for (uint32_t w = k.flushed + lane; w < wend; w += 64) {
+        k.outw[w] = k.stage[w & (kDefStage - 1)];
+        k.stage[w & (kDefStage - 1)] = 0;
+    }
+    k.flushed = wend;
+    __syncthreads();
+}
+
+__device__ __forceinline__ uint32_t def_load4(const uint8_t *p, uint32_t at, uint32_t n) {   // bytes at .. at + 3 of a piece of n bytes, zeros behind it
+    if (at + 4 <= n) { uint32_t w; __builtin_memcpy(&w, p + at, 4); return w; }
+    uint32_t w = 0;
+    for (uint32_t i = 0; i < 4 && at + i < n; ++i) w |= (uint32_t)p[at + i] << (8 * i);
+    return w;
+}
+
+__global__ __launch_bounds__(64) void k_bgzf_deflate(const uint8_t *text, uint64_t text_bytes, uint32_t n_members, uint8_t *slots, uint32_t *member_len,
+                                                     CrcShift1K shift) {
+    __shared__ DefLds S;
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t mi = blockIdx.x; mi < n_members; mi += gridDim.x) {
+        const uint8_t *src = text + (uint64_t)mi * kDefBlock;
+        const uint64_t left = text_bytes - (uint64_t)mi * kDefBlock;
+        const uint32_t n = left < kDefBlock ? (uint32_t)left : kDefBlock;   // >= 1
+        uint8_t *slot = slots + (uint64_t)mi * kDefSlot;
+        __syncthreads();
+        // ---- CRC-32 (RFC 1952 8): a lane per slice of 1 KiB, the slices aligned to the END of the piece so that every slice but the first is
+        // whole; slicing by 4; the lanes' registers folded with the "append 1024 zero bytes" operator (as k_bgzf_inflate_wave checks it)
+        uint32_t *ct = S.u.crc;
+        for (uint32_t i = lane; i < 256; i += 64) {
+            uint32_t c = i;
+            for (int b = 0; b < 8; ++b) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
+            ct[i] = c;
+        }
+        __syncthreads();
+        for (uint32_t i = lane; i < 256; i += 64) {
+            uint32_t c = ct[i];
+            for (int t = 1; t < 4; ++t) { c = ct[c & 0xFFu] ^ (c >> 8); ct[256 * t + i] = c; }
+        }
+        for (uint32_t i = lane; i < kDefLit + 3; i += 64) S.freq[i] = 0;
+        for (uint32_t i = lane; i < kDefStage; i += 64) S.stage[i] = 0;
+        if (lane < 20) S.clfreq[lane] = 0;
+        __syncthreads();
+        const uint32_t n_slices = (n + 1023u) / 1024u, first_len = n - (n_slices - 1u) * 1024u;
+        uint32_t c = 0;
+        if (lane < n_slices) {
+            const uint32_t b0 = lane == 0 ? 0u : first_len + (lane - 1u) * 1024u, b1 = lane == 0 ? first_len : b0 + 1024u;
+            c = lane == 0 ? 0xFFFFFFFFu : 0u;
+            uint32_t i = b0;
+            for (; i < b1 && ((b1 - i) & 3u); ++i) c = ct[(c ^ src[i]) & 0xFFu] ^ (c >> 8);
+            for (; i < b1; i += 4) {
+                uint32_t wd;
+                __builtin_memcpy(&wd, src + i, 4);
+                c ^= wd;
+                c = ct[768 + (c & 0xFFu)] ^ ct[512 + ((c >> 8) & 0xFFu)] ^ ct[256 + ((c >> 16) & 0xFFu)] ^ ct[c >> 24];
+            }
+        }
+        uint32_t reg = 0xFFFFFFFFu;
+        for (uint32_t sl = 0; sl < n_slices; ++sl) {
+            const uint32_t cs = (uint32_t)__shfl((int)c, (int)sl, 64);
+            if (sl == 0) reg = cs;
+            else {
+                uint32_t rr = 0;
+                for (uint32_t j = 0; j < 32; ++j) rr ^= shift.m[j] & (0u - ((reg >> j) & 1u));
+                reg = rr ^ cs;
+            }
+        }
+        const uint32_t crc = reg ^ 0xFFFFFFFFu;
+        // ---- histogram of the piece (coalesced: a lane takes 4 bytes of every 256)
+        for (uint32_t at = lane * 4; at < n; at += 256) {
+            const uint32_t w = def_load4(src, at, n), k = n - at < 4 ? n - at : 4;
+            for (uint32_t i = 0; i < k; ++i) atomicAdd(&S.freq[(w >> (8 * i)) & 0xFFu], 1u);
+        }
+        if (lane == 0) S.freq[256] = 1;
+        __syncthreads();   // (the CRC tables are done with: the tree takes their place)
+        bool coded = def_huffman(S.freq, kDefLit, 15, S.len, S.tab, S, lane);
+        uint32_t data_bits = 0, hdr_bits = 0, ncl = 4;
+        if (coded) {
+            for (uint32_t s = lane; s < kDefLit; s += 64) data_bits += S.freq[s] * S.len[s];
+            data_bits = def_wave_sum(data_bits);
+            if (lane == 0) { S.len[kDefLit] = 1; S.len[kDefLit + 1] = 1; }
+            __syncthreads();
+            for (uint32_t s = lane; s < kDefLens; s += 64) atomicAdd(&S.clfreq[S.len[s]], 1u);
+            __syncthreads();
+            coded = def_huffman(S.clfreq, 19, 7, S.cllen, S.cltab, S, lane);
+        }
+        const uint8_t cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+        if (coded) {
+            for (uint32_t i = 4; i < 19; ++i) if (S.cllen[cl_order[i]]) ncl = i + 1;
+            hdr_bits = lane < 19 ? S.clfreq[lane] * S.cllen[lane] : 0u;
+            hdr_bits = def_wave_sum(hdr_bits) + 17u + 3u * ncl;
+        }
+        const uint32_t coded_bytes = 18u + (hdr_bits + data_bits + 7u) / 8u + 8u, stored_bytes = n + 31u;
+        const bool use_coded = coded && coded_bytes < stored_bytes;   // not smaller -> stored
+        const uint32_t total = use_coded ? coded_bytes : stored_bytes;
+        // the gzip header (RFC 1952; the "BC" extra field of the SAM specification 4.1: BSIZE = the member's length - 1)
+        const uint64_t h0 = 0x1Full | (0x8Bull << 8) | (8ull << 16) | (4ull << 24);                    // magic, deflate, FEXTRA, mtime 0 (2 of 4 bytes)
+        const uint64_t h1 = (0xFFull << 24) | (6ull << 32);                                            // mtime, xfl 0, os 255, XLEN 6
+        const uint64_t h2 = 0x42ull | (0x43ull << 8) | (2ull << 16) | ((uint64_t)(total - 1u) << 32);  // 'B' 'C' SLEN 2, BSIZE
+        if (use_coded) {
+            DefSink sink{S.stage, reinterpret_cast<uint32_t *>(slot), 0u, 0u};
+            uint64_t v[4] = {0, 0, 0, 0};
+            uint32_t nb[4] = {0, 0, 0, 0};
+            if (lane == 0) {
+                v[0] = h0; v[1] = h1; v[2] = h2; nb[0] = nb[1] = nb[2] = 48;
+                v[3] = 1ull | (2ull << 1) | (0ull << 3) | (1ull << 8) | ((uint64_t)(ncl - 4u) << 13);   // BFINAL, dynamic, HLIT 257, HDIST 2, HCLEN
+                nb[3] = 17;
+            }
+            def_put(sink, lane, v, nb);
+            v[0] = v[1] = v[2] = v[3] = 0; nb[0] = nb[1] = nb[2] = nb[3] = 0;
+            if (lane == 0) {
+                for (uint32_t i = 0; i < ncl; ++i) v[0] |= (uint64_t)S.cllen[cl_order[i]] << (3 * i);
+                nb[0] = 3 * ncl;
+            }
+            def_put(sink, lane, v, nb);
+            v[0] = 0; nb[0] = 0;
+            for (uint32_t s = lane * 5; s < lane * 5 + 5 && s < kDefLens; ++s) {
+                const uint32_t e = S.cltab[S.len[s]];
+                v[0] |= (uint64_t)(e & 0xFFFFu) << nb[0];
+                nb[0] += e >> 16;
+            }
+            def_put(sink, lane, v, nb);
+            for (uint32_t base = 0; base < n; base += 1024) {
+                const uint32_t at = base + lane * 16;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    v[q] = 0; nb[q] = 0;
+                    const uint32_t a = at + 4 * q;
+                    if (a < n) {
+                        const uint32_t w = def_load4(src, a, n), k = n - a < 4 ? n - a : 4;
+                        for (uint32_t i = 0; i < k; ++i) {
+                            const uint32_t e = S.tab[(w >> (8 * i)) & 0xFFu];
+                            v[q] |= (uint64_t)(e & 0xFFFFu) << nb[q];
+                            nb[q] += e >> 16;
+                        }
+                    }
+                }
+                def_put(sink, lane, v, nb);
+            }
+            v[0] = v[1] = v[2] = v[3] = 0; nb[0] = nb[1] = nb[2] = nb[3] = 0;
+            if (lane == 0) {
+                const uint32_t e = S.tab[256];
+                v[0] = e & 0xFFFFu; nb[0] = e >> 16;
+                nb[1] = (0u - (sink.bitpos + nb[0])) & 7u;             // the stream ends on a byte boundary
+                v[2] = (uint64_t)crc | ((uint64_t)n << 32); nb[2] = 64;
+            }
+            def_put(sink, lane, v, nb);
+            if (lane == 0 && (sink.bitpos & 31u)) sink.outw[sink.flushed] = S.stage[sink.flushed & (kDefStage - 1)];
+            __syncthreads();
+            if (lane == 0) S.stage[sink.flushed & (kDefStage - 1)] = 0;
+        } else {
+            // one stored block: BFINAL | stored, LEN, ~LEN, the bytes
+            if (lane == 0) {
+                for (int i = 0; i < 6; ++i) { slot[i] = (uint8_t)(h0 >> (8 * i)); slot[6 + i] = (uint8_t)(h1 >> (8 * i)); slot[12 + i] = (uint8_t)(h2 >> (8 * i)); }
+                slot[18] = 1;
+                slot[19] = (uint8_t)n; slot[20] = (uint8_t)(n >> 8); slot[21] = (uint8_t)~n; slot[22] = (uint8_t)(~n >> 8);
+                uint8_t *t = slot + 23 + n;
+                for (int i = 0; i < 4; ++i) { t[i] = (uint8_t)(crc >> (8 * i)); t[4 + i] = (uint8_t)(n >> (8 * i)); }
+            }
+            for (uint32_t i = lane; i < n; i += 64) slot[23 + i] = src[i];
+        }
+        if (lane == 0) member_len[mi] = total;
+    }
+}
+
+// member i's bytes from its slot to members + off[i]; whole words of the destination, the source read through two aligned words
+__global__ __launch_bounds__(256) void k_bgzf_gather(const uint8_t *slots, const uint32_t *member_len, const uint64_t *off, uint32_t n_members, uint8_t *members,
+                                                     uint64_t *total) {
+    if (blockIdx.x == 0 && threadIdx.x == 0 && total) *total = off[n_members];
+    for (uint32_t mi = blockIdx.x; mi < n_members; mi += gridDim.x) {
+        const uint8_t *src = slots + (uint64_t)mi * kDefSlot;
+        uint8_t *dst = members + off[mi];
+        const uint32_t len = member_len[mi];
+        const uint32_t head = (uint32_t)((0u - (uint32_t)reinterpret_cast<uintptr_t>(dst)) & 3u) < len ? (uint32_t)((0u - (uint32_t)reinterpret_cast<uintptr_t>(dst)) & 3u) : len;
+        const uint32_t words = (len - head) / 4, tail = head + words * 4;
+        if (threadIdx.x < head) dst[threadIdx.x] = src[threadIdx.x];
+        if (threadIdx.x < len - tail) dst[tail + threadIdx.x] = src[tail + threadIdx.x];
+        const uint32_t *sw = reinterpret_cast<const uint32_t *>(src);   // (slots are whole words; `head` is the source's misalignment)
+        uint32_t *dw = reinterpret_cast<uint32_t *>(dst + head);
+        for (uint32_t k = threadIdx.x; k < words; k += 256) {
+            const uint32_t a = sw[k], b = head ? sw[k + 1] : 0u;   // (k + 1 stays inside the slot: head > 0 leaves bytes behind word k)
+            dw[k] = head ? (a >> (8 * head)) | (b << (32 - 8 * head)) : a;
+        }
+    }
+}
+
+struct DefLenIn {   // the members' lengths and a zero behind them
+    const uint32_t *p;
+    uint64_t n;
+    __device__ uint64_t operator()(uint64_t i) const { return i < n ? p[i] : 0ull; }
+};
+
+static CrcShift1K make_crc_shift_1k() {
+    uint32_t tab[256];
+    for (uint32_t i = 0; i < 256; ++i) {
+        uint32_t c = i;
+        for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
+        tab[i] = c;
+    }
+    CrcShift1K s;
+    for (uint32_t j = 0; j < 32; ++j) {
+        uint32_t c = 1u << j;
+        for (int i = 0; i < 1024; ++i) c = tab[c & 0xFFu] ^ (c >> 8);
+        s.m[j] = c;
+    }
+    return s;
+}
+
+hipError_t warm_deflate() {
+    hipFuncAttributes a;
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_bgzf_deflate));
+}
+
+size_t bgzf_deflate_members(size_t text_bytes) { return (text_bytes + kDefBlock - 1) / kDefBlock; }
+
+// d_text (16-byte aligned) -> d_members (>= cid_bgzf_deflate_bound bytes), d_member_len [n], *d_total = the members' bytes; scratch from
+// the ctx's block cache, returned behind the kernels on the same stream
+int bgzf_deflate_launch(cid_ctx *c, hipStream_t st, const uint8_t *d_text, size_t text_bytes, uint8_t *d_members, uint32_t *d_member_len, uint64_t *d_total) {
+    const size_t n = bgzf_deflate_members(text_bytes);
+    if (n == 0) {
+        if (d_total) HIP_TRY(hipMemsetAsync(d_total, 0, 8, st));
+        return CID_OK;
+    }
+    if (n >= (1ull << 31)) return fail(CID_ERR_UNSUPPORTED, "cid_bgzf_deflate: more than 2^31 members in one call");
+    static const CrcShift1K shift = make_crc_shift_1k();
+    void *slots = nullptr, *off = nullptr, *state = nullptr;
+    int rc;
+    if ((rc = ctx_alloc(c, n * kDefSlot + 16, &slots))) return rc;
+    if ((rc = ctx_alloc(c, (n + 1) * 8, &off))) { ctx_free(c, slots); return rc; }
+    if ((rc = ctx_alloc(c, scan_state_words(n + 1) * 8, &state))) { ctx_free(c, slots); ctx_free(c, off); return rc; }
+    auto done = [&](int code) { ctx_free(c, slots); ctx_free(c, off); ctx_free(c, state); return code; };
+    const unsigned grid = (unsigned)std::min<size_t>(n, (size_t)c->n_cu * 16);
+    hipLaunchKernelGGL(k_bgzf_deflate, dim3(grid), dim3(64), 0, st, d_text, (uint64_t)text_bytes, (uint32_t)n, (uint8_t *)slots, d_member_len, shift);
+    hipError_t e = hipGetLastError();
+    // off[i] = the bytes of the members before i (the element behind the last one is zero: its prefix is the total)
+    if (e == hipSuccess) e = scan_launch(DefLenIn{d_member_len, n}, ScanOutU64{(uint64_t *)off, 0ull}, n + 1, (uint64_t *)state, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_bgzf_gather, dim3((unsigned)std::min<size_t>(n, 65535)), dim3(256), 0, st, (const uint8_t *)slots, (const uint32_t *)d_member_len,
+                           (const uint64_t *)off, (uint32_t)n, d_members, d_total);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return done(fail(CID_ERR_HIP, "cid_bgzf_deflate: %s", hipGetErrorString(e)));
+    return done(CID_OK);
+}
+
+}  // namespace cid
+
+extern "C" {
+
+size_t cid_bgzf_deflate_bound(size_t text_bytes) { return text_bytes + 31 * cid::bgzf_deflate_members(text_bytes); }
+
+int cid_bgzf_deflate_dev(cid_ctx *c, const uint8_t *d_text, size_t text_bytes, uint8_t *d_members, size_t members_cap, uint64_t *d_members_bytes,
+                         uint32_t *d_member_len, size_t *n_members) {
+    if (!c || !n_members) return fail(CID_ERR_INVALID, "null argument");
+    *n_members = cid::bgzf_deflate_members(text_bytes);
+    if (text_bytes && (!d_text || !d_members || !d_member_len)) return fail(CID_ERR_INVALID, "null argument");
+    if (!cid::aligned16(d_text)) return fail(CID_ERR_INVALID, "cid_bgzf_deflate_dev: the text must be 16-byte aligned");
+    if (members_cap < cid_bgzf_deflate_bound(text_bytes))
+        return fail(CID_ERR_INVALID, "cid_bgzf_deflate_dev: %zu bytes of room for the members, cid_bgzf_deflate_bound asks for %zu", members_cap,
+                    cid_bgzf_deflate_bound(text_bytes));
+    HIP_TRY(hipSetDevice(c->device));
+    return cid::bgzf_deflate_launch(c, c->stream, d_text, text_bytes, d_members, d_member_len, d_members_bytes);
+}
+
+int cid_bgzf_deflate(cid_ctx *c, const uint8_t *text, size_t text_bytes, uint8_t *members, size_t members_cap, size_t *members_bytes,
+                     uint32_t *member_len, size_t *n_members) {
+    if (!c || !members_bytes || !n_members) return fail(CID_ERR_INVALID, "null argument");
+    *members_bytes = 0;
+    const size_t n = *n_members = cid::bgzf_deflate_members(text_bytes);
+    if (n == 0) return CID_OK;
+    if (!text || !members || !member_len) return fail(CID_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bound = cid_bgzf_deflate_bound(text_bytes);
+    void *d_text = nullptr, *d_out = nullptr, *d_len = nullptr;
+    int rc;
+    if ((rc = cid::ctx_alloc(c, text_bytes + 16, &d_text))) return rc;
+    if ((rc = cid::ctx_alloc(c, bound + 16, &d_out))) { cid::ctx_free(c, d_text); return rc; }
+    if ((rc = cid::ctx_alloc(c, n * 4 + 16, &d_len))) { cid::ctx_free(c, d_text); cid::ctx_free(c, d_out); return rc; }
+    uint64_t *d_total = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(d_len) + ((n * 4 + 7) & ~(size_t)7));
+    auto done = [&](int code) {
+        (void)hipStreamSynchronize(c->stream);
+        cid::ctx_free(c, d_text); cid::ctx_free(c, d_out); cid::ctx_free(c, d_len);
+        return code;
+    };
+    hipError_t e = hipMemcpyAsync(d_text, text, text_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) return done(fail(CID_ERR_HIP, "cid_bgzf_deflate: %s", hipGetErrorString(e)));
+    if ((rc = cid::bgzf_deflate_launch(c, c->stream, (const uint8_t *)d_text, text_bytes, (uint8_t *)d_out, (uint32_t *)d_len, d_total))) return done(rc);
+    uint64_t total = 0;
+    e = hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(member_len, d_len, n * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return done(fail(CID_ERR_HIP, "cid_bgzf_deflate: %s", hipGetErrorString(e)));
+    *members_bytes = (size_t)total;
+    if (total > members_cap)
+        return done(fail(CID_ERR_INVALID, "cid_bgzf_deflate: the members take %llu bytes, the buffer holds %zu (cid_bgzf_deflate_bound: %zu)",
+                         (unsigned long long)total, members_cap, bound));
+    e = hipMemcpy(members, d_out, (size_t)total, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return done(fail(CID_ERR_HIP, "cid_bgzf_deflate: %s", hipGetErrorString(e)));
+    return done(CID_OK);
+}
+
+}  // extern "C"

@@ -187,6 +187,43 @@ __global__ __launch_bounds__(256) void k_fq_ids(FqFile f0, uint64_t n_reads, con
         if (lane == 0) ids[o + n] = 0;
     }
 }
+// cid_fastq_filter: the bytes record r of a file takes in the output, `header\nsequence\n+\nquality\n` (the reference's format!,
+// src/read_filter.rs:89-105: the lines as lines() gives them, whatever followed the '+' dropped), or none when the read is not kept
+struct FqKeepIn {
+    FqFile f;
+    const uint8_t *keep;
+    uint64_t n;
+    __device__ uint64_t operator()(uint64_t r) const {
+        if (r >= n || !keep[r]) return 0ull;
+        uint32_t b, e;
+        uint64_t bytes = 5;
+        fq_line(f, 4 * r, b, e); bytes += e - b;
+        fq_line(f, 4 * r + 1, b, e); bytes += e - b;
+        fq_line(f, 4 * r + 3, b, e); bytes += e - b;
+        return bytes;
+    }
+};
+// one wave per kept record: its three lines (the sequence as the input has it, not quality-masked) to out[off[r] ..)
+__global__ __launch_bounds__(256) void k_fq_filter_copy(FqFile f, const uint8_t *keep, uint64_t n, const uint64_t *off, uint8_t *out) {
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (uint64_t)gridDim.x * 4) {
+        if (!keep[r]) continue;
+        uint8_t *o = out + off[r];
+        uint32_t b, e;
+        fq_line(f, 4 * r, b, e);
+        for (uint32_t j = lane; j < e - b; j += 64) o[j] = f.text[b + j];
+        o += e - b;
+        if (lane == 0) o[0] = '\n';
+        fq_line(f, 4 * r + 1, b, e);
+        for (uint32_t j = lane; j < e - b; j += 64) o[1 + j] = f.text[b + j];
+        o += 1 + (e - b);
+        if (lane == 0) { o[0] = '\n'; o[1] = '+'; o[2] = '\n'; }
+        fq_line(f, 4 * r + 3, b, e);
+        for (uint32_t j = lane; j < e - b; j += 64) o[3 + j] = f.text[b + j];
+        if (lane == 0) o[3 + (e - b)] = '\n';
+    }
+}
+
 __global__ void k_fq_read_seq0(uint64_t *read_seq0, uint64_t n_reads, uint32_t n_files) {
     const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r <= n_reads) read_seq0[r] = r * n_files;
@@ -249,8 +286,23 @@ struct cid_fastq {
         uint32_t *report = nullptr, *nk = nullptr;
         uint8_t *status = nullptr, *ids = nullptr;
         uint64_t *id_off = nullptr;
+        uint32_t *nl[2] = {nullptr, nullptr};   // the line ends of either text: the step's generation takes them when steps are kept
         std::vector<void *> scratch;   // what the kernels in flight read: back to the cache in _end
     } infl;
+    // cid_fastq_keep_steps: the step that _end has just ended stays on the device as it was cut — either file's text and line ends —
+    // until the next _end, for cid_fastq_filter.  The text the next step appends to is then a buffer of its own (the unfinished tail
+    // is copied there instead of moved to the front): one more generation of text + 4 bytes per line in HBM, ~2 x 256 MiB per file at
+    // the command line's stretch size.  Transient, inside one cid_fastq_filter call and back in the block cache when it returns: the kept
+    // text (K bytes), the bound for its members (K + 31 a member) and bgzf_deflate_launch's slots (65 312 a member): ~3 K, so up to
+    // ~0.75 GiB more when a whole 256 MiB stretch of one file is kept.
+    bool keep_steps = false;
+    struct Gen {
+        bool valid = false;
+        uint64_t n = 0;
+        uint8_t *text[2] = {nullptr, nullptr};
+        uint32_t *nl[2] = {nullptr, nullptr};
+        uint32_t len[2] = {0, 0};
+    } gen;
     hipStream_t fetch_stream = nullptr;   // results leave beside the classifier of the NEXT step, not behind it
     // CID_FASTQ_TIMING=1: host time per part of a step, printed when the reader is destroyed
     bool timing = false;
@@ -320,10 +372,17 @@ void drop_results(cid_fastq *fq) {
     fq->n_reads = fq->id_bytes = 0;
 }
 
+void drop_gen(cid_fastq *fq) {   // (no filter call outlives its return)
+    cid_ctx *c = fq->ctx;
+    for (int f = 0; f < 2; ++f) { cid::ctx_free(c, fq->gen.text[f]); cid::ctx_free(c, fq->gen.nl[f]); }
+    fq->gen = cid_fastq::Gen();
+}
+
 void drop_inflight(cid_fastq *fq) {   // (after the stream has drained)
     cid_ctx *c = fq->ctx;
     cid_fastq::Inflight &in = fq->infl;
     for (void *p : in.scratch) cid::ctx_free(c, p);
+    cid::ctx_free(c, in.nl[0]); cid::ctx_free(c, in.nl[1]);
     cid::ctx_free(c, in.report); cid::ctx_free(c, in.nk); cid::ctx_free(c, in.status); cid::ctx_free(c, in.ids); cid::ctx_free(c, in.id_off);
     in = cid_fastq::Inflight();
 }
@@ -365,6 +424,7 @@ void cid_fastq_destroy(cid_fastq *fq) {
     if (fq->fetch_stream) (void)hipStreamSynchronize(fq->fetch_stream);
     drop_results(fq);
     drop_inflight(fq);
+    drop_gen(fq);
     for (int i = 0; i < 2; ++i) {
         if (fq->f[i].members_pending) (void)hipEventDestroy(fq->f[i].members_pending);   // (the streams have drained)
         cid::ctx_free(c, fq->f[i].text);
@@ -644,7 +704,8 @@ static int fastq_begin(cid_fastq *fq, const cid_index *ix, cid_kmerset *ks, uint
         // what the kernels in flight still read stays until _end has seen the stream drain
         keep(span); keep(seq_off); keep(read_seq0); keep(id_off); keep(id_begin); keep(scan_a); keep(scan_b); keep(bases); keep(ids); keep(status); keep(report); keep(nk);
     }
-    keep(nl[0]); keep(nl[1]); keep(n_nl); keep(stats);
+    in.nl[0] = nl[0].release(); in.nl[1] = nl[1].release();
+    keep(n_nl); keep(stats);
     in.active = true;
     in.n = n; in.total_ids = total_ids;
     for (int f = 0; f < nf; ++f) {
@@ -690,13 +751,32 @@ static int fastq_end(cid_fastq *fq, uint64_t *n_reads, uint64_t *n_entries, uint
     const bool spent[2] = {in.spent[0], in.spent[1]};
     const uint64_t total_ids = in.total_ids;
     const bool classified = in.classify;
+    const bool keep_step = fq->keep_steps;
+    if (keep_step) {   // this step replaces the one kept before; the texts follow below
+        drop_gen(fq);
+        fq->gen.valid = true;
+        fq->gen.n = n;
+        for (int f = 0; f < nf; ++f) { fq->gen.nl[f] = in.nl[f]; in.nl[f] = nullptr; }
+    }
     drop_inflight(fq);
     // what is left of either text moves to the front: the next push continues behind it
     for (int f = 0; f < nf; ++f) {
         cid_fastq::File &src = fq->f[f];
         if (boundary[f] > src.len) boundary[f] = src.len;   // (the line end added at the end of the input sits AT the length)
         const size_t left = src.len - (size_t)boundary[f];
-        if (boundary[f] && left) {
+        if (keep_step && n) {   // the step's text stays where it is; the next step appends behind a copy of the unfinished tail
+            void *nb = nullptr;
+            const size_t cap = left + left / 4 + 64;
+            if (left) {
+                if ((rc = cid::ctx_alloc(c, cap, &nb))) return rc;
+                HIP_TRY(hipMemcpyAsync(nb, src.text + boundary[f], left, hipMemcpyDeviceToDevice, st));
+                HIP_TRY(hipStreamSynchronize(st));
+            }
+            fq->gen.text[f] = src.text;
+            fq->gen.len[f] = (uint32_t)src.len;
+            src.text = (uint8_t *)nb;
+            src.cap = left ? cap : 0;
+        } else if (boundary[f] && left) {
             Buf<uint8_t> tmp(c);
             if ((rc = tmp.alloc(left))) return rc;
             HIP_TRY(hipMemcpyAsync(tmp.p, src.text + boundary[f], left, hipMemcpyDeviceToDevice, st));
@@ -755,6 +835,65 @@ int cid_fastq_count_kmers(cid_fastq *fq, cid_kmerset *ks, int max_pushes, uint64
     if (cid::kmerset_ctx(ks) != fq->ctx) return fail(CID_ERR_INVALID, "the k-mer set and the reader belong to different contexts");
     uint64_t ne = 0, idb = 0;
     return fastq_step(fq, nullptr, ks, cid::kmerset_k(ks), 1, 0, max_pushes, n_reads, &ne, &idb);
+}
+
+int cid_fastq_keep_steps(cid_fastq *fq, int on) {
+    if (!fq) return fail(CID_ERR_INVALID, "null argument");
+    if (fq->infl.active) return fail(CID_ERR_STATE, "cid_fastq_keep_steps: a step is in flight");
+    fq->keep_steps = on != 0;
+    if (!on) {
+        HIP_TRY(hipSetDevice(fq->ctx->device));
+        drop_gen(fq);
+    }
+    return CID_OK;
+}
+
+int cid_fastq_filter(cid_fastq *fq, const uint8_t *keep, int file, uint8_t *members, size_t members_cap, size_t *members_bytes, size_t *n_members,
+                     uint64_t *n_kept) {
+    if (!fq || !members_bytes || !n_members || !n_kept || file < 0 || file >= fq->n_files) return fail(CID_ERR_INVALID, "bad argument");
+    *members_bytes = 0; *n_members = 0; *n_kept = 0;
+    if (!fq->keep_steps) return fail(CID_ERR_STATE, "cid_fastq_filter: the reader keeps no steps (cid_fastq_keep_steps)");
+    if (!fq->gen.valid) return fail(CID_ERR_STATE, "cid_fastq_filter: no finished step to filter");
+    const uint64_t n = fq->gen.n;
+    if (n == 0) return CID_OK;
+    if (!keep) return fail(CID_ERR_INVALID, "null argument");
+    if (!fq->gen.text[file] || !fq->gen.nl[file]) return fail(CID_ERR_STATE, "cid_fastq_filter: the step's text was not kept (its _end failed)");
+    uint64_t kept = 0;
+    for (uint64_t r = 0; r < n; ++r) kept += keep[r] != 0;
+    *n_kept = kept;
+    if (kept == 0) return CID_OK;
+    cid_ctx *c = fq->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;   // (behind a classifier launched since: the step's buffers and the block cache are this stream's)
+    int rc;
+    Buf<uint8_t> d_keep(c), d_text(c), d_out(c);
+    Buf<uint64_t> off(c), state(c), d_total(c);
+    Buf<uint32_t> d_len(c);
+    if ((rc = d_keep.alloc(n)) || (rc = off.alloc(n + 1)) || (rc = state.alloc(cid::scan_state_words(n + 1))) || (rc = d_total.alloc(2))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_keep.p, keep, n, hipMemcpyHostToDevice, st));
+    const cid::FqFile F{fq->gen.text[file], fq->gen.nl[file], nullptr, fq->gen.len[file]};
+    HIP_TRY(cid::scan_launch(cid::FqKeepIn{F, d_keep.p, n}, cid::ScanOutU64{off.p, 0ull}, n + 1, state.p, st));
+    uint64_t text_bytes = 0;
+    HIP_TRY(hipMemcpyAsync(&text_bytes, off.p + n, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const size_t nm = (size_t)((text_bytes + 65279) / 65280), bound = cid_bgzf_deflate_bound((size_t)text_bytes);
+    if ((rc = d_text.alloc(text_bytes + 16)) || (rc = d_out.alloc(bound + 16)) || (rc = d_len.alloc(nm))) return rc;
+    unsigned grid = (unsigned)((n + 3) / 4);
+    if (grid > 16384) grid = 16384;
+    hipLaunchKernelGGL(cid::k_fq_filter_copy, dim3(grid), dim3(256), 0, st, F, (const uint8_t *)d_keep.p, n, (const uint64_t *)off.p, d_text.p);
+    HIP_TRY(hipGetLastError());
+    if ((rc = cid::bgzf_deflate_launch(c, st, d_text.p, (size_t)text_bytes, d_out.p, d_len.p, d_total.p))) { (void)hipStreamSynchronize(st); return rc; }
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, d_total.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *members_bytes = (size_t)total;
+    *n_members = nm;
+    if (total > members_cap || !members)
+        return fail(CID_ERR_INVALID, "cid_fastq_filter: the members take %llu bytes, the buffer holds %zu: call again with that much room",
+                    (unsigned long long)total, members_cap);
+    HIP_TRY(hipMemcpyAsync(members, d_out.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CID_OK;
 }
 
 int cid_fastq_fetch(cid_fastq *fq, uint32_t *n_kmers, uint8_t *status, uint64_t *row_start, uint32_t *colours, uint32_t *counts, uint64_t *id_off,

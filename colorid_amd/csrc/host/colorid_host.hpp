@@ -22,6 +22,10 @@
 namespace colorid {
 
 [[noreturn]] void die(const char *fmt, ...);  // the reference panics (expect/unwrap): message + exit code 101
+// An output that is only valid once finished (--taxon's .fq.gz: whole members without the end-of-file block pass gzip -t): from
+// remove_on_die until keep_on_die, die() on any thread unlinks it before the process leaves.
+void remove_on_die(const std::string &path);
+void keep_on_die(const std::string &path);
 
 // ---------------------------------------------------------------- seq.rs / kmer.rs (query side)
 std::vector<std::string> read_fasta(const std::string &path);                                          // kmer.rs:10-45
@@ -388,6 +392,11 @@ bool device_fastq_wanted(const std::vector<std::string> &fq, size_t n_files);
 size_t device_fastq_stretch_bytes(size_t n_colors);   // text per stretch (n_colors == 0: before the index is known)
 double device_fastq_host_share();                     // share of a stretch's text inflated by the reader's host threads
 int device_fastq_host_threads(size_t n_files);
+// read_id / batch_id --taxon TAXON [--exclude] (the reference's read_filter, src/read_filter.rs, fused into the classifying pass): the
+// reads whose label — column 2 of their _reads.txt row — contains TAXON (--exclude: does not contain it) are written by the device
+// front end as PREFIX_TAXON.fq.gz / PREFIX_TAXON_R1.fq.gz + _R2 (cid_fastq_filter).  Set before the streamers run; on == false: none.
+struct TaxonFilter { bool on = false; std::string taxon; bool exclude = false; };
+void set_taxon_filter(const TaxonFilter &f);
 void per_read_stream_se(cid_ctx *, const std::vector<std::string> &fq, const Bigsi &b, size_t d, double fp_correct, size_t batch,
                         const std::string &prefix, uint8_t qual_offset, size_t start_sample);   // read_id_mt_pe.rs:835-951
 void per_read_stream_pe(cid_ctx *, const std::vector<std::string> &fq, const Bigsi &b, size_t d, double fp_correct, size_t batch,

@@ -11,6 +11,8 @@ namespace colorid {
 
 static double g_ms_gpu = 0, g_ms_poll = 0, g_ms_gpu_count = 0, g_ms_write = 0;
 static uint64_t g_entries = 0;
+static read_id_mt_pe::TaxonFilter g_taxon;   // --taxon / --exclude
+void read_id_mt_pe::set_taxon_filter(const TaxonFilter &f) { g_taxon = f; }
 static double g_ms_wait[4] = {0, 0, 0, 0};   // parser blocked by a full queue | GPU stage idle | GPU stage blocked by the poll | poll idle
 
 // probability::Binomial::mass in log space.  The poll evaluates it ~10 times per read (once per candidate colour), so the pieces that
@@ -137,6 +139,7 @@ struct Counted {   // one batch after the GPU stage: each read's non-zero (colou
     std::vector<uint8_t> status;
     std::vector<uint64_t> row_start;
     std::vector<uint32_t> colours, counts;
+    std::vector<uint8_t> keep;   // --taxon: per read, whether its label passes the filter (filled by the poll)
 };
 void count_batch(cid_ctx *ctx, const Bigsi &b, Counted &c, size_t d, size_t start_sample) {
     ReadBatch &rb = c.rb;
@@ -179,7 +182,7 @@ static inline void append_u64(std::string &o, uint64_t v) {
     do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
     while (n) o.push_back(t[--n]);
 }
-void poll_batch(const Bigsi &b, const Counted &c, double fp_correct, const std::vector<double> &fp, FILE *out,
+void poll_batch(const Bigsi &b, Counted &c, double fp_correct, const std::vector<double> &fp, FILE *out,
                 std::map<std::string, uint64_t> &tally, bool &tally_ok) {
     const size_t n = c.rb.size(), C = b.colors.size();
     const auto t_poll = Clock::now();
@@ -195,6 +198,13 @@ void poll_batch(const Bigsi &b, const Counted &c, double fp_correct, const std::
     // the tally of <prefix>_counts.txt: an accepted read counts under its label — one accession, "no_hits" or "too_short" — every other under "reject"
     for (size_t t = 0; t < nt; ++t) { text[t].clear(); acc[t].assign(C + 3, 0); }   // [C] no_hits, [C+1] too_short, [C+2] reject
     if (memchr(c.rb.id_chars.data(), '\t', c.rb.id_chars.size())) tally_ok = false;
+    // --taxon: read_filter's tab_to_map keeps a row when its second column contains the query (read_filter.rs:21)
+    const bool filter = g_taxon.on;
+    if (filter) c.keep.assign(n, 0);
+    auto passes = [&](const std::string &o, size_t label_begin) {
+        const bool hit = g_taxon.taxon.empty() || memmem(o.data() + label_begin, o.size() - label_begin, g_taxon.taxon.data(), g_taxon.taxon.size()) != nullptr;
+        return (uint8_t)(hit != g_taxon.exclude);
+    };
     auto work = [&](size_t t) {
         // (the slice's string is moved onto this thread's stack while it grows: the headers of text[0], text[1], ... share cache lines,
         // and every append writes its string's size — two slices polled side by side took twice as long as one after the other)
@@ -206,11 +216,17 @@ void poll_batch(const Bigsi &b, const Counted &c, double fp_correct, const std::
         std::vector<uint64_t> &a = acc[t];
         for (size_t r = r0; r < r1; ++r) {
             o += c.rb.id(r);
-            if (c.status[r] == 1) { o += "\ttoo_short\t0\t0\taccept\t0\n"; ++a[C + 1]; continue; }
+            if (c.status[r] == 1) {
+                if (filter) { const size_t lb = o.size() + 1; o += "\ttoo_short"; c.keep[r] = passes(o, lb); o += "\t0\t0\taccept\t0\n"; }
+                else o += "\ttoo_short\t0\t0\taccept\t0\n";
+                ++a[C + 1];
+                continue;
+            }
             const size_t e0 = (size_t)c.row_start[r], ne = (size_t)(c.row_start[r + 1] - c.row_start[r]);
             if (sig.size() < ne + 1) sig.resize(ne + 1);
             const Poll p = poll_core(c.colours.data() + e0, c.counts.data() + e0, ne, c.nk[r], C, fp, fp_correct, sig.data());
             o += '\t';
+            const size_t label_begin = o.size();
             if (p.kind == 0) { o += "no_hits"; ++a[C]; }
             else if (p.kind == 1) { o += "no_significant_hits"; ++a[C + 2]; }
             else {
@@ -219,6 +235,7 @@ void poll_batch(const Bigsi &b, const Counted &c, double fp_correct, const std::
                     if (sig[e]) { if (!first) o += ','; first = false; o += b.colors[c.colours[e0 + e]]; }
                 ++a[p.n_top == 1 ? p.first_top : C + 2];
             }
+            if (filter) c.keep[r] = passes(o, label_begin);
             o += '\t'; append_u64(o, p.best);
             o += '\t'; append_u64(o, c.nk[r]);
             o += (p.kind == 0 || (p.kind == 2 && p.n_top == 1)) ? "\taccept\t" : "\treject\t";
@@ -299,6 +316,14 @@ class BatchClassifier {
         counted_.push_back(std::move(c));
         cv_counted_.notify_one();
     }
+    // --taxon: the keep flags of the oldest polled batch not yet taken (batches are polled in the order they were handed over)
+    std::vector<uint8_t> take_keep() {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_keep_.wait(lk, [&] { return !keep_ready_.empty(); });
+        std::vector<uint8_t> k = std::move(keep_ready_.front());
+        keep_ready_.pop_front();
+        return k;
+    }
     uint64_t finish() {
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -357,6 +382,7 @@ class BatchClassifier {
             n_reads_ += c->rb.size();
             fprintf(stderr, progress_fmt_, (unsigned long long)n_reads_);
             std::lock_guard<std::mutex> lk(mu_);
+            if (g_taxon.on) { keep_ready_.push_back(std::move(c->keep)); c->keep.clear(); cv_keep_.notify_one(); }
             if (!ids_stay_) {   // (the device front end fills a Counted's ids itself: they stay with it, sized, for the next stretch)
                 c->rb.clear();
                 if (spare_.size() < 16) spare_.push_back(std::move(c->rb));
@@ -374,7 +400,8 @@ class BatchClassifier {
     FILE *out_;
     const char *progress_fmt_;
     std::mutex mu_;
-    std::condition_variable cv_work_, cv_room_, cv_counted_, cv_polled_;
+    std::condition_variable cv_work_, cv_room_, cv_counted_, cv_polled_, cv_keep_;
+    std::deque<std::vector<uint8_t>> keep_ready_;
     std::deque<ReadBatch> queue_;
     std::deque<std::unique_ptr<Counted>> counted_;
     std::vector<std::unique_ptr<Counted>> free_counted_;
@@ -454,11 +481,75 @@ namespace {
 // finishes the classifier, empties the output and runs the whole input through the host front end (which takes such reads) — an input
 // that the host path completes is never a hard failure here.
 enum FrontEnd { kFrontEndDone, kFrontEndNotMine, kFrontEndRestart };
+// --taxon: the output files of a sample, PREFIX_TAXON.fq.gz or PREFIX_TAXON_R1.fq.gz + _R2 (read_filter.rs:38, :54-57, :151-152: spaces in the
+// taxon become '_'), written a step at a time as the block-gzip members cid_fastq_filter hands back and closed with the BGZF end-of-file
+// block.  A run that cannot finish them removes them, whichever die() on whichever thread ends it (remove_on_die): a truncated file would
+// look whole to gzip -t up to its last member.
+struct FilteredOutput {
+    std::string path[2];
+    FILE *f[2] = {nullptr, nullptr};
+    size_t n_files = 0;
+    uint64_t n_kept = 0;
+    PinnedBuf buf;
+    double ms = 0;
+    void open(const std::string &prefix, size_t nf, const std::vector<std::string> &fq) {
+        std::string cleaned = g_taxon.taxon;
+        std::replace(cleaned.begin(), cleaned.end(), ' ', '_');
+        n_files = nf;
+        size_t in_bytes = 0;
+        for (size_t i = 0; i < nf; ++i) {
+            path[i] = prefix + "_" + cleaned + (nf == 2 ? (i ? "_R2" : "_R1") : "") + ".fq.gz";
+            f[i] = fopen(path[i].c_str(), "wb");
+            if (f[i]) remove_on_die(path[i]);
+            if (!f[i]) die("could not create %s!", nf == 2 ? (i ? "R2" : "R1") : "R1");
+            struct stat sb;
+            if (stat(fq[i].c_str(), &sb) == 0) in_bytes = std::max(in_bytes, (size_t)sb.st_size);
+        }
+        buf.reserve(std::min<size_t>((size_t)96 << 20, 8 * in_bytes + (64u << 10)));   // (a step's members; grown when one takes more)
+    }
+    void write_step(cid_fastq *fr, const std::vector<uint8_t> &keep) {
+        const auto t = Clock::now();
+        for (size_t i = 0; i < n_files; ++i) {
+            size_t bytes = 0, n_members = 0;
+            uint64_t kept = 0;
+            int rc = cid_fastq_filter(fr, keep.data(), (int)i, buf.p, buf.cap, &bytes, &n_members, &kept);
+            if (rc == CID_ERR_INVALID && bytes > buf.cap) {   // (the members take more room than the buffer has: once more with that much)
+                buf.reserve(bytes + bytes / 8);
+                rc = cid_fastq_filter(fr, keep.data(), (int)i, buf.p, buf.cap, &bytes, &n_members, &kept);
+            }
+            if (rc != CID_OK) die("%s", cid_last_error());
+            if (bytes && fwrite(buf.p, 1, bytes, f[i]) != bytes) die("could not write %s!", n_files == 2 ? (i ? "R2" : "R1") : "R1");
+            if (i == 0) n_kept += kept;
+        }
+        ms += ms_since(t);
+    }
+    void finish() {
+        static const unsigned char eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (size_t i = 0; i < n_files; ++i) {
+            const bool ok = fwrite(eof_block, 1, sizeof(eof_block), f[i]) == sizeof(eof_block);
+            const bool closed = fclose(f[i]) == 0;
+            f[i] = nullptr;
+            if (!ok || !closed) die("Could not close new read file");
+        }
+        for (size_t i = 0; i < n_files; ++i) keep_on_die(path[i]);
+        if (g_taxon.exclude)   // (read_filter.rs:119-129: either line counts the reads WRITTEN)
+            fprintf(stderr, "Excluded %llu read pairs  with classification containing '%s' from output files\n", (unsigned long long)n_kept, g_taxon.taxon.c_str());
+        else
+            fprintf(stderr, "Wrote %llu read-pairs with classification containing '%s' to output files\n", (unsigned long long)n_kept, g_taxon.taxon.c_str());
+        if (g_timing) fprintf(stderr, "timing: --taxon: %.0f ms in cid_fastq_filter (waiting for the classifier in flight included) and writing the members\n", ms);
+    }
+};
+
 FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &fq, size_t n_files, const Bigsi &b, size_t d, size_t start_sample,
-                             uint8_t qual_offset, BatchClassifier &classifier) {
+                             uint8_t qual_offset, BatchClassifier &classifier, const std::string &prefix) {
     const auto t_enter = Clock::now();
     cid_fastq *fr = nullptr;
     CID_TRY(cid_fastq_create(ctx, (int)n_files, qual_offset, &fr));
+    FilteredOutput filtered;
+    if (g_taxon.on) {
+        CID_TRY(cid_fastq_keep_steps(fr, 1));
+        filtered.open(prefix, n_files, fq);
+    }
     classifier.ids_stay_with_counted(true);
     const size_t target = read_id_mt_pe::device_fastq_stretch_bytes(b.colors.size());
     std::unique_ptr<BgzfMemberReader> rd[2];
@@ -518,6 +609,9 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
             ms_classify += ms_since(tc);
             for (size_t i = 0; i < n_files; ++i) if (pending[i]) --pending[i];
             if (rc == CID_ERR_UNSUPPORTED) {   // (tests inject one through the library: cid_ctx_tune fastq_refuse_at_step / CID_FASTQ_REFUSE_AT_STEP)
+                if (g_taxon.on)   // the host front end writes no filtered reads; die() leaves no partial .fq.gz behind
+                    die("%s — --taxon writes the kept reads on the device front end only, which gave way; the partial .fq.gz files were removed "
+                        "(run read_id without --taxon, or the reference's read_filter)", cid_last_error());
                 fprintf(stderr, "note: %s — %s\n", cid_last_error(), first ? "using the host front end" : "starting over with the host front end");
                 cid_fastq_destroy(fr);
                 classifier.ids_stay_with_counted(false);
@@ -527,6 +621,7 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
             first = false;
             ++n_steps;
         }
+        const bool filter_step = g_taxon.on && have && have_n;
         if (have && have_n) {
             const auto tb = Clock::now();
             std::unique_ptr<Counted> c = classifier.take_counted();
@@ -548,6 +643,8 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
         have = false;
         for (size_t i = 0; i < n_files; ++i)   // the stretches after this one: inflated while this one is classified
             while (more[i] && pending[i] < ahead + 1) push_next(i);
+        // --taxon: the step just handed to the poll stays on the device until the next _end; its labels come back from the poll
+        if (filter_step) filtered.write_step(fr, classifier.take_keep());
         if (!begin) break;
         const auto tc = Clock::now();
         const int rc = cid_fastq_classify_end(fr, &have_n, &have_ne, &have_idb);
@@ -559,6 +656,7 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
         t_gpu = Clock::now();
     }
     cid_fastq_destroy(fr);
+    if (g_taxon.on) filtered.finish();
     if (g_timing)
         fprintf(stderr, "timing: device front end: waiting for the file reader %.0f ms, push (H2D of the members) %.0f ms, classify %.0f ms, fetch %.0f ms "
                 "(+ %.0f ms sizing its buffers), handing the rows to the poll %.0f ms; %.0f ms until the first stretch was pushed, %.0f ms in all\n",
@@ -587,12 +685,13 @@ void read_id_mt_pe::per_read_stream_se(cid_ctx *ctx, const std::vector<std::stri
     if (!out) die("could not create outfile!");
     ReadBatch rb;
     const bool on_device = device_fastq_wanted(fq, 1);
+    if (g_taxon.on && !on_device) die("--taxon needs the device front end (block-gzip input on one GPU; recompress with bgzip)");
     if (on_device && !cli_env("COLORID_POLL_THREADS"))
         g_poll_threads = std::max(g_poll_threads, read_id_mt_pe::device_fastq_host_share() > 0.0 ? std::min(6, cpu_budget() * 3 / 8) : std::min(12, cpu_budget() * 5 / 8));   // no packing threads beside them: a stretch's poll on 4 threads takes 18 ms, the GPU side 13
     auto make_classifier = [&] { return std::unique_ptr<BatchClassifier>(new BatchClassifier(ctx, b, d, fp_correct, start_sample, fp, out, "%llu read pairs classified\r")); };
     std::unique_ptr<BatchClassifier> classifier = make_classifier();
     if (g_timing) fprintf(stderr, "timing: %.0f ms of set-up before the first read\n", ms_since(t0));
-    FrontEnd fe = on_device ? classify_bgzf_on_device(ctx, fq, 1, b, d, start_sample, qual_offset, *classifier) : kFrontEndNotMine;
+    FrontEnd fe = on_device ? classify_bgzf_on_device(ctx, fq, 1, b, d, start_sample, qual_offset, *classifier, prefix) : kFrontEndNotMine;
     if (fe == kFrontEndRestart) {
         classifier->finish();
         empty_output(out, prefix);
@@ -622,11 +721,12 @@ void read_id_mt_pe::per_read_stream_pe(cid_ctx *ctx, const std::vector<std::stri
     if (!out) die("could not create outfile!");
     ReadBatch rb;
     const bool on_device = device_fastq_wanted(fq, 2);
+    if (g_taxon.on && !on_device) die("--taxon needs the device front end (block-gzip input on one GPU; recompress with bgzip)");
     if (on_device && !cli_env("COLORID_POLL_THREADS"))
         g_poll_threads = std::max(g_poll_threads, read_id_mt_pe::device_fastq_host_share() > 0.0 ? std::min(6, cpu_budget() * 3 / 8) : std::min(12, cpu_budget() * 5 / 8));
     auto make_classifier = [&] { return std::unique_ptr<BatchClassifier>(new BatchClassifier(ctx, b, d, fp_correct, start_sample, fp, out, "%llu read pairs classified\r")); };
     std::unique_ptr<BatchClassifier> classifier = make_classifier();
-    FrontEnd fe = on_device ? classify_bgzf_on_device(ctx, fq, 2, b, d, start_sample, qual_offset, *classifier) : kFrontEndNotMine;
+    FrontEnd fe = on_device ? classify_bgzf_on_device(ctx, fq, 2, b, d, start_sample, qual_offset, *classifier, prefix) : kFrontEndNotMine;
     if (fe == kFrontEndRestart) {
         classifier->finish();
         empty_output(out, prefix);

@@ -8,8 +8,10 @@
 #include <dlfcn.h>
 #include <zlib.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
@@ -27,6 +29,20 @@
 
 namespace colorid {
 
+namespace {
+std::mutex g_unfinished_mu;
+std::vector<std::string> &unfinished() { static auto *v = new std::vector<std::string>; return *v; }   // (never destroyed: die() may run during exit)
+}  // namespace
+void remove_on_die(const std::string &path) {
+    std::lock_guard<std::mutex> lk(g_unfinished_mu);
+    unfinished().push_back(path);
+}
+void keep_on_die(const std::string &path) {
+    std::lock_guard<std::mutex> lk(g_unfinished_mu);
+    auto &v = unfinished();
+    v.erase(std::remove(v.begin(), v.end(), path), v.end());
+}
+
 void die(const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -34,6 +50,15 @@ void die(const char *fmt, ...) {
     vfprintf(stderr, fmt, ap);
     fprintf(stderr, "\n");
     va_end(ap);
+    fflush(nullptr);
+    {
+        std::lock_guard<std::mutex> lk(g_unfinished_mu);
+        for (const std::string &path : unfinished()) {
+            struct stat sb;
+            const long long had = stat(path.c_str(), &sb) == 0 ? (long long)sb.st_size : 0;
+            if (::remove(path.c_str()) == 0) fprintf(stderr, "colorid: removed the unfinished %s (%lld bytes had been written)\n", path.c_str(), had);
+        }
+    }
     // a Rust panic exits with 101.  Reader / classifier threads may be running (and may be the caller): flush what was written
     // and leave without running static destructors under them.
     fflush(nullptr);

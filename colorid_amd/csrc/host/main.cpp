@@ -661,6 +661,27 @@ bool wants_device_front_end(const Args &a, const std::vector<std::string> &fq) {
     return ends_with(fq[0], ".gz") && one_gpu_run(a) && read_id_mt_pe::device_fastq_wanted(fq, fq.size() > 1 ? 2 : 1);
 }
 
+// --taxon TAXON [--exclude] (read_id, batch_id): the reference's read_filter fused into the classifying pass — the kept reads are cut and
+// compressed on the device (cid_fastq_filter), so only block-gzip input on one GPU is served; everything else is refused here, before the
+// GPU context is made.
+read_id_mt_pe::TaxonFilter taxon_filter(const Args &a) {
+    read_id_mt_pe::TaxonFilter f;
+    const bool exclude = a.flags.count("exclude") != 0;
+    if (exclude && !a.has("taxon")) die("error: --exclude needs --taxon TAXON (the classification to leave out)");
+    if (!a.has("taxon")) return f;
+    f.on = true; f.taxon = a.one("taxon"); f.exclude = exclude;
+    return f;
+}
+void require_filter_route(const Args &a, const std::vector<std::string> &fq) {
+    if (wants_device_front_end(a, fq)) return;
+    const char *why = !one_gpu_run(a) ? "it runs on one GPU only (no --gpus / --devices / --placement)"
+                      : (cli_env("COLORID_DEVICE_FASTQ") && atoi(cli_env("COLORID_DEVICE_FASTQ")) == 0) ? "COLORID_DEVICE_FASTQ=0 turns the device front end off"
+                      : !ends_with(fq[0], ".gz") ? "the input is not compressed"
+                      : "the input is a single gzip stream, not block-gzip";
+    die("error: --taxon writes the kept reads in the classifying pass on the GPU, which takes block-gzip (BGZF) fastq input: %s; "
+        "compress the reads with bgzip (%s)", why, fq[0].c_str());
+}
+
 // Start reading a sample's files before whoever classifies them asks: gzip decoding (or, for the device front end, reading the
 // compressed members: a stretch or two, the reader's queue) then runs beside GPU start-up and the index load — measured against
 // starting it after the context exists, the classification phase of 1 M reads ends 130 ms earlier — or, in batch_id, beside the
@@ -693,12 +714,16 @@ int cmd_read_id(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, with_common({{'b', "bigsi", true, false}, {'q', "query", true, true}, {'c', "batch", true, false},
                                                      {'t', "threads", true, false}, {'n', "prefix", true, false}, {'d', "down_sample", true, false},
                                                      {'H', "high_mem_load", false, false}, {'p', "fp_correct", true, false},
-                                                     {'Q', "quality", true, false}, {'B', "bitvector_sample", true, false}}));
+                                                     {'Q', "quality", true, false}, {'B', "bitvector_sample", true, false},
+                                                     {0, "taxon", true, false}, {0, "exclude", false, false}}));
     for (const char *req : {"bigsi", "query", "prefix"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const std::vector<std::string> fq = a.values.at("query");
     const ClassifyFlags flags = classify_flags(a);
     const std::string prefix = a.one("prefix");
+    const read_id_mt_pe::TaxonFilter filter = taxon_filter(a);
+    if (filter.on) require_filter_route(a, fq);
+    read_id_mt_pe::set_taxon_filter(filter);
     if (cli_env("COLORID_GPU_INFLATE") && atoi(cli_env("COLORID_GPU_INFLATE")) > 0) LineReader::inflate_on_gpu(num_or<int>(a, "device", 0));
     const bool device_front_end = wants_device_front_end(a, fq);
     read_ahead(fq, device_front_end);
@@ -727,13 +752,17 @@ int cmd_batch_id(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, with_common({{'b', "bigsi", true, false}, {'q', "query", true, false}, {'T', "tag", true, false},
                                                      {'c', "batch", true, false}, {'t', "threads", true, false}, {'d', "down_sample", true, false},
                                                      {'H', "high_mem_load", false, false}, {'p', "fp_correct", true, false},
-                                                     {'Q', "quality", true, false}, {'B', "bitvector_sample", true, false}}));
+                                                     {'Q', "quality", true, false}, {'B', "bitvector_sample", true, false},
+                                                     {0, "taxon", true, false}, {0, "exclude", false, false}}));
     for (const char *req : {"bigsi", "query", "tag"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const ClassifyFlags flags = classify_flags(a);
     const std::string tag = a.one("tag");
     const auto sheet = tab_to_map(a.one("query"));
     std::vector<std::pair<std::string, std::vector<std::string>>> samples(sheet.begin(), sheet.end());
+    const read_id_mt_pe::TaxonFilter filter = taxon_filter(a);
+    if (filter.on) for (const auto &sm : samples) require_filter_route(a, sm.second);
+    read_id_mt_pe::set_taxon_filter(filter);
     if (cli_env("COLORID_GPU_INFLATE") && atoi(cli_env("COLORID_GPU_INFLATE")) > 0) LineReader::inflate_on_gpu(num_or<int>(a, "device", 0));
     std::vector<char> on_device(samples.size(), 0);
     bool any_on_device = false;

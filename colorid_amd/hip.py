@@ -4,7 +4,7 @@ import weakref
 
 import numpy as np
 
-from ._lib import check, load_library, vp
+from ._lib import CID_ERR_INVALID, check, load_library, vp
 
 NOT_UNIQUE = 0xFFFFFFFF
 
@@ -686,6 +686,18 @@ class GroupKmerSet:
                 self.g._ksets.remove(self)
 
 
+def bgzf_deflate(ctx, text: bytes):
+    """cid_bgzf_deflate: `text` as block-gzip members written on the GPU -> (members [bytes], member_len [uint32 per member])"""
+    lib = ctx.lib
+    cap = lib.cid_bgzf_deflate_bound(len(text))
+    buf = np.frombuffer(text, np.uint8) if len(text) else np.zeros(1, np.uint8)
+    out = np.zeros(max(cap, 1), np.uint8)
+    ln = np.zeros(max((len(text) + 65279) // 65280, 1), np.uint32)
+    nb, nm = C.c_size_t(0), C.c_size_t(0)
+    check(lib.cid_bgzf_deflate(ctx.h, _p(buf), len(text), _p(out), cap, C.byref(nb), _p(ln), C.byref(nm)))
+    return out[:nb.value].tobytes(), ln[:nm.value].copy()
+
+
 class FastqReader:
     """cid_fastq: FASTQ text or block-gzip members -> records -> quality-masked reads -> classification counts, all on the device."""
 
@@ -741,6 +753,23 @@ class FastqReader:
         raw = ids.tobytes()
         names = [raw[int(io[r]):int(io[r + 1]) - 1] for r in range(n.value)]
         return names, nk, st, rs, col, cnt
+
+    def keep_steps(self, on=True):
+        """from the next classify_end on, an ended step stays on the device until the next one ends (what filter() reads)"""
+        check(self.lib.cid_fastq_keep_steps(self.h, 1 if on else 0))
+
+    def filter(self, keep, file=0):
+        """the kept records (keep[r] != 0) of file `file` of the last ended step, `header\\nsequence\\n+\\nquality\\n` each, as
+        block-gzip members -> (members [bytes], n_members, n_kept)"""
+        keep = np.ascontiguousarray(keep, np.uint8)
+        nb, nm, nk = C.c_size_t(0), C.c_size_t(0), C.c_uint64(0)
+        out = np.zeros(1 << 16, np.uint8)
+        rc = self.lib.cid_fastq_filter(self.h, _p(keep), file, _p(out), out.size, C.byref(nb), C.byref(nm), C.byref(nk))
+        if rc == CID_ERR_INVALID and nb.value > out.size:   # with the size the members take: the same call with that much room
+            out = np.zeros(nb.value, np.uint8)
+            rc = self.lib.cid_fastq_filter(self.h, _p(keep), file, _p(out), out.size, C.byref(nb), C.byref(nm), C.byref(nk))
+        check(rc)
+        return out[:nb.value].tobytes(), nm.value, nk.value
 
     def count_kmers(self, kmerset, max_pushes=0):
         """every complete record held adds its reads' k-mers to `kmerset` (search's fastq producers); -> reads taken"""

@@ -505,6 +505,22 @@ CID_CORE int cid_bgzf_inflate(cid_ctx *, const uint8_t *members, size_t n_bytes,
 int cid_bgzf_inflate_start(cid_ctx *, const uint8_t *members, size_t n_bytes, const uint32_t *member_off, const uint32_t *member_len,
                            const uint32_t *text_off, const uint32_t *text_len, size_t n_members, size_t text_bytes);
 int cid_bgzf_inflate_finish(cid_ctx *, uint8_t *text, size_t text_bytes, size_t *bad_member);
+/* ---- output side: block-gzip members WRITTEN on the GPU, the mirror of cid_bgzf_inflate (read_id --taxon: the kept reads leave the device
+ *      compressed; the reference's read_filter gzips them on one thread, src/read_filter.rs:54-59).  `text` is cut every 65 280 bytes
+ *      (htslib's block size); each piece becomes one whole member — gzip header with the "BC" field (BSIZE = its length - 1), ONE DEFLATE
+ *      block, CRC-32, ISIZE — and the members lie back to back in `members`; member_len[i] is member i's length,
+ *      *n_members = ceil(text_bytes / 65280) (0 for an empty text: the 28-byte BGZF end-of-file block is the file writer's business).
+ *      The block is dynamic Huffman over literals and end-of-block (no LZ77 matches), or stored when that would not be smaller: no
+ *      member is longer than its text + 31 bytes, and cid_bgzf_deflate_bound(text_bytes) bytes of room are never refused.  The bytes
+ *      are a function of the text alone.  CID_ERR_INVALID: a null argument, or (host form) members that take more than members_cap —
+ *      *members_bytes then says how much.
+ *      _dev: text, members, member_len [n] and members_bytes (one u64) in device memory, text 16-byte aligned, members_cap at least the
+ *      bound; queued on the ctx stream. ---- */
+size_t cid_bgzf_deflate_bound(size_t text_bytes);
+int cid_bgzf_deflate(cid_ctx *, const uint8_t *text, size_t text_bytes, uint8_t *members, size_t members_cap, size_t *members_bytes,
+                     uint32_t *member_len, size_t *n_members);
+int cid_bgzf_deflate_dev(cid_ctx *, const uint8_t *text, size_t text_bytes, uint8_t *members, size_t members_cap, uint64_t *members_bytes,
+                         uint32_t *member_len, size_t *n_members);
 /* ---- the FASTQ front end of read_id on the device: what the reference does per read before its search — inflate
  *      (src/read_id_mt_pe.rs:848-856), take the lines four at a time (:862-879 / pairs :927-975: header, sequence, '+', quality; lines()
  *      strips "\n" and "\r\n"; an unterminated last line counts), seq::qual_mask (src/seq.rs:36-56) and the (id, [seq(, mate)]) batch
@@ -558,6 +574,24 @@ CID_CORE int cid_fastq_classify_end(cid_fastq *, uint64_t *n_reads, uint64_t *n_
 CID_CORE int cid_fastq_count_kmers(cid_fastq *, cid_kmerset *set, int max_pushes, uint64_t *n_reads);
 CID_CORE int cid_fastq_fetch(cid_fastq *, uint32_t *n_kmers, uint8_t *status, uint64_t *row_start, uint32_t *colours, uint32_t *counts, uint64_t *id_off,
                     char *ids);
+/* read_id --taxon: the kept records of the step that the last _end ended, as block-gzip members (cid_bgzf_deflate's), written in the
+ * classifying pass — the reference reads and inflates the input a second time (read_filter, src/read_filter.rs).
+ *   keep_steps   on: from the next _end on, a step's text and line ends stay on the device until the NEXT _end (like its results for
+ *                fetch), also across the _begin of the step after it.  Costs one more generation of text + 4 bytes per line in device
+ *                memory per file (the next step appends to a buffer of its own).  Off (the default): nothing is kept, today's path.
+ *                On top of that, while it runs, a filter call takes from the ctx's block cache, for K bytes of kept text: K for the
+ *                kept text, K + 31 per member for the gathered members and 65 312 per member (K / 65 280 members) for the slots
+ *                the members are coded into, ~3 K in all plus ~10 bytes per read of the step; given back before it returns.
+ *   filter       keep[n_reads] (0 / 1, the step's reads in order); for every kept read the record of file `file` is written as
+ *                `header\nsequence\n+\nquality\n` (read_filter.rs:89-105: the lines as lines() gives them — "\r\n" stripped, an
+ *                unterminated last line counts —, the sequence as the input has it, not quality-masked, whatever followed the '+'
+ *                dropped), in input order; the text goes through cid_bgzf_deflate_dev and the members come back in `members`.
+ *                For pairs: once per file with the same flags.  Runs on the ctx stream (behind a classifier launched since).
+ *                CID_ERR_STATE: keep_steps is off or no step has ended yet; CID_ERR_INVALID: members_cap too small — *members_bytes
+ *                then says how much room the same call needs. */
+int cid_fastq_keep_steps(cid_fastq *, int on);
+int cid_fastq_filter(cid_fastq *, const uint8_t *keep, int file, uint8_t *members, size_t members_cap, size_t *members_bytes, size_t *n_members,
+                     uint64_t *n_kept);
 CID_CORE void cid_fastq_destroy(cid_fastq *);
 #define CID_WARM_READID 1u
 #define CID_WARM_SEARCH 2u

@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""Evidence for `read_id --taxon` on 1 M x 150 bp reads with Illumina-style headers and 41 skewed quality letters:
+
+  (a) the compressor alone: tools/exp_deflate.py (HIP events around cid_bgzf_deflate_dev, the members' size, zlib level 6 over the same
+      65 280-byte pieces on 16 host threads) and, from a run of its own under rocprofv3 --kernel-trace --stats, the time per kernel;
+  (b) the command line: an index of 16 random 1 Mb genomes (m = 5 M, n = 4, k = 31), the reads drawn from them with 1 % errors and
+      written as block gzip; `read_id` without the flags, `read_id --taxon genomeA` (8 of the 16 genomes: about half the reads kept) and
+      `read_id` without the flags from PARENT_BIN (the parent commit's binary), alternating, REPS times each after one warm-up: the
+      whole-process wall clock and the classification phase (COLORID_TIMING), then one traced --taxon run for the filter's kernels.
+
+Run on the GPU box:   python3 tools/profile_filter.py OUT_DIR [PARENT_BIN]
+writes OUT_DIR/filter_summary.md, filter_deflate.json, filter_deflate_kernel_stats.csv, filter_cli_kernel_stats.csv"""
+import json
+import os
+import pathlib
+import re
+import shutil
+import struct
+import sys
+import tempfile
+import zlib
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+BIN = os.path.join(ROOT, "colorid_amd", "bin", "colorid")
+REPS = 3
+G, LG, R = 16, 1_000_000, int(os.environ.get("EXP_READS", 1_000_000))
+
+from profile_merge import kernel_stats, run   # noqa: E402
+
+
+def make_sample(work):
+    rng = np.random.default_rng(1)
+    acgt = np.frombuffer(b"ACGT", np.uint8)
+    genomes = []
+    with open(work / "refs.tsv", "w") as tsv:
+        for g in range(G):
+            s = acgt[rng.integers(0, 4, LG)]
+            genomes.append(s)
+            body = s.tobytes()
+            (work / f"g{g:02d}.fasta").write_bytes(f">g{g}\n".encode() + b"\n".join(body[i:i + 80] for i in range(0, LG, 80)) + b"\n")
+            tsv.write(f"genome{'A' if g < G // 2 else 'B'}{g:02d}\t{work}/g{g:02d}.fasta\n")
+    src, pos = rng.integers(0, G, R), rng.integers(0, LG - 150, R)
+    reads = np.stack([genomes[src[i]][pos[i]:pos[i] + 150] for i in range(R)])
+    err = rng.random(reads.shape) < 0.01
+    reads[err] = acgt[rng.integers(0, 4, int(err.sum()))]
+    p = np.linspace(1, 8, 41)
+    qual = rng.choice(np.arange(33, 74, dtype=np.uint8), size=(R, 150), p=p / p.sum())
+    text = b"".join(b"@A00123:45:HXXXXXXXX:1:%d:%d:%d 1:N:0:ACGTACGT\n" % (1101 + i // 5000, 1000 + (i * 37) % 30000, 1000 + (i * 101) % 30000) +
+                    reads[i].tobytes() + b"\n+\n" + qual[i].tobytes() + b"\n" for i in range(R))
+    with open(work / "reads.fastq.gz", "wb") as f:
+        for i in range(0, len(text), 65280):
+            c = text[i:i + 65280]
+            co = zlib.compressobj(1, zlib.DEFLATED, -15)
+            body = co.compress(c) + co.flush()
+            f.write(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff" + struct.pack("<H", 6) + b"BC" + struct.pack("<HH", 2, 12 + 6 + len(body) + 8 - 1))
+            f.write(body + struct.pack("<II", zlib.crc32(c) & 0xFFFFFFFF, len(c)))
+        f.write(bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0]))
+    run([BIN, "build", "-s", "5000000", "-n", "4", "-k", "31", "-b", str(work / "idx"), "-r", str(work / "refs.tsv")])
+    return len(text)
+
+
+def phases(stderr):
+    return [ln.split("\r")[-1] for ln in stderr.splitlines() if "timing:" in ln or "Wrote " in ln]
+
+
+def classification_ms(stderr):
+    for name, ms in re.findall(r"timing: ([A-Za-z_ ,]+?) (\d+) ms", stderr.replace("\r", "\n")):
+        if "lassif" in name:
+            return int(ms)
+    return None
+
+
+def rng_of(xs, unit, fmt="{:.2f}"):
+    xs = [x for x in xs if x is not None]
+    return (fmt.format(min(xs)) + "–" + fmt.format(max(xs)) + " " + unit + " (" + ", ".join(fmt.format(x) for x in xs) + ")") if xs else "n/a"
+
+
+def main():
+    out_dir = os.path.abspath(sys.argv[1])
+    parent_bin = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else None
+    os.makedirs(out_dir, exist_ok=True)
+    lines = [f"# `read_id --taxon`: the device compressor and the fused filter, {R:,} x 150 bp reads", ""]
+    # ---- (a) the compressor alone
+    exp = [sys.executable, os.path.join(ROOT, "tools", "exp_deflate.py")]
+    p, _ = run(exp, env=dict(os.environ, EXP_READS=str(R)), limit=900)
+    print(p.stdout.strip().splitlines()[-1], file=sys.stderr, flush=True)
+    dj = json.loads(p.stdout.strip().splitlines()[-1])
+    with open(os.path.join(out_dir, "filter_deflate.json"), "w") as fh:
+        fh.write(json.dumps(dj) + "\n")
+    os.environ["EXP_READS"] = str(R)
+    stats = kernel_stats(out_dir, "filter_deflate", exp)
+    later = dj["device_ms_later"]
+    lines += ["## (a) `cid_bgzf_deflate_dev` on the reads' text, against zlib level 6", "",
+              f"text {dj['text_MB']} MB in {dj['members']} members; HIP events around the call, text and members resident: first call "
+              f"{dj['device_ms_first']} ms, then {min(later)}–{max(later)} ms ({dj['text_MB'] / 1e3 / (min(later) / 1e3):.0f} GB/s of text at the best); "
+              f"output {dj['device_out_MB']} MB = {dj['device_ratio']} x.",
+              f"zlib level 6 over the same pieces on {dj['zlib6_threads']} host threads: {dj['zlib6_ms']} ms, {dj['zlib6_out_MB']} MB = {dj['zlib6_ratio']} x.",
+              "", "Per kernel (one `rocprofv3 --kernel-trace --stats` run of the same script: six calls):", "",
+              "| kernel | calls | total ms | ms per call |", "|---|---|---|---|"]
+    for name, r in stats.items():
+        if any(k in name for k in ("k_bgzf_deflate", "k_bgzf_gather", "scan")):
+            n, t = int(r["Calls"]), float(r["TotalDurationNs"]) / 1e6
+            lines.append(f"| `{name.split('(')[0][-60:]}` | {n} | {t:.2f} | {t / n:.3f} |")
+    # ---- (b) the command line
+    work = pathlib.Path(tempfile.mkdtemp(prefix="filter_prof_"))
+    try:
+        text_bytes = make_sample(work)
+        print("sample and index made", file=sys.stderr, flush=True)
+        env = dict(os.environ, COLORID_TIMING="1")
+        q = ["-b", str(work / "idx.bxi"), "-q", str(work / "reads.fastq.gz")]
+        cmds = {"plain": [BIN, "read_id", *q, "-n", str(work / "plain")],
+                "taxon": [BIN, "read_id", *q, "-n", str(work / "taxon"), "--taxon", "genomeA"]}
+        if parent_bin:
+            cmds["parent"] = [parent_bin, "read_id", *q, "-n", str(work / "parent")]
+        run(cmds["plain"], env=env)                              # a warm-up nobody counts: index and reads come into the page cache
+        walls, cls, first = {k: [] for k in cmds}, {k: [] for k in cmds}, {}
+        for rep in range(REPS):                                  # alternating, so a drift of the box hits them alike
+            for tag, cmd in cmds.items():
+                p, wall = run(cmd, env=env)
+                walls[tag].append(wall)
+                print(f"{tag}: {wall:.2f} s", file=sys.stderr, flush=True)
+                cls[tag].append(classification_ms(p.stderr))
+                first.setdefault(tag, phases(p.stderr))
+        same = all(open(work / f"taxon_{s}.txt", "rb").read() == open(work / f"plain_{s}.txt", "rb").read() for s in ("reads", "counts"))
+        out_gz = os.path.getsize(work / "taxon_genomeA.fq.gz")
+        cli_stats = kernel_stats(out_dir, "filter_cli", cmds["taxon"])
+        label = {"plain": "`read_id`", "taxon": "`read_id --taxon genomeA`", "parent": "`read_id`, the parent commit's binary"}
+        lines += ["", "## (b) the command line", "",
+                  f"index: {G} genomes of {LG:,} bases, m = 5 M, n = 4, k = 31; reads: {text_bytes / 1e6:.1f} MB of FASTQ text as block gzip "
+                  f"({os.path.getsize(work / 'reads.fastq.gz') / 1e6:.1f} MB); `--taxon genomeA` names {G // 2} of the {G} accessions; its output: "
+                  f"{out_gz / 1e6:.1f} MB; `_reads.txt` and `_counts.txt` equal to the run without the flags: {same}", "",
+                  f"| command | process wall, {REPS} alternating runs | classification phase (COLORID_TIMING) |", "|---|---|---|"]
+        for tag in cmds:
+            lines.append(f"| {label[tag]} | {rng_of(walls[tag], 's')} | {rng_of(cls[tag], 'ms', '{:.0f}')} |")
+        lines += ["", "Kernels of one traced `--taxon` run that the flags add:", "", "| kernel | calls | total ms |", "|---|---|---|"]
+        for name, r in cli_stats.items():
+            if any(k in name for k in ("k_bgzf_deflate", "k_bgzf_gather", "k_fq_filter")):
+                lines.append(f"| `{name.split('(')[0][-60:]}` | {int(r['Calls'])} | {float(r['TotalDurationNs']) / 1e6:.2f} |")
+        for tag in cmds:
+            lines += ["", f"{label[tag]}, first counted run:", "", "```", *first[tag], "```"]
+    finally:
+        shutil.rmtree(work, ignore_errors=True)
+    with open(os.path.join(out_dir, "filter_summary.md"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+if __name__ == "__main__":
+    main()
