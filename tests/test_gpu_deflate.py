@@ -2,7 +2,6 @@
 parallel; stored when that is not smaller) against zlib — zlib.decompressobj(31) over the members checks the codes, the CRC-32 and the
 ISIZE of every one; the framing ("BC", BSIZE) is checked here, and cid_bgzf_inflate reads the members back."""
 import ctypes as C
-import heapq
 import struct
 import zlib
 
@@ -10,22 +9,10 @@ import numpy as np
 import pytest
 
 from colorid_amd._lib import CID_ERR_INVALID
+from deflate_props import BLOCK, gunzip_members, illumina_fastq, literal_code_lengths, split_members, unlimited_huffman_depth
 from test_gpu_inflate import inflate
 
 pytestmark = pytest.mark.gpu
-
-BLOCK = 65280
-
-
-def illumina_fastq(rng, n_bytes):
-    out, size, i = [], 0, 0
-    quals = np.frombuffer(bytes(range(33, 74)), np.uint8)                       # 41 quality letters
-    while size < n_bytes:
-        rec = (b"@A00123:45:HXXXXXXXX:1:%d:%d:%d 1:N:0:ACGTACGT\n" % (1101 + i // 5000, 1000 + (i * 37) % 30000, 1000 + (i * 101) % 30000) +
-               bytes(rng.choice(list(b"ACGT"), size=150).astype(np.uint8)) + b"\n+\n" +
-               bytes(rng.choice(quals, size=150, p=np.linspace(1, 8, 41) / np.linspace(1, 8, 41).sum())) + b"\n")
-        out.append(rec); size += len(rec); i += 1
-    return b"".join(out)[:n_bytes]
 
 
 def fibonacci_text(rng):
@@ -63,80 +50,6 @@ def _texts():
 TEXTS = _texts()
 
 
-def unlimited_huffman_depth(piece):
-    """the deepest leaf of the plain Huffman tree over a piece's literals and the end-of-block"""
-    heap = [(c, 0) for c in np.bincount(np.frombuffer(piece, np.uint8), minlength=256).tolist() + [1] if c]
-    heapq.heapify(heap)
-    while len(heap) > 1:
-        (a, da), (b, db) = heapq.heappop(heap), heapq.heappop(heap)
-        heapq.heappush(heap, (a + b, max(da, db) + 1))
-    return heap[0][1]
-
-
-def literal_code_lengths(member):
-    """the literal/length code lengths a dynamic-Huffman member declares (RFC 1951 3.2.7)"""
-    bits = np.unpackbits(np.frombuffer(member[18:], np.uint8), bitorder="little")
-    pos = 0
-
-    def take(n):
-        nonlocal pos
-        v = int(sum(int(b) << i for i, b in enumerate(bits[pos:pos + n])))
-        pos += n
-        return v
-
-    assert (take(1), take(2)) == (1, 2)
-    hlit, _, hclen = take(5) + 257, take(5) + 1, take(4) + 4
-    cl = [0] * 19
-    for sym in [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15][:hclen]:
-        cl[sym] = take(3)
-    codes, code = {}, 0                                                          # canonical: (length, code) -> symbol
-    for ln in range(1, 8):
-        for sym in range(19):
-            if cl[sym] == ln:
-                codes[(ln, code)] = sym
-                code += 1
-        code <<= 1
-    out = []
-    while len(out) < hlit:
-        ln, code = 0, 0
-        while (ln, code) not in codes or ln == 0:
-            code = (code << 1) | take(1)
-            ln += 1
-        sym = codes[(ln, code)]
-        if sym < 16:
-            out.append(sym)
-        elif sym == 16:
-            out += [out[-1]] * (3 + take(2))
-        else:
-            out += [0] * ((3 + take(3)) if sym == 17 else (11 + take(7)))
-    return out[:hlit]
-
-
-def split_members(blob):
-    """the members of a BGZF byte string by their BSIZE; every one must carry the "BC" field"""
-    out, pos = [], 0
-    while pos < len(blob):
-        assert blob[pos:pos + 4] == b"\x1f\x8b\x08\x04", "gzip header with FEXTRA"
-        xlen = struct.unpack_from("<H", blob, pos + 10)[0]
-        assert xlen == 6 and blob[pos + 12:pos + 16] == b"BC\x02\x00"
-        bsize = struct.unpack_from("<H", blob, pos + 16)[0]
-        out.append(blob[pos:pos + bsize + 1])
-        pos += bsize + 1
-    assert pos == len(blob)
-    return out
-
-
-def gunzip_members(blob):
-    """zlib over one member after the other: Huffman codes, CRC-32 and ISIZE checked by zlib"""
-    out, rest = [], blob
-    while rest:
-        d = zlib.decompressobj(31)
-        out.append(d.decompress(rest))
-        assert d.eof
-        rest = d.unused_data
-    return out
-
-
 @pytest.mark.parametrize("name", list(TEXTS))
 def test_deflate_round_trip(hip_ctx, name):
     from colorid_amd.hip import bgzf_deflate
@@ -164,7 +77,7 @@ def test_deflate_round_trip(hip_ctx, name):
         assert all((m[18] & 7) == 0b101 for m in members)                         # BFINAL, dynamic Huffman
     if name == "fibonacci":                                                       # the case is what it claims: the plain tree is deeper than
         assert unlimited_huffman_depth(text) > 15                                 # DEFLATE allows, and the limited code reaches the limit
-        lens = literal_code_lengths(members[0])
+        lens, _ = literal_code_lengths(members[0])
         assert max(lens) == 15 and sum(2.0 ** -l for l in lens if l) == 1.0
     if name == "fastq_200k":
         assert n == 4 and len(blob) < len(text)
