@@ -85,11 +85,11 @@ __global__ void k_mode_pick_table(const uint32_t *table, uint32_t C, uint32_t cp
     const uint32_t f = i >> cp_log, c = ((i & ((1u << cp_log) - 1u)) - f) & ((1u << cp_log) - 1u);
     if (c < C) atomicMax(&best[c], ((unsigned long long)v << 32) | (0xFFFFFFFFu - f));
 }
-__global__ void k_mode_pick_runs(const uint64_t *keys, const uint32_t *runs, const uint64_t *n_runs, unsigned long long *best) {
+__global__ void k_mode_pick_runs(const uint64_t *keys, const uint32_t *runs, const uint64_t *n_runs, uint32_t C, unsigned long long *best) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= *n_runs) return;
     const uint64_t k = keys[i];
-    atomicMax(&best[k >> 32], ((unsigned long long)runs[i] << 32) | (0xFFFFFFFFu - (uint32_t)k));
+    if ((k >> 32) < C) atomicMax(&best[k >> 32], ((unsigned long long)runs[i] << 32) | (0xFFFFFFFFu - (uint32_t)k));
 }
 __global__ void k_mode_final(const unsigned long long *best, uint32_t C, uint64_t *modes) {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -145,7 +145,7 @@ int unique_freq_modes_finish(cid_ctx *c, ModeWork *w, unsigned long long n_ovf, 
         // (cid_kmerset_cold.hip: the rocPRIM unit is loaded only when a query has multiplicities beyond the table)
         if ((rc = cold_sort_keys_u64(c, st, w->ovf, keys_sorted.p, (size_t)n_ovf, 0u, 64u)) ||
             (rc = cold_run_length_u64(c, st, keys_sorted.p, (size_t)n_ovf, keys_u.p, runs.p, n_runs.p))) goto out;
-        hipLaunchKernelGGL(k_mode_pick_runs, dim3(grid_for_n(n_ovf)), dim3(256), 0, st, keys_u.p, runs.p, n_runs.p, w->best);
+        hipLaunchKernelGGL(k_mode_pick_runs, dim3(grid_for_n(n_ovf)), dim3(256), 0, st, keys_u.p, runs.p, n_runs.p, w->C, w->best);
         hipLaunchKernelGGL(k_mode_final, dim3((w->C + 255) / 256), dim3(256), 0, st, w->best, w->C, d_modes);
         if (hipGetLastError() != hipSuccess) rc = fail(CID_ERR_HIP, "mode kernels");
     }

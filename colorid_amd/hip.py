@@ -37,6 +37,11 @@ class Context:
             from ._lib import CidError
             raise CidError(rc, self.lib.cid_last_error().decode(errors="replace"))
 
+    def unique_freq_modes_dev(self, d_uc, d_freq, n, n_colors, d_modes):
+        """cid_unique_freq_modes_dev: the mode step alone on device arrays (d_freq 0 / None = every multiplicity 1); d_modes is u64[n_colors]"""
+        check(self.lib.cid_unique_freq_modes_dev(self.h, vp(d_uc) if d_uc else None, vp(d_freq) if d_freq else None, n, n_colors,
+                                                 vp(d_modes) if d_modes else None))
+
     def timer_start(self):
         check(self.lib.cid_timer_start(self.h))
 

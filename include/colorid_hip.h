@@ -320,7 +320,9 @@ CID_CORE int cid_search_perfect_set(cid_ctx *, const cid_index *, const cid_kmer
 /* The same search with everything reports::generate_report prints (src/reports.rs:8-48) and nothing per k-mer: per colour the
  * hits, the number of k-mers that hit only that colour, the sum of their multiplicities (-> mean) and their MODE
  * (src/reports.rs:65-77; ties -> the smallest value, the reference's tie follows HashMap order) — 4 x n_colors u64 instead of
- * 8 bytes per k-mer crossing PCIe.  cid_unique_freq_modes_dev is the mode step alone on device arrays (d_freq NULL = all 1). */
+ * 8 bytes per k-mer crossing PCIe.  cid_unique_freq_modes_dev is the mode step alone on device arrays (d_freq NULL = all 1).
+ * Precondition: every d_unique_colour entry is below n_colors or is 0xFFFFFFFF (no unique colour); d_modes[c] = 0 for a colour
+ * without an entry. */
 CID_CORE int cid_search_count_set_report(cid_ctx *, const cid_index *, const cid_kmerset *, uint64_t *hits, uint64_t *n_unique,
                                 uint64_t *sum_unique_freq, uint64_t *mode_unique_freq);
 int cid_unique_freq_modes_dev(cid_ctx *, const uint32_t *d_unique_colour, const uint32_t *d_freq, size_t n_kmers, uint32_t n_colors,
