@@ -342,29 +342,17 @@ int cid_index_row_stride_words(const cid_index *ix, uint64_t *row_stride_words) 
 }  // extern "C"
 
 namespace cid {
-int index_insert_codes(cid_index *ix, const uint64_t *d_codes, size_t n, uint32_t k, uint32_t colour) {
-    if (!ix || (n && !d_codes)) return fail(CID_ERR_INVALID, "null argument");
+int index_insert_keys(cid_index *ix, const DevKeys &keys, uint32_t colour) {
+    if (!ix || (keys.n && !keys.ascii && !keys.codes)) return fail(CID_ERR_INVALID, "null argument");
     if (ix->finalized) return fail(CID_ERR_STATE, "index already finalized");
-    if (ix->k != k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", k, ix->k);
+    if (ix->k != keys.k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", keys.k, ix->k);
     if (colour >= ix->n_colors) return fail(CID_ERR_INVALID, "colour %u >= n_colors", colour);
     cid_ctx *c = ix->ctx;
     HIP_TRY(hipSetDevice(c->device));
-    InsertParams p = insert_params(ix, n);
-    p.codes = d_codes; p.colour = colour;
+    InsertParams p = insert_params(ix, keys.n);
+    p.kmers = keys.ascii; p.codes = keys.codes; p.colour = colour;
     HIP_TRY(cid::launch_insert_kmers(p, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CID_OK;
 }
-int index_insert_ascii(cid_index *ix, const uint8_t *d_ascii, size_t n, uint32_t k, uint32_t colour) {
-    if (!ix || (n && !d_ascii)) return fail(CID_ERR_INVALID, "null argument");
-    if (ix->finalized) return fail(CID_ERR_STATE, "index already finalized");
-    if (ix->k != k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", k, ix->k);
-    if (colour >= ix->n_colors) return fail(CID_ERR_INVALID, "colour %u >= n_colors", colour);
-    cid_ctx *c = ix->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    InsertParams p = insert_params(ix, n);
-    p.kmers = d_ascii; p.colour = colour;
-    HIP_TRY(cid::launch_insert_kmers(p, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return CID_OK;
-}}  // namespace cid
+}  // namespace cid

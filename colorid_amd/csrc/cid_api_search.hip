@@ -13,10 +13,11 @@ using namespace cid::slots;
 
 namespace {
 
-// bytes per chunk of the pipelined host-pointer calls (H2D of chunk i+1 beside the kernel of chunk i)
-// (cid_ctx_tune "upload_chunk_bytes" / CID_UPLOAD_CHUNK_BYTES: 256 MiB of k-mers per upload chunk)
-
-int fill_search_params(const cid_ctx *c, const cid_index *ix, cid::SearchParams &p) {
+// the index's search parameters with `keys` as the query (outputs and modes are the caller's to set); refuses keys that no kernel can read
+int fill_search_params(const cid_ctx *c, const cid_index *ix, const cid::DevKeys &keys, cid::SearchParams &p) {
+    if (keys.n && !keys.ascii && !keys.codes) return fail(CID_ERR_INVALID, "null argument");
+    if (keys.ascii && !aligned16(keys.ascii)) return fail(CID_ERR_INVALID, "d_kmers must be 16-byte aligned");
+    if (keys.codes && ix->k > 32) return fail(CID_ERR_UNSUPPORTED, "2-bit codes need k_size <= 32");
     memset(&p, 0, sizeof(p));
     p.mat = ix->mat;
     p.rs = ix->rs;
@@ -37,29 +38,111 @@ int fill_search_params(const cid_ctx *c, const cid_index *ix, cid::SearchParams 
     if (cid::search_smem_bytes(p) > 160u * 1024u)
         return fail(CID_ERR_UNSUPPORTED, "LDS need %zu B exceeds 160 KiB (n_colors=%u k=%u n_hash=%u)",
                     cid::search_smem_bytes(p), ix->n_colors, ix->k, ix->n_hash);
+    p.kmers = keys.ascii; p.codes = keys.codes; p.n_kmers = keys.n;
+    p.tiles_per_block = pick_tiles_per_block(c, keys.n);
     return CID_OK;
 }
-}  // namespace
 
-int cid::search_count_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_codes, const uint32_t *d_freq,
-                             size_t n_kmers, uint64_t *d_hits, uint64_t *d_n_unique, uint64_t *d_sum_unique_freq,
-                             uint32_t *d_unique_colour, bool zero_counters) {
+// a caller's device pointers as keys of the index's k
+cid::DevKeys caller_keys(const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_codes, const uint32_t *d_freq, size_t n_kmers) {
+    return cid::DevKeys{d_kmers, d_codes, d_freq, n_kmers, ix ? ix->k : 0, nullptr};
+}
+
+// k-mers per chunk of the pipelined host-pointer calls (cid_ctx_tune "upload_chunk_bytes" / CID_UPLOAD_CHUNK_BYTES: 256 MiB at k + 8 bytes
+// a k-mer).  Chunks start on a tile boundary: 64*k bytes keep the 16-byte alignment of the k-mer array; a budget below k + 8 bytes
+// (0 included) still moves a tile per chunk
+size_t upload_chunk_kmers(const cid_ctx *c, size_t k) {
+    const size_t chunk = ((size_t)c->tune.upload_chunk_bytes / (k + 8) + 63) & ~(size_t)63;
+    return chunk ? chunk : 64;
+}
+
+// host results for k-mers that are already on the device
+int search_count_to_host(cid_ctx *c, const cid_index *ix, const cid::DevKeys &keys, uint64_t *hits, uint64_t *n_unique, uint64_t *sum_unique_freq,
+                         uint32_t *unique_colour) {
+    const size_t C = ix->n_colors;
+    void *d_out, *d_uc = nullptr;
+    int rc = slot_reserve(c, S_OUT, 3 * C * 8, &d_out);
+    if (rc) return rc;
+    if (unique_colour) { rc = slot_reserve(c, S_UC, keys.n * 4, &d_uc); if (rc) return rc; }
+    uint64_t *o = (uint64_t *)d_out;
+    rc = cid::search_count_launch(c, ix, keys, o, n_unique ? o + C : nullptr, sum_unique_freq ? o + 2 * C : nullptr, (uint32_t *)d_uc);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(hits, o, C * 8, hipMemcpyDeviceToHost, c->stream));
+    if (n_unique) HIP_TRY(hipMemcpyAsync(n_unique, o + C, C * 8, hipMemcpyDeviceToHost, c->stream));
+    if (sum_unique_freq) HIP_TRY(hipMemcpyAsync(sum_unique_freq, o + 2 * C, C * 8, hipMemcpyDeviceToHost, c->stream));
+    if (unique_colour) HIP_TRY(hipMemcpyAsync(unique_colour, d_uc, keys.n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CID_OK;
+}
+
+int search_perfect_to_host(cid_ctx *c, const cid_index *ix, const cid::DevKeys &keys, uint32_t *and_words_le, int *any_row_missing) {
+    void *d_out;
+    int rc = slot_reserve(c, S_MISC, (size_t)ix->rs * 8 + 16, &d_out);
+    if (rc) return rc;
+    uint64_t *d_and = (uint64_t *)d_out;
+    int *d_missing = (int *)(d_and + ix->rs);
+    rc = cid::search_perfect_launch(c, ix, keys, d_and, d_missing);
+    if (rc) return rc;
+    std::vector<uint64_t> h(ix->rs);
+    int missing = 0;
+    HIP_TRY(hipMemcpyAsync(h.data(), d_and, (size_t)ix->rs * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&missing, d_missing, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *any_row_missing = missing ? 1 : 0;
+    for (uint32_t w = 0; w < ix->w32; ++w) {
+        const uint32_t v = (uint32_t)(h[w / 2] >> (32 * (w & 1)));
+        and_words_le[w] = missing ? 0u : v;
+    }
+    return CID_OK;
+}
+
+int check_segments_index(const cid_ctx *c, const cid_index *ix) {
     int rc = check_ready(c, ix);
     if (rc) return rc;
     if ((rc = check_not_mini(ix))) return rc;
-    if (!d_hits || (n_kmers && !d_kmers && !d_codes)) return fail(CID_ERR_INVALID, "null argument");
-    if (d_kmers && !aligned16(d_kmers)) return fail(CID_ERR_INVALID, "d_kmers must be 16-byte aligned");
+    if (ix->rs > 128)
+        return fail(CID_ERR_UNSUPPORTED, "segmented search needs at most 8192 colours (index has %u): one cid_search_count per segment instead", ix->n_colors);
+    return CID_OK;
+}
+
+// device-resident inputs and outputs; `zero`: clear the outputs first (else they are added to); asynchronous on the ctx stream
+int search_segments_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs, uint64_t n_kmers,
+                           uint32_t *d_hits, uint8_t *d_missing, bool zero) {
+    if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
+    if (!d_seg_off || !d_hits) return fail(CID_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
-    cid::SearchParams p;
-    rc = fill_search_params(c, ix, p);
+    cid::SegmentParams q;
+    int rc = fill_search_params(c, ix, caller_keys(ix, d_kmers, nullptr, nullptr, n_kmers), q.s);
     if (rc) return rc;
-    p.kmers = d_kmers; p.codes = d_codes; p.freq = d_freq; p.n_kmers = n_kmers;
+    q.seg_off = d_seg_off; q.n_segs = n_segs; q.hits = d_hits; q.missing = d_missing;
+    if (zero) {
+        HIP_TRY(hipMemsetAsync(d_hits, 0, n_segs * (size_t)ix->n_colors * 4, c->stream));
+        if (d_missing) HIP_TRY(hipMemsetAsync(d_missing, 0, n_segs, c->stream));
+    }
+    HIP_TRY(cid::launch_search_segments(q, c->stream));
+    return CID_OK;
+}
+
+}  // namespace
+
+namespace cid {
+
+int search_count_launch(cid_ctx *c, const cid_index *ix, const DevKeys &keys, uint64_t *d_hits, uint64_t *d_n_unique, uint64_t *d_sum_unique_freq,
+                        uint32_t *d_unique_colour, bool zero_counters) {
+    int rc = check_ready(c, ix);
+    if (rc) return rc;
+    if ((rc = check_not_mini(ix))) return rc;
+    if (!d_hits) return fail(CID_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    SearchParams p;
+    rc = fill_search_params(c, ix, keys, p);
+    if (rc) return rc;
+    p.freq = keys.counts;
     p.hits = d_hits; p.n_unique = d_n_unique; p.sum_unique_freq = d_sum_unique_freq; p.unique_colour = d_unique_colour;
     p.want_unique = (d_n_unique || d_sum_unique_freq || d_unique_colour) ? 1u : 0u;
-    p.tiles_per_block = pick_tiles_per_block(c, n_kmers);
 #ifdef CID_TUNE_BUILD
     p.mixed = c->tune.search_mixed ? 1u : 0u;
-    if (c->tune.search_persist && ix->rs <= 128 && n_kmers >= (1u << 16)) {   // persistent grid, one work queue per XCD (cid_search.hip)
+    if (c->tune.search_persist && ix->rs <= 128 && keys.n >= (1u << 16)) {   // persistent grid, one work queue per XCD (cid_search.hip)
         void *d_q;
         rc = slot_reserve(c, S_QUEUE, 8 * 128, &d_q); if (rc) return rc;
         HIP_TRY(hipMemsetAsync(d_q, 0, 8 * 128, c->stream));
@@ -77,114 +160,20 @@ int cid::search_count_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_k
     HIP_TRY(cid::launch_search_count(p, c->stream));
     return CID_OK;
 }
-using cid::search_count_launch;
-extern "C" {
-
-int cid_search_count_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint32_t *d_freq, size_t n_kmers,
-                         uint64_t *d_hits, uint64_t *d_n_unique, uint64_t *d_sum_unique_freq, uint32_t *d_unique_colour) {
-    return search_count_launch(c, ix, d_kmers, nullptr, d_freq, n_kmers, d_hits, d_n_unique, d_sum_unique_freq, d_unique_colour);
-}
-
-// One colour stripe of a wider index (SURVEY.md §8e.2): per-colour hits are final; per-k-mer popcounts and unique
-// candidates accumulate across the stripes' calls and are resolved by cid_search_unique_finalize_dev.
-int cid_search_count_stripe_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_codes, size_t n_kmers,
-                                uint32_t colour_base, uint64_t *d_hits, uint32_t *d_fact) {
-    int rc = check_ready(c, ix);
-    if (rc) return rc;
-    if ((rc = check_not_mini(ix))) return rc;
-    if (!d_hits || !d_fact || (n_kmers && !d_kmers && !d_codes)) return fail(CID_ERR_INVALID, "null argument");
-    if (d_kmers && !aligned16(d_kmers)) return fail(CID_ERR_INVALID, "d_kmers must be 16-byte aligned");
-    if (d_codes && ix->k > 32) return fail(CID_ERR_UNSUPPORTED, "2-bit codes need k_size <= 32");
-    HIP_TRY(hipSetDevice(c->device));
-    cid::SearchParams p;
-    rc = fill_search_params(c, ix, p);
-    if (rc) return rc;
-    p.kmers = d_kmers; p.codes = d_codes; p.n_kmers = n_kmers; p.hits = d_hits;
-    p.colour_base = colour_base; p.fact = d_fact;
-    p.tiles_per_block = pick_tiles_per_block(c, n_kmers);
-    HIP_TRY(hipMemsetAsync(d_hits, 0, (size_t)ix->n_colors * 8, c->stream));
-    HIP_TRY(cid::launch_search_count(p, c->stream));
-    return CID_OK;
-}
-
-int cid_search_unique_finalize_dev(cid_ctx *c, const uint32_t *d_fact, const uint32_t *d_freq,
-                                   size_t n_kmers, uint32_t n_colors_total, uint64_t *d_n_unique, uint64_t *d_sum_unique_freq,
-                                   uint32_t *d_unique_colour) {
-    if (!c || (n_kmers && !d_fact) || n_colors_total == 0 || n_colors_total > (1u << 20)) return fail(CID_ERR_INVALID, "bad argument");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(cid::launch_unique_finalize(d_fact, d_freq, n_kmers, n_colors_total, d_n_unique, d_sum_unique_freq,
-                                        d_unique_colour, c->stream));
-    return CID_OK;
-}
-
-// Perfect search on one stripe: the stripe's AND words are final; d_zero_acc[n_kmers] (preset to all-ones) collects,
-// per k-mer, the seeds whose row is all-zero in every stripe so far — any bit left at the end means "row absent".
-int cid_search_perfect_stripe_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_codes, size_t n_kmers,
-                                  uint64_t *d_and_words, uint32_t *d_zero_acc) {
-    int rc = check_ready(c, ix);
-    if (rc) return rc;
-    if ((rc = check_not_mini(ix))) return rc;
-    if (!d_and_words || !d_zero_acc || (n_kmers && !d_kmers && !d_codes)) return fail(CID_ERR_INVALID, "null argument");
-    if (d_codes && ix->k > 32) return fail(CID_ERR_UNSUPPORTED, "2-bit codes need k_size <= 32");
-    if (d_kmers && !aligned16(d_kmers)) return fail(CID_ERR_INVALID, "d_kmers must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(c->device));
-    void *d_scratch;
-    rc = slot_reserve(c, S_MISC, 16, &d_scratch);
-    if (rc) return rc;
-    cid::SearchParams p;
-    rc = fill_search_params(c, ix, p);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(d_and_words, 0xFF, (size_t)ix->rs * 8, c->stream));
-    p.kmers = d_kmers; p.codes = d_codes; p.n_kmers = n_kmers; p.and_words = d_and_words; p.missing = (int *)d_scratch;
-    p.zero_acc = d_zero_acc;
-    p.tiles_per_block = pick_tiles_per_block(c, n_kmers);
-    HIP_TRY(cid::launch_search_perfect(p, c->stream));
-    return CID_OK;
-}
-int cid_search_count_codes_dev(cid_ctx *c, const cid_index *ix, const uint64_t *d_codes, const uint32_t *d_freq, size_t n_kmers,
-                               uint64_t *d_hits, uint64_t *d_n_unique, uint64_t *d_sum_unique_freq, uint32_t *d_unique_colour) {
-    if (ix && ix->k > 32) return fail(CID_ERR_UNSUPPORTED, "2-bit codes need k_size <= 32");
-    return search_count_launch(c, ix, nullptr, d_codes, d_freq, n_kmers, d_hits, d_n_unique, d_sum_unique_freq, d_unique_colour);
-}
-
-// host results for k-mers (ASCII `d_k` or codes `d_codes`) that are already on the device
-static int search_count_to_host(cid_ctx *c, const cid_index *ix, const uint8_t *d_k, const uint64_t *d_codes, const uint32_t *d_f,
-                                size_t n_kmers, uint64_t *hits, uint64_t *n_unique, uint64_t *sum_unique_freq, uint32_t *unique_colour) {
-    const size_t C = ix->n_colors;
-    void *d_out, *d_uc = nullptr;
-    int rc = slot_reserve(c, S_OUT, 3 * C * 8, &d_out);
-    if (rc) return rc;
-    if (unique_colour) { rc = slot_reserve(c, S_UC, n_kmers * 4, &d_uc); if (rc) return rc; }
-    uint64_t *o = (uint64_t *)d_out;
-    rc = search_count_launch(c, ix, d_k, d_codes, d_f, n_kmers, o, n_unique ? o + C : nullptr, sum_unique_freq ? o + 2 * C : nullptr,
-                             (uint32_t *)d_uc);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(hits, o, C * 8, hipMemcpyDeviceToHost, c->stream));
-    if (n_unique) HIP_TRY(hipMemcpyAsync(n_unique, o + C, C * 8, hipMemcpyDeviceToHost, c->stream));
-    if (sum_unique_freq) HIP_TRY(hipMemcpyAsync(sum_unique_freq, o + 2 * C, C * 8, hipMemcpyDeviceToHost, c->stream));
-    if (unique_colour) HIP_TRY(hipMemcpyAsync(unique_colour, d_uc, n_kmers * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return CID_OK;
-}
 
 // Host-pointer form.  The batch goes through in chunks: the H2D copy of chunk i+1 (copy stream) runs beside the kernel of chunk i
 // (ctx stream), and the per-k-mer results of chunk i-1 come back while both run; counters accumulate on the device over the
 // chunks.  What is left is the PCIe time of 31+4 bytes in and 4 bytes out per k-mer.
-}  // extern "C"
-// host k-mers in, per-k-mer results out to the host, the 3*C counters (hits | n_unique | sum_unique_freq) left on the device in
+// Host k-mers in, per-k-mer results out to the host, the 3*C counters (hits | n_unique | sum_unique_freq) left on the device in
 // *d_counters (the ctx's S_OUT slot); returns with both streams drained
-int cid::search_count_host_input(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint32_t *freq, size_t n_kmers, bool want_unique,
-                                 uint32_t *unique_colour, uint64_t **d_counters) {
+int search_count_host_input(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint32_t *freq, size_t n_kmers, bool want_unique,
+                            uint32_t *unique_colour, uint64_t **d_counters) {
     int rc = check_ready(c, ix);
     if (rc) return rc;
     if (n_kmers && !kmers) return fail(CID_ERR_INVALID, "null argument");
-    uint64_t hits_dummy = 0;
-    uint64_t *hits = &hits_dummy, *n_unique = want_unique ? &hits_dummy : nullptr, *sum_unique_freq = n_unique;
     HIP_TRY(hipSetDevice(c->device));
     const size_t C = ix->n_colors, k = ix->k;
-    size_t chunk = (size_t)c->tune.upload_chunk_bytes / (k + 8);
-    chunk = (chunk + 63) & ~(size_t)63;          // chunks start on a tile boundary: 64*k bytes keep the 16-byte alignment of the k-mer array
-    if (chunk == 0) chunk = 64;                  // a budget below k + 8 bytes (0 included) still moves a tile per chunk
+    size_t chunk = upload_chunk_kmers(c, k);
     if (chunk >= n_kmers || c->stream != c->own_stream) chunk = n_kmers ? n_kmers : 1;   // a borrowed stream: keep everything on it
     void *d_k, *d_f = nullptr, *d_out, *d_uc = nullptr;
     const size_t two = chunk < n_kmers ? 2 : 1;
@@ -212,7 +201,7 @@ int cid::search_count_host_input(cid_ctx *c, const cid_index *ix, const uint8_t 
             HIP_TRY(hipEventRecord(c->ev_copied[b], cs));
             HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_copied[b], 0));
         }
-        rc = search_count_launch(c, ix, dk, nullptr, df, nk, o, n_unique ? o + C : nullptr, sum_unique_freq ? o + 2 * C : nullptr, du, false);
+        rc = search_count_launch(c, ix, DevKeys{dk, nullptr, df, nk, ix->k, c}, o, want_unique ? o + C : nullptr, want_unique ? o + 2 * C : nullptr, du, false);
         if (rc) return rc;
         if (piped) HIP_TRY(hipEventRecord(c->ev_done[b], c->stream));
         // the previous chunk's per-k-mer results: its kernel finished while this chunk was copied in
@@ -227,11 +216,107 @@ int cid::search_count_host_input(cid_ctx *c, const cid_index *ix, const uint8_t 
         HIP_TRY(hipMemcpyAsync(unique_colour + prev_first, (uint32_t *)d_uc + (size_t)prev_b * chunk, prev_n * 4, hipMemcpyDeviceToHost, c->stream));
     if (piped) HIP_TRY(hipStreamSynchronize(cs));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    (void)hits;
     *d_counters = o;
     return CID_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ a4
+
+int search_perfect_launch(cid_ctx *c, const cid_index *ix, const DevKeys &keys, uint64_t *d_and, int *d_missing) {
+    int rc = check_not_mini(ix);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d_and, 0xFF, (size_t)ix->rs * 8, c->stream));
+    HIP_TRY(hipMemsetAsync(d_missing, 0, 16, c->stream));
+    SearchParams p;
+    rc = fill_search_params(c, ix, keys, p);
+    if (rc) return rc;
+    p.and_words = d_and; p.missing = d_missing;
+    HIP_TRY(launch_search_perfect(p, c->stream));
+    return CID_OK;
+}
+
+int search_count_keys(cid_ctx *c, const cid_index *ix, const DevKeys &keys, uint64_t *hits, uint64_t *n_unique, uint64_t *sum_unique_freq,
+                      uint32_t *unique_colour) {
+    int rc = check_ready(c, ix);
+    if (rc) return rc;
+    if (!hits) return fail(CID_ERR_INVALID, "null argument");
+    if (ix->k != keys.k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", keys.k, ix->k);
+    HIP_TRY(hipSetDevice(c->device));
+    return search_count_to_host(c, ix, keys, hits, n_unique, sum_unique_freq, unique_colour);
+}
+
+int search_perfect_keys(cid_ctx *c, const cid_index *ix, const DevKeys &keys, uint32_t *and_words_le, int *any_row_missing) {
+    int rc = check_ready(c, ix);
+    if (rc) return rc;
+    if (!and_words_le || !any_row_missing) return fail(CID_ERR_INVALID, "null argument");
+    if (keys.n == 0) return fail(CID_ERR_INVALID, "perfect search needs at least one k-mer (src/perfect_search.rs:22-23)");
+    if (ix->k != keys.k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", keys.k, ix->k);
+    HIP_TRY(hipSetDevice(c->device));
+    return search_perfect_to_host(c, ix, keys, and_words_le, any_row_missing);
+}
+
+}  // namespace cid
+
 extern "C" {
+
+int cid_search_count_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint32_t *d_freq, size_t n_kmers,
+                         uint64_t *d_hits, uint64_t *d_n_unique, uint64_t *d_sum_unique_freq, uint32_t *d_unique_colour) {
+    return cid::search_count_launch(c, ix, caller_keys(ix, d_kmers, nullptr, d_freq, n_kmers), d_hits, d_n_unique, d_sum_unique_freq, d_unique_colour);
+}
+
+int cid_search_count_codes_dev(cid_ctx *c, const cid_index *ix, const uint64_t *d_codes, const uint32_t *d_freq, size_t n_kmers,
+                               uint64_t *d_hits, uint64_t *d_n_unique, uint64_t *d_sum_unique_freq, uint32_t *d_unique_colour) {
+    return cid::search_count_launch(c, ix, caller_keys(ix, nullptr, d_codes, d_freq, n_kmers), d_hits, d_n_unique, d_sum_unique_freq, d_unique_colour);
+}
+
+// One colour stripe of a wider index (SURVEY.md §8e.2): per-colour hits are final; per-k-mer popcounts and unique
+// candidates accumulate across the stripes' calls and are resolved by cid_search_unique_finalize_dev.
+int cid_search_count_stripe_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_codes, size_t n_kmers,
+                                uint32_t colour_base, uint64_t *d_hits, uint32_t *d_fact) {
+    int rc = check_ready(c, ix);
+    if (rc) return rc;
+    if ((rc = check_not_mini(ix))) return rc;
+    if (!d_hits || !d_fact) return fail(CID_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    cid::SearchParams p;
+    rc = fill_search_params(c, ix, caller_keys(ix, d_kmers, d_codes, nullptr, n_kmers), p);
+    if (rc) return rc;
+    p.hits = d_hits; p.colour_base = colour_base; p.fact = d_fact;
+    HIP_TRY(hipMemsetAsync(d_hits, 0, (size_t)ix->n_colors * 8, c->stream));
+    HIP_TRY(cid::launch_search_count(p, c->stream));
+    return CID_OK;
+}
+
+int cid_search_unique_finalize_dev(cid_ctx *c, const uint32_t *d_fact, const uint32_t *d_freq,
+                                   size_t n_kmers, uint32_t n_colors_total, uint64_t *d_n_unique, uint64_t *d_sum_unique_freq,
+                                   uint32_t *d_unique_colour) {
+    if (!c || (n_kmers && !d_fact) || n_colors_total == 0 || n_colors_total > (1u << 20)) return fail(CID_ERR_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(cid::launch_unique_finalize(d_fact, d_freq, n_kmers, n_colors_total, d_n_unique, d_sum_unique_freq,
+                                        d_unique_colour, c->stream));
+    return CID_OK;
+}
+
+// Perfect search on one stripe: the stripe's AND words are final; d_zero_acc[n_kmers] (preset to all-ones) collects,
+// per k-mer, the seeds whose row is all-zero in every stripe so far — any bit left at the end means "row absent".
+int cid_search_perfect_stripe_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_codes, size_t n_kmers,
+                                  uint64_t *d_and_words, uint32_t *d_zero_acc) {
+    int rc = check_ready(c, ix);
+    if (rc) return rc;
+    if ((rc = check_not_mini(ix))) return rc;
+    if (!d_and_words || !d_zero_acc) return fail(CID_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    void *d_scratch;
+    rc = slot_reserve(c, S_MISC, 16, &d_scratch);
+    if (rc) return rc;
+    cid::SearchParams p;
+    rc = fill_search_params(c, ix, caller_keys(ix, d_kmers, d_codes, nullptr, n_kmers), p);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d_and_words, 0xFF, (size_t)ix->rs * 8, c->stream));
+    p.and_words = d_and_words; p.missing = (int *)d_scratch; p.zero_acc = d_zero_acc;
+    HIP_TRY(cid::launch_search_perfect(p, c->stream));
+    return CID_OK;
+}
 
 int cid_search_count(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint32_t *freq, size_t n_kmers,
                      uint64_t *hits, uint64_t *n_unique, uint64_t *sum_unique_freq, uint32_t *unique_colour) {
@@ -247,47 +332,6 @@ int cid_search_count(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, cons
     return CID_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ a4
-
-}  // extern "C"
-int cid::search_perfect_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_k, const uint64_t *d_codes, size_t n_kmers, uint64_t *d_and,
-                               int *d_missing) {
-    int rc = check_not_mini(ix);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(d_and, 0xFF, (size_t)ix->rs * 8, c->stream));
-    HIP_TRY(hipMemsetAsync(d_missing, 0, 16, c->stream));
-    cid::SearchParams p;
-    rc = fill_search_params(c, ix, p);
-    if (rc) return rc;
-    p.kmers = d_k; p.codes = d_codes; p.n_kmers = n_kmers; p.and_words = d_and; p.missing = d_missing;
-    p.tiles_per_block = pick_tiles_per_block(c, n_kmers);
-    HIP_TRY(cid::launch_search_perfect(p, c->stream));
-    return CID_OK;
-}
-extern "C" {
-
-static int search_perfect_to_host(cid_ctx *c, const cid_index *ix, const uint8_t *d_k, const uint64_t *d_codes, size_t n_kmers,
-                                  uint32_t *and_words_le, int *any_row_missing) {
-    void *d_out;
-    int rc = slot_reserve(c, S_MISC, (size_t)ix->rs * 8 + 16, &d_out);
-    if (rc) return rc;
-    uint64_t *d_and = (uint64_t *)d_out;
-    int *d_missing = (int *)(d_and + ix->rs);
-    rc = cid::search_perfect_launch(c, ix, d_k, d_codes, n_kmers, d_and, d_missing);
-    if (rc) return rc;
-    std::vector<uint64_t> h(ix->rs);
-    int missing = 0;
-    HIP_TRY(hipMemcpyAsync(h.data(), d_and, (size_t)ix->rs * 8, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(&missing, d_missing, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *any_row_missing = missing ? 1 : 0;
-    for (uint32_t w = 0; w < ix->w32; ++w) {
-        const uint32_t v = (uint32_t)(h[w / 2] >> (32 * (w & 1)));
-        and_words_le[w] = missing ? 0u : v;
-    }
-    return CID_OK;
-}
-
 int cid_search_perfect(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, size_t n_kmers, uint32_t *and_words_le,
                        int *any_row_missing) {
     int rc = check_ready(c, ix);
@@ -299,88 +343,10 @@ int cid_search_perfect(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, si
     rc = slot_reserve(c, S_KMERS, n_kmers * ix->k, &d_k);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(d_k, kmers, n_kmers * ix->k, hipMemcpyHostToDevice, c->stream));
-    return search_perfect_to_host(c, ix, (const uint8_t *)d_k, nullptr, n_kmers, and_words_le, any_row_missing);
+    return search_perfect_to_host(c, ix, cid::DevKeys{(const uint8_t *)d_k, nullptr, nullptr, n_kmers, ix->k, c}, and_words_le, any_row_missing);
 }
-
-extern "C++" {
-namespace cid {
-int search_count_ascii(cid_ctx *c, const cid_index *ix, const uint8_t *d_ascii, const uint32_t *d_counts, size_t n, uint32_t k,
-                       uint64_t *hits, uint64_t *n_unique, uint64_t *sum_unique_freq, uint32_t *unique_colour) {
-    int rc = check_ready(c, ix);
-    if (rc) return rc;
-    if (!hits) return fail(CID_ERR_INVALID, "null argument");
-    if (ix->k != k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", k, ix->k);
-    HIP_TRY(hipSetDevice(c->device));
-    return search_count_to_host(c, ix, d_ascii, nullptr, d_counts, n, hits, n_unique, sum_unique_freq, unique_colour);
-}
-int search_perfect_ascii(cid_ctx *c, const cid_index *ix, const uint8_t *d_ascii, size_t n, uint32_t k, uint32_t *and_words_le, int *any_row_missing) {
-    int rc = check_ready(c, ix);
-    if (rc) return rc;
-    if (!and_words_le || !any_row_missing) return fail(CID_ERR_INVALID, "null argument");
-    if (n == 0) return fail(CID_ERR_INVALID, "perfect search needs at least one k-mer (src/perfect_search.rs:22-23)");
-    if (ix->k != k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", k, ix->k);
-    HIP_TRY(hipSetDevice(c->device));
-    return search_perfect_to_host(c, ix, d_ascii, nullptr, n, and_words_le, any_row_missing);
-}
-int search_count_codes(cid_ctx *c, const cid_index *ix, const uint64_t *d_codes, const uint32_t *d_counts, size_t n, uint32_t k,
-                       uint64_t *hits, uint64_t *n_unique, uint64_t *sum_unique_freq, uint32_t *unique_colour) {
-    int rc = check_ready(c, ix);
-    if (rc) return rc;
-    if (!hits) return fail(CID_ERR_INVALID, "null argument");
-    if (ix->k != k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", k, ix->k);
-    HIP_TRY(hipSetDevice(c->device));
-    return search_count_to_host(c, ix, nullptr, d_codes, d_counts, n, hits, n_unique, sum_unique_freq, unique_colour);
-}
-int search_perfect_codes(cid_ctx *c, const cid_index *ix, const uint64_t *d_codes, size_t n, uint32_t k, uint32_t *and_words_le,
-                         int *any_row_missing) {
-    int rc = check_ready(c, ix);
-    if (rc) return rc;
-    if (!and_words_le || !any_row_missing) return fail(CID_ERR_INVALID, "null argument");
-    if (n == 0) return fail(CID_ERR_INVALID, "perfect search needs at least one k-mer (src/perfect_search.rs:22-23)");
-    if (ix->k != k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", k, ix->k);
-    HIP_TRY(hipSetDevice(c->device));
-    return search_perfect_to_host(c, ix, nullptr, d_codes, n, and_words_le, any_row_missing);
-}
-}  // namespace cid
-}  // extern "C++"
-
-}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ segmented search (cid_segments.hip)
-
-namespace {
-int check_segments_index(const cid_ctx *c, const cid_index *ix) {
-    int rc = check_ready(c, ix);
-    if (rc) return rc;
-    if ((rc = check_not_mini(ix))) return rc;
-    if (ix->rs > 128)
-        return fail(CID_ERR_UNSUPPORTED, "segmented search needs at most 8192 colours (index has %u): one cid_search_count per segment instead", ix->n_colors);
-    return CID_OK;
-}
-
-// device-resident inputs and outputs; `zero`: clear the outputs first (else they are added to); asynchronous on the ctx stream
-int search_segments_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs, uint64_t n_kmers,
-                           uint32_t *d_hits, uint8_t *d_missing, bool zero) {
-    if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
-    if (!d_seg_off || !d_hits || (n_kmers && !d_kmers)) return fail(CID_ERR_INVALID, "null argument");
-    if (d_kmers && !aligned16(d_kmers)) return fail(CID_ERR_INVALID, "d_kmers must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(c->device));
-    cid::SegmentParams q;
-    int rc = fill_search_params(c, ix, q.s);
-    if (rc) return rc;
-    q.s.kmers = d_kmers; q.s.n_kmers = n_kmers;
-    q.s.tiles_per_block = pick_tiles_per_block(c, n_kmers);
-    q.seg_off = d_seg_off; q.n_segs = n_segs; q.hits = d_hits; q.missing = d_missing;
-    if (zero) {
-        HIP_TRY(hipMemsetAsync(d_hits, 0, n_segs * (size_t)ix->n_colors * 4, c->stream));
-        if (d_missing) HIP_TRY(hipMemsetAsync(d_missing, 0, n_segs, c->stream));
-    }
-    HIP_TRY(cid::launch_search_segments(q, c->stream));
-    return CID_OK;
-}
-}  // namespace
-
-extern "C" {
 
 int cid_search_segments_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs, uint64_t n_kmers,
                             uint32_t *d_hits, uint8_t *d_any_row_missing) {
@@ -409,9 +375,7 @@ int cid_search_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, c
     if (n_kmers && !kmers) return fail(CID_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
     const size_t C = ix->n_colors, k = ix->k;
-    size_t chunk = (size_t)c->tune.upload_chunk_bytes / (k + 8);
-    chunk = (chunk + 63) & ~(size_t)63;
-    if (chunk == 0) chunk = 64;                  // a budget below k + 8 bytes (0 included) still moves a tile per chunk
+    size_t chunk = upload_chunk_kmers(c, k);
     if (chunk > n_kmers) chunk = n_kmers ? (size_t)n_kmers : 1;
     size_t per_slice = (size_t)(c->tune.dense_report_bytes / (C * 4));
     if (per_slice == 0) per_slice = 1;
@@ -455,4 +419,4 @@ int cid_search_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, c
     return CID_OK;
 }
 
-}  // extern "C"
+}  // extern C

@@ -56,14 +56,6 @@ int allreduce_sum(cid_group *g, void *const *d_bufs, size_t count, int elem_byte
     return CID_OK;
 }
 
-}  // namespace cidg
-
-namespace {
-
-int allreduce_u64(cid_group *g, uint64_t *const *d_bufs, size_t count) {
-    return cidg::allreduce_sum(g, reinterpret_cast<void *const *>(d_bufs), count, 8);
-}
-
 // rank 0's counters -> the caller's host arrays
 int counters_to_host(cid_group *g, const uint64_t *d0, size_t C, uint64_t *hits, uint64_t *n_unique, uint64_t *sum_unique_freq) {
     cid_ctx *c = g->ctx[0];
@@ -73,6 +65,29 @@ int counters_to_host(cid_group *g, const uint64_t *d0, size_t C, uint64_t *hits,
     if (sum_unique_freq) HIP_TRY(hipMemcpyAsync(sum_unique_freq, d0 + 2 * C, C * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CID_OK;
+}
+
+int perfect_combine(cid_group *g, cid_index *const *replicas, const std::vector<std::vector<uint32_t>> &words, const std::vector<int> &missing,
+                    const std::vector<size_t> &shard_n, uint32_t *and_words_le, int *any_row_missing) {
+    const uint32_t w32 = replicas[0]->w32;
+    int miss = 0;
+    for (uint32_t w = 0; w < w32; ++w) and_words_le[w] = 0xFFFFFFFFu;
+    for (size_t r = 0; r < g->ctx.size(); ++r) {
+        if (shard_n[r] == 0) continue;   // an empty shard contributes the neutral element
+        miss |= missing[r];
+        for (uint32_t w = 0; w < w32; ++w) and_words_le[w] &= words[r][w];
+    }
+    if (miss) for (uint32_t w = 0; w < w32; ++w) and_words_le[w] = 0;
+    *any_row_missing = miss ? 1 : 0;
+    return CID_OK;
+}
+
+}  // namespace cidg
+
+namespace {
+
+int allreduce_u64(cid_group *g, uint64_t *const *d_bufs, size_t count) {
+    return cidg::allreduce_sum(g, reinterpret_cast<void *const *>(d_bufs), count, 8);
 }
 
 }  // namespace
@@ -204,46 +219,27 @@ int cid_group_search_count_set(cid_group *g, cid_index *const *replicas, const c
     int rc = check_replicas(g, replicas);
     if (rc) return rc;
     if (!hits) return fail(CID_ERR_INVALID, "null argument");
-    cid_ctx *kc;
-    const uint64_t *codes = nullptr;
-    const uint8_t *ascii = nullptr;     // byte-string sets (k > 32): n x k bytes instead of 2-bit codes
-    const uint32_t *counts;
-    uint64_t nk;
-    uint32_t kk;
-    if (cid::kmerset_view_ascii(ks, &kc, &ascii, &counts, &nk, &kk) != CID_OK) {
-        ascii = nullptr;
-        if ((rc = cid::kmerset_view(ks, &kc, &codes, &counts, &nk, &kk))) return rc;
-    }
-    if (kk != replicas[0]->k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", kk, replicas[0]->k);
+    cid::DevKeys set;
+    if ((rc = cid::kmerset_keys(ks, &set))) return rc;
+    if (set.k != replicas[0]->k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", set.k, replicas[0]->k);
     const int n = (int)g->ctx.size();
     const size_t C = replicas[0]->n_colors;
-    const size_t unit = ascii ? kk : 8;   // bytes per k-mer in the set
-    HIP_TRY(hipSetDevice(kc->device));
-    HIP_TRY(hipStreamSynchronize(kc->stream));
+    HIP_TRY(hipSetDevice(set.ctx->device));
+    HIP_TRY(hipStreamSynchronize(set.ctx->stream));
     std::vector<uint64_t *> d_out(n, nullptr);
     rc = for_each_rank(g, [&](int r) -> int {
         cid_ctx *c = g->ctx[r];
         size_t lo, hi;
-        if (ascii) shard_bounds64(nk, r, n, &lo, &hi); else shard_bounds(nk, r, n, &lo, &hi);
+        set.shard(r, n, &lo, &hi);
         const size_t ns = hi - lo;
         HIP_TRY(hipSetDevice(c->device));
-        void *d_o, *d_uc = nullptr, *d_k = nullptr, *d_f = nullptr;
+        void *d_o, *d_uc = nullptr;
         int e = cid::slot_reserve(c, S_OUT, 3 * C * 8, &d_o); if (e) return e;
         if (unique_colour) { e = cid::slot_reserve(c, S_UC, ns * 4, &d_uc); if (e) return e; }
-        const uint8_t *my_keys = ascii ? ascii + lo * unit : reinterpret_cast<const uint8_t *>(codes + lo);
-        const uint32_t *my_counts = counts + lo;
-        if (c->device != kc->device) {   // another GPU: the slice travels over xGMI
-            e = cid::slot_reserve(c, S_KMERS, ns * unit, &d_k); if (e) return e;
-            e = cid::slot_reserve(c, S_FREQ, ns * 4, &d_f); if (e) return e;
-            if (ns) {
-                HIP_TRY(hipMemcpyPeerAsync(d_k, c->device, my_keys, kc->device, ns * unit, c->stream));
-                HIP_TRY(hipMemcpyPeerAsync(d_f, c->device, counts + lo, kc->device, ns * 4, c->stream));
-            }
-            my_keys = (const uint8_t *)d_k; my_counts = (const uint32_t *)d_f;
-        }
+        cid::DevKeys mine;
+        e = keys_on_rank(c, set.slice(lo, hi), true, &mine); if (e) return e;
         uint64_t *o = (uint64_t *)d_o;
-        e = cid::search_count_launch(c, replicas[r], ascii ? my_keys : nullptr, ascii ? nullptr : reinterpret_cast<const uint64_t *>(my_keys), my_counts, ns, o,
-                                     n_unique ? o + C : nullptr, sum_unique_freq ? o + 2 * C : nullptr, (uint32_t *)d_uc);
+        e = cid::search_count_launch(c, replicas[r], mine, o, n_unique ? o + C : nullptr, sum_unique_freq ? o + 2 * C : nullptr, (uint32_t *)d_uc);
         if (e) return e;
         if (!n_unique) HIP_TRY(hipMemsetAsync(o + C, 0, C * 8, c->stream));           // the all-reduce covers all 3*C words
         if (!sum_unique_freq) HIP_TRY(hipMemsetAsync(o + 2 * C, 0, C * 8, c->stream));
@@ -257,22 +253,7 @@ int cid_group_search_count_set(cid_group *g, cid_index *const *replicas, const c
     return counters_to_host(g, d_out[0], C, hits, n_unique, sum_unique_freq);
 }
 
-// a4 over the group: every rank ANDs the rows of its shard; the W words and the absent-row flags are combined on the host
-static int perfect_combine(cid_group *g, cid_index *const *replicas, const std::vector<std::vector<uint32_t>> &words, const std::vector<int> &missing,
-                           const std::vector<size_t> &shard_n, uint32_t *and_words_le, int *any_row_missing) {
-    const uint32_t w32 = replicas[0]->w32;
-    int miss = 0;
-    for (uint32_t w = 0; w < w32; ++w) and_words_le[w] = 0xFFFFFFFFu;
-    for (size_t r = 0; r < g->ctx.size(); ++r) {
-        if (shard_n[r] == 0) continue;   // an empty shard contributes the neutral element
-        miss |= missing[r];
-        for (uint32_t w = 0; w < w32; ++w) and_words_le[w] &= words[r][w];
-    }
-    if (miss) for (uint32_t w = 0; w < w32; ++w) and_words_le[w] = 0;
-    *any_row_missing = miss ? 1 : 0;
-    return CID_OK;
-}
-
+// a4 over the group: every rank ANDs the rows of its shard; the W words and the absent-row flags are combined on the host (perfect_combine)
 int cid_group_search_perfect(cid_group *g, cid_index *const *replicas, const uint8_t *kmers, size_t n_kmers, uint32_t *and_words_le,
                              int *any_row_missing) {
     int rc = check_replicas(g, replicas);
@@ -299,41 +280,26 @@ int cid_group_search_perfect_set(cid_group *g, cid_index *const *replicas, const
     int rc = check_replicas(g, replicas);
     if (rc) return rc;
     if (!and_words_le || !any_row_missing) return fail(CID_ERR_INVALID, "null argument");
-    cid_ctx *kc;
-    const uint64_t *codes = nullptr;
-    const uint8_t *ascii = nullptr;
-    const uint32_t *counts;
-    uint64_t nk;
-    uint32_t kk;
-    if (cid::kmerset_view_ascii(ks, &kc, &ascii, &counts, &nk, &kk) != CID_OK) {
-        ascii = nullptr;
-        if ((rc = cid::kmerset_view(ks, &kc, &codes, &counts, &nk, &kk))) return rc;
-    }
-    if (nk == 0) return fail(CID_ERR_INVALID, "perfect search needs at least one k-mer (src/perfect_search.rs:22-23)");
-    if (kk != replicas[0]->k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", kk, replicas[0]->k);
+    cid::DevKeys set;
+    if ((rc = cid::kmerset_keys(ks, &set))) return rc;
+    if (set.n == 0) return fail(CID_ERR_INVALID, "perfect search needs at least one k-mer (src/perfect_search.rs:22-23)");
+    if (set.k != replicas[0]->k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", set.k, replicas[0]->k);
     const int n = (int)g->ctx.size();
-    HIP_TRY(hipSetDevice(kc->device));
-    HIP_TRY(hipStreamSynchronize(kc->stream));
+    HIP_TRY(hipSetDevice(set.ctx->device));
+    HIP_TRY(hipStreamSynchronize(set.ctx->stream));
     std::vector<std::vector<uint32_t>> words(n, std::vector<uint32_t>(replicas[0]->w32, 0xFFFFFFFFu));
     std::vector<int> missing(n, 0);
     std::vector<size_t> shard_n(n, 0);
     rc = for_each_rank(g, [&](int r) -> int {
         cid_ctx *c = g->ctx[r];
         size_t lo, hi;
-        if (ascii) shard_bounds64(nk, r, n, &lo, &hi); else shard_bounds(nk, r, n, &lo, &hi);
+        set.shard(r, n, &lo, &hi);
         shard_n[r] = hi - lo;
         if (hi == lo) return CID_OK;
         HIP_TRY(hipSetDevice(c->device));
-        const size_t unit = ascii ? kk : 8;
-        const uint8_t *my_keys = ascii ? ascii + lo * unit : reinterpret_cast<const uint8_t *>(codes + lo);
-        if (c->device != kc->device) {
-            void *d_k;
-            const int e = cid::slot_reserve(c, S_KMERS, (hi - lo) * unit, &d_k); if (e) return e;
-            HIP_TRY(hipMemcpyPeerAsync(d_k, c->device, my_keys, kc->device, (hi - lo) * unit, c->stream));
-            my_keys = (const uint8_t *)d_k;
-        }
-        if (ascii) return cid::search_perfect_ascii(c, replicas[r], my_keys, hi - lo, kk, words[r].data(), &missing[r]);
-        return cid::search_perfect_codes(c, replicas[r], reinterpret_cast<const uint64_t *>(my_keys), hi - lo, kk, words[r].data(), &missing[r]);
+        cid::DevKeys mine;
+        const int e = keys_on_rank(c, set.slice(lo, hi), false, &mine); if (e) return e;
+        return cid::search_perfect_keys(c, replicas[r], mine, words[r].data(), &missing[r]);
     });
     if (rc) return rc;
     return perfect_combine(g, replicas, words, missing, shard_n, and_words_le, any_row_missing);

@@ -129,22 +129,7 @@ struct cid_group {
 
 namespace cidg {
 
-
-// contiguous, balanced partition (the same rule as colorid_amd/dist.py shard_bounds): sizes differ by at most one
-inline void shard_bounds(size_t n_units, int rank, int world, size_t *lo, size_t *hi) {
-    const size_t base = n_units / (size_t)world, rem = n_units % (size_t)world;
-    *lo = (size_t)rank * base + ((size_t)rank < rem ? (size_t)rank : rem);
-    *hi = *lo + base + ((size_t)rank < rem ? 1 : 0);
-}
-
-// the same with every boundary on a multiple of 64 units (byte-string k-mers: a shard's first k-mer must sit on a 16-byte boundary)
-inline void shard_bounds64(size_t n_units, int rank, int world, size_t *lo, size_t *hi) {
-    const size_t blocks = (n_units + 63) / 64;
-    shard_bounds(blocks, rank, world, lo, hi);
-    *lo *= 64; *hi *= 64;
-    if (*lo > n_units) *lo = n_units;
-    if (*hi > n_units) *hi = n_units;
-}
+using cid::shard_bounds;
 
 // run fn(rank) on one host thread per rank (a cid_ctx is used by one thread at a time); returns the first failure, whose
 // message is re-recorded on the calling thread (cid_last_error is thread-local)
@@ -179,6 +164,31 @@ inline int check_replicas(const cid_group *g, cid_index *const *replicas) {
 // ranks' ctx streams, or through the host (synchronous).  Touches no file descriptor: what RCCL may print (its version banner,
 // NCCL_DEBUG output) is printed at communicator creation, which a host that needs a clean stdout wraps itself (host/main.cpp)
 int allreduce_sum(cid_group *g, void *const *d_bufs, size_t count, int elem_bytes);
+// rank 0's counters (hits | n_unique | sum_unique_freq, C each) -> the caller's host arrays; waits for rank 0's stream
+int counters_to_host(cid_group *g, const uint64_t *d0, size_t C, uint64_t *hits, uint64_t *n_unique, uint64_t *sum_unique_freq);
+// the perfect search's AND of the ranks' words and absent-row flags on the host; a rank with shard_n == 0 contributes the neutral element
+int perfect_combine(cid_group *g, cid_index *const *replicas, const std::vector<std::vector<uint32_t>> &words, const std::vector<int> &missing,
+                    const std::vector<size_t> &shard_n, uint32_t *and_words_le, int *any_row_missing);
+
+// The keys that rank ctx `c` (its device current) should read for `keys`, which live on keys.ctx's device and are complete there:
+// the same pointers on the same GPU; on another one a copy over xGMI into c's S_KMERS slot (the counts, when wanted, into S_FREQ),
+// queued on c's stream.
+inline int keys_on_rank(cid_ctx *c, const cid::DevKeys &keys, bool want_counts, cid::DevKeys *mine) {
+    *mine = keys;
+    if (c->device == keys.ctx->device) return CID_OK;
+    void *d_k, *d_f = nullptr;
+    int rc = cid::slot_reserve(c, cid::slots::S_KMERS, keys.n * keys.unit(), &d_k); if (rc) return rc;
+    if (want_counts) { rc = cid::slot_reserve(c, cid::slots::S_FREQ, keys.n * 4, &d_f); if (rc) return rc; }
+    if (keys.n) {
+        CIDG_HIP_TRY(hipMemcpyPeerAsync(d_k, c->device, keys.bytes(), keys.ctx->device, keys.n * keys.unit(), c->stream));
+        if (want_counts) CIDG_HIP_TRY(hipMemcpyPeerAsync(d_f, c->device, keys.counts, keys.ctx->device, keys.n * 4, c->stream));
+    }
+    if (keys.ascii) mine->ascii = (const uint8_t *)d_k;
+    if (keys.codes) mine->codes = (const uint64_t *)d_k;
+    mine->counts = (const uint32_t *)d_f;
+    mine->ctx = c;
+    return CID_OK;
+}
 // the colour-striped half of cid_group_readid_sparse_fetch (cid_group_stripes.hip)
 int stripes_sparse_fetch(cid_group *g, uint64_t *row_start, uint32_t *colours, uint32_t *counts);
 

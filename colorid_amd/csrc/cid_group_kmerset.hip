@@ -45,11 +45,11 @@ __global__ void k_lower_bounds(const uint64_t *codes, uint64_t n, const uint64_t
     bounds[j] = lo;
 }
 
-struct View { cid_ctx *c; const uint64_t *codes; const uint32_t *counts; uint64_t n; };
-
-int view_of(const cid_kmerset *ks, View &v) {
-    uint32_t k;
-    return cid::kmerset_view(ks, &v.c, &v.codes, &v.counts, &v.n, &k);
+// a part's keys: 2-bit codes by construction (k <= 32), which is what this file's kernels read
+int part_keys(const cid_kmerset *ks, cid::DevKeys &v) {
+    const int rc = cid::kmerset_keys(ks, &v);
+    if (rc == CID_OK && v.ascii) return fail(CID_ERR_UNSUPPORTED, "a k_size > 32 set holds byte strings: shard it with the host-pointer group calls");
+    return rc;
 }
 
 int check_set(const cid_group_kmerset *s, bool want_final) {
@@ -120,14 +120,14 @@ int cid_group_kmerset_finalize(cid_group_kmerset *s, uint64_t *n_distinct) {
         int rc = for_each_rank(g, [&](int r) { return cid_kmerset_finalize(s->part[r], nullptr); });   // local dedup
         if (rc) return rc;
         if (n > 1) {
-            std::vector<View> v(n);
-            for (int r = 0; r < n; ++r) if ((rc = view_of(s->part[r], v[r]))) return rc;
+            std::vector<cid::DevKeys> v(n);
+            for (int r = 0; r < n; ++r) if ((rc = part_keys(s->part[r], v[r]))) return rc;
             // splitters: 1024 quantiles of every rank's own (sorted) set, pooled and cut into n equal shares
             constexpr uint32_t S = 1024;
             std::vector<uint64_t> pool;
             for (int r = 0; r < n; ++r) {
                 if (v[r].n == 0) continue;
-                cid_ctx *c = v[r].c;
+                cid_ctx *c = v[r].ctx;
                 HIP_TRY(hipSetDevice(c->device));
                 void *d_q;
                 if ((rc = cid::slot_reserve(c, S_MISC, S * 8 + 64, &d_q))) return rc;
@@ -144,7 +144,7 @@ int cid_group_kmerset_finalize(cid_group_kmerset *s, uint64_t *n_distinct) {
             // every rank: where its set crosses the splitters
             std::vector<std::vector<uint64_t>> bound(n, std::vector<uint64_t>(n + 1, 0));
             rc = for_each_rank(g, [&](int r) -> int {
-                cid_ctx *c = v[r].c;
+                cid_ctx *c = v[r].ctx;
                 bound[r][n] = v[r].n;
                 if (v[r].n == 0) return CID_OK;
                 HIP_TRY(hipSetDevice(c->device));
@@ -174,12 +174,12 @@ int cid_group_kmerset_finalize(cid_group_kmerset *s, uint64_t *n_distinct) {
                     if (!len) continue;
                     const uint64_t *sc = v[r].codes + bound[r][j];
                     const uint32_t *sn = v[r].counts + bound[r][j];
-                    if (v[r].c->device == c->device) {
+                    if (v[r].ctx->device == c->device) {
                         HIP_TRY(hipMemcpyAsync((uint64_t *)in_codes[j] + at, sc, len * 8, hipMemcpyDeviceToDevice, c->stream));
                         HIP_TRY(hipMemcpyAsync((uint32_t *)in_counts[j] + at, sn, len * 4, hipMemcpyDeviceToDevice, c->stream));
                     } else {
-                        HIP_TRY(hipMemcpyPeerAsync((uint64_t *)in_codes[j] + at, c->device, sc, v[r].c->device, len * 8, c->stream));
-                        HIP_TRY(hipMemcpyPeerAsync((uint32_t *)in_counts[j] + at, c->device, sn, v[r].c->device, len * 4, c->stream));
+                        HIP_TRY(hipMemcpyPeerAsync((uint64_t *)in_codes[j] + at, c->device, sc, v[r].ctx->device, len * 8, c->stream));
+                        HIP_TRY(hipMemcpyPeerAsync((uint32_t *)in_counts[j] + at, c->device, sn, v[r].ctx->device, len * 4, c->stream));
                     }
                     at += len;
                 }
@@ -283,15 +283,14 @@ int cid_group_search_count_parts(cid_group *g, cid_index *const *replicas, const
     std::vector<uint64_t *> d_out(n, nullptr);
     rc = for_each_rank(g, [&](int r) -> int {
         cid_ctx *c = g->ctx[r];
-        View v;
-        int e = view_of(s->part[r], v); if (e) return e;
+        cid::DevKeys v;
+        int e = part_keys(s->part[r], v); if (e) return e;
         HIP_TRY(hipSetDevice(c->device));
         void *d_o, *d_uc = nullptr;
         e = cid::slot_reserve(c, S_OUT, 3 * C * 8, &d_o); if (e) return e;
         if (unique_colour) { e = cid::slot_reserve(c, S_UC, (v.n ? v.n : 1) * 4, &d_uc); if (e) return e; }
         uint64_t *o = (uint64_t *)d_o;
-        e = cid::search_count_launch(c, replicas[r], nullptr, v.codes, v.counts, v.n, o, n_unique ? o + C : nullptr, sum_unique_freq ? o + 2 * C : nullptr,
-                                     (uint32_t *)d_uc);
+        e = cid::search_count_launch(c, replicas[r], v, o, n_unique ? o + C : nullptr, sum_unique_freq ? o + 2 * C : nullptr, (uint32_t *)d_uc);
         if (e) return e;
         if (!n_unique) HIP_TRY(hipMemsetAsync(o + C, 0, C * 8, c->stream));           // the all-reduce covers all 3*C words
         if (!sum_unique_freq) HIP_TRY(hipMemsetAsync(o + 2 * C, 0, C * 8, c->stream));
@@ -302,13 +301,7 @@ int cid_group_search_count_parts(cid_group *g, cid_index *const *replicas, const
     });
     if (rc) return rc;
     if ((rc = allreduce_sum(g, reinterpret_cast<void *const *>(d_out.data()), 3 * C, 8))) return rc;
-    cid_ctx *c0 = g->ctx[0];
-    HIP_TRY(hipSetDevice(c0->device));
-    HIP_TRY(hipMemcpyAsync(hits, d_out[0], C * 8, hipMemcpyDeviceToHost, c0->stream));
-    if (n_unique) HIP_TRY(hipMemcpyAsync(n_unique, d_out[0] + C, C * 8, hipMemcpyDeviceToHost, c0->stream));
-    if (sum_unique_freq) HIP_TRY(hipMemcpyAsync(sum_unique_freq, d_out[0] + 2 * C, C * 8, hipMemcpyDeviceToHost, c0->stream));
-    HIP_TRY(hipStreamSynchronize(c0->stream));
-    return CID_OK;
+    return counters_to_host(g, d_out[0], C, hits, n_unique, sum_unique_freq);
 }
 
 // The same with everything reports::generate_report prints and nothing per k-mer (the group form of cid_search_count_set_report):
@@ -329,14 +322,14 @@ int cid_group_search_count_parts_report(cid_group *g, cid_index *const *replicas
     std::vector<std::vector<uint32_t>> cnts(n);
     rc = for_each_rank(g, [&](int r) -> int {
         cid_ctx *c = g->ctx[r];
-        View v;
-        int e = view_of(s->part[r], v); if (e) return e;
+        cid::DevKeys v;
+        int e = part_keys(s->part[r], v); if (e) return e;
         HIP_TRY(hipSetDevice(c->device));
         void *d_o, *d_uc;
         e = cid::slot_reserve(c, S_OUT, 3 * C * 8, &d_o); if (e) return e;
         e = cid::slot_reserve(c, S_UC, (v.n ? v.n : 1) * 4, &d_uc); if (e) return e;
         uint64_t *o = (uint64_t *)d_o;
-        e = cid::search_count_launch(c, replicas[r], nullptr, v.codes, v.counts, v.n, o, o + C, o + 2 * C, (uint32_t *)d_uc);
+        e = cid::search_count_launch(c, replicas[r], v, o, o + C, o + 2 * C, (uint32_t *)d_uc);
         if (e) return e;
         e = cid::unique_freq_hist(c, (const uint32_t *)d_uc, v.counts, v.n, keys[r], cnts[r]);
         d_out[r] = o;
@@ -344,12 +337,7 @@ int cid_group_search_count_parts_report(cid_group *g, cid_index *const *replicas
     });
     if (rc) return rc;
     if ((rc = allreduce_sum(g, reinterpret_cast<void *const *>(d_out.data()), 3 * C, 8))) return rc;
-    cid_ctx *c0 = g->ctx[0];
-    HIP_TRY(hipSetDevice(c0->device));
-    HIP_TRY(hipMemcpyAsync(hits, d_out[0], C * 8, hipMemcpyDeviceToHost, c0->stream));
-    HIP_TRY(hipMemcpyAsync(n_unique, d_out[0] + C, C * 8, hipMemcpyDeviceToHost, c0->stream));
-    HIP_TRY(hipMemcpyAsync(sum_unique_freq, d_out[0] + 2 * C, C * 8, hipMemcpyDeviceToHost, c0->stream));
-    HIP_TRY(hipStreamSynchronize(c0->stream));
+    if ((rc = counters_to_host(g, d_out[0], C, hits, n_unique, sum_unique_freq))) return rc;
     // merge the ranks' sorted histograms; per colour the multiplicity with the most k-mers (keys ascend, so the first maximum is the smallest)
     std::vector<std::pair<uint64_t, uint64_t>> all;
     for (int r = 0; r < n; ++r)
@@ -380,28 +368,18 @@ int cid_group_search_perfect_parts(cid_group *g, cid_index *const *replicas, con
     cid_group_kmerset_size(s, &nk);
     if (nk == 0) return fail(CID_ERR_INVALID, "perfect search needs at least one k-mer (src/perfect_search.rs:22-23)");
     const int n = (int)g->ctx.size();
-    const uint32_t w32 = replicas[0]->w32;
-    std::vector<std::vector<uint32_t>> words(n, std::vector<uint32_t>(w32, 0xFFFFFFFFu));
+    std::vector<std::vector<uint32_t>> words(n, std::vector<uint32_t>(replicas[0]->w32, 0xFFFFFFFFu));
     std::vector<int> missing(n, 0);
-    std::vector<uint64_t> np(n, 0);
+    std::vector<size_t> np(n, 0);
     rc = for_each_rank(g, [&](int r) -> int {
-        View v;
-        const int e = view_of(s->part[r], v); if (e) return e;
+        cid::DevKeys v;
+        const int e = part_keys(s->part[r], v); if (e) return e;
         np[r] = v.n;
         if (v.n == 0) return CID_OK;
-        return cid::search_perfect_codes(g->ctx[r], replicas[r], v.codes, v.n, s->k, words[r].data(), &missing[r]);
+        return cid::search_perfect_keys(g->ctx[r], replicas[r], v, words[r].data(), &missing[r]);
     });
     if (rc) return rc;
-    int miss = 0;
-    for (uint32_t w = 0; w < w32; ++w) and_words_le[w] = 0xFFFFFFFFu;
-    for (int r = 0; r < n; ++r) {
-        if (np[r] == 0) continue;
-        miss |= missing[r];
-        for (uint32_t w = 0; w < w32; ++w) and_words_le[w] &= words[r][w];
-    }
-    if (miss) for (uint32_t w = 0; w < w32; ++w) and_words_le[w] = 0;
-    *any_row_missing = miss ? 1 : 0;
-    return CID_OK;
+    return perfect_combine(g, replicas, words, missing, np, and_words_le, any_row_missing);
 }
 
 }  // extern "C"

@@ -194,49 +194,28 @@ int reduce_u32(cid_group *g, uint32_t *const *d_bufs, size_t count, bool sum, bo
 struct Query {
     const uint8_t *h_kmers = nullptr;        // host, n x k bytes
     const uint32_t *h_freq = nullptr;        // host multiplicities (rank 0 only needs them) or NULL
-    cid_ctx *kc = nullptr;                   // the device arrays' context
-    const uint64_t *d_codes = nullptr;       // device, 2-bit codes
-    const uint8_t *d_ascii = nullptr;        // device, n x k bytes (k > 32 sets)
-    const uint32_t *d_counts = nullptr;      // device multiplicities
-    size_t n = 0;
-    uint32_t k = 0;
+    cid::DevKeys dev;                        // a device-resident set; of a host array its n and k only
 };
 
-// the whole query on rank r's device: *d_k (ASCII) or *d_c (codes)
-int query_on_rank(cid_group *g, int r, const Query &q, const uint8_t **d_k, const uint64_t **d_c) {
+// the whole query on rank r's device
+int query_on_rank(cid_group *g, int r, const Query &q, cid::DevKeys *mine) {
     cid_ctx *c = g->ctx[r];
-    *d_k = nullptr; *d_c = nullptr;
     HIP_TRY(hipSetDevice(c->device));
-    if (q.h_kmers) {
-        void *d;
-        const int rc = cid::slot_reserve(c, S_KMERS, q.n * q.k, &d); if (rc) return rc;
-        if (q.n) HIP_TRY(hipMemcpyAsync(d, q.h_kmers, q.n * q.k, hipMemcpyHostToDevice, c->stream));
-        *d_k = (const uint8_t *)d;
-        return CID_OK;
-    }
-    const size_t unit = q.d_ascii ? q.k : 8;
-    const uint8_t *src = q.d_ascii ? q.d_ascii : reinterpret_cast<const uint8_t *>(q.d_codes);
-    if (c->device != q.kc->device) {   // another GPU: the set travels over xGMI
-        void *d;
-        const int rc = cid::slot_reserve(c, S_KMERS, q.n * unit, &d); if (rc) return rc;
-        if (q.n) HIP_TRY(hipMemcpyPeerAsync(d, c->device, src, q.kc->device, q.n * unit, c->stream));
-        src = (const uint8_t *)d;
-    }
-    if (q.d_ascii) *d_k = src; else *d_c = reinterpret_cast<const uint64_t *>(src);
+    if (!q.h_kmers) return keys_on_rank(c, q.dev, false, mine);
+    void *d;
+    const int rc = cid::slot_reserve(c, S_KMERS, q.dev.n * q.dev.k, &d); if (rc) return rc;
+    if (q.dev.n) HIP_TRY(hipMemcpyAsync(d, q.h_kmers, q.dev.n * q.dev.k, hipMemcpyHostToDevice, c->stream));
+    *mine = q.dev;
+    mine->ascii = (const uint8_t *)d;
     return CID_OK;
 }
 
 int query_from_set(const cid_kmerset *ks, uint32_t index_k, Query &q) {
-    uint64_t nk;
-    if (cid::kmerset_view_ascii(ks, &q.kc, &q.d_ascii, &q.d_counts, &nk, &q.k) != CID_OK) {
-        q.d_ascii = nullptr;
-        const int rc = cid::kmerset_view(ks, &q.kc, &q.d_codes, &q.d_counts, &nk, &q.k);
-        if (rc) return rc;
-    }
-    q.n = (size_t)nk;
-    if (q.k != index_k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", q.k, index_k);
-    HIP_TRY(hipSetDevice(q.kc->device));
-    HIP_TRY(hipStreamSynchronize(q.kc->stream));
+    const int rc = cid::kmerset_keys(ks, &q.dev);
+    if (rc) return rc;
+    if (q.dev.k != index_k) return fail(CID_ERR_INVALID, "k-mer set k=%u, index k=%u", q.dev.k, index_k);
+    HIP_TRY(hipSetDevice(q.dev.ctx->device));
+    HIP_TRY(hipStreamSynchronize(q.dev.ctx->stream));
     return CID_OK;
 }
 
@@ -247,17 +226,17 @@ int stripes_search_count(cid_group *g, cid_index *const *stripes, const Query &q
     if (rc) return rc;
     if (!hits) return fail(CID_ERR_INVALID, "null argument");
     const bool want_unique = n_unique || sum_unique_freq || unique_colour || mode_unique_freq;
-    const size_t K = q.n;
+    const size_t K = q.dev.n;
     std::vector<uint32_t *> d_fact(st.n, nullptr);
     rc = for_each_rank(g, [&](int r) -> int {
         cid_ctx *c = g->ctx[r];
-        const uint8_t *d_k; const uint64_t *d_c;
-        int e = query_on_rank(g, r, q, &d_k, &d_c); if (e) return e;
+        cid::DevKeys mine;
+        int e = query_on_rank(g, r, q, &mine); if (e) return e;
         void *d_h, *d_f;
         e = cid::slot_reserve(c, S_OUT, (size_t)stripes[r]->n_colors * 8 + 3 * (size_t)st.total * 8, &d_h); if (e) return e;
         e = cid::slot_reserve(c, S_UC, (K ? K : 1) * 4, &d_f); if (e) return e;
         HIP_TRY(hipMemsetAsync(d_f, 0, (K ? K : 1) * 4, c->stream));
-        e = cid_search_count_stripe_dev(c, stripes[r], d_k, d_c, K, st.base[r], (uint64_t *)d_h, (uint32_t *)d_f);
+        e = cid_search_count_stripe_dev(c, stripes[r], mine.ascii, mine.codes, K, st.base[r], (uint64_t *)d_h, (uint32_t *)d_f);
         if (e) return e;
         HIP_TRY(hipMemcpyAsync(hits + st.base[r], d_h, (size_t)stripes[r]->n_colors * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -274,14 +253,14 @@ int stripes_search_count(cid_group *g, cid_index *const *stripes, const Query &q
     HIP_TRY(hipMemsetAsync(d_nu, 0, 2 * (size_t)st.total * 8, c0->stream));
     const uint32_t *d_freq = nullptr;
     void *d_fr = nullptr;
-    if (q.h_freq || (q.d_counts && q.kc->device != c0->device)) {
+    if (q.h_freq || (q.dev.counts && q.dev.ctx->device != c0->device)) {
         rc = cid::slot_reserve(c0, S_FREQ, (K ? K : 1) * 4, &d_fr); if (rc) return rc;
         if (K) {
             if (q.h_freq) HIP_TRY(hipMemcpyAsync(d_fr, q.h_freq, K * 4, hipMemcpyHostToDevice, c0->stream));
-            else HIP_TRY(hipMemcpyPeerAsync(d_fr, c0->device, q.d_counts, q.kc->device, K * 4, c0->stream));
+            else HIP_TRY(hipMemcpyPeerAsync(d_fr, c0->device, q.dev.counts, q.dev.ctx->device, K * 4, c0->stream));
         }
         d_freq = (const uint32_t *)d_fr;
-    } else if (q.d_counts) d_freq = q.d_counts;
+    } else if (q.dev.counts) d_freq = q.dev.counts;
     void *d_uc;
     rc = cid::ctx_alloc(c0, (K ? K : 1) * 4, &d_uc); if (rc) return rc;
     rc = cid_search_unique_finalize_dev(c0, d_fact[0], d_freq, K, st.total, d_nu, d_sf, (uint32_t *)d_uc);
@@ -315,20 +294,20 @@ int stripes_search_perfect(cid_group *g, cid_index *const *stripes, const Query 
     int rc = check_stripes(g, stripes, st);
     if (rc) return rc;
     if (!and_words_le || !any_row_missing) return fail(CID_ERR_INVALID, "null argument");
-    if (q.n == 0) return fail(CID_ERR_INVALID, "perfect search needs at least one k-mer (src/perfect_search.rs:22-23)");
-    const size_t K = q.n;
+    if (q.dev.n == 0) return fail(CID_ERR_INVALID, "perfect search needs at least one k-mer (src/perfect_search.rs:22-23)");
+    const size_t K = q.dev.n;
     const uint32_t w32_total = (st.total + 31u) / 32u;
     std::vector<uint32_t *> d_zero(st.n, nullptr);
     std::vector<std::vector<uint64_t>> words(st.n);
     rc = for_each_rank(g, [&](int r) -> int {
         cid_ctx *c = g->ctx[r];
-        const uint8_t *d_k; const uint64_t *d_c;
-        int e = query_on_rank(g, r, q, &d_k, &d_c); if (e) return e;
+        cid::DevKeys mine;
+        int e = query_on_rank(g, r, q, &mine); if (e) return e;
         void *d_w, *d_z;
         e = cid::slot_reserve(c, S_OUT, (size_t)stripes[r]->rs * 8, &d_w); if (e) return e;
         e = cid::slot_reserve(c, S_UC, K * 4, &d_z); if (e) return e;
         HIP_TRY(hipMemsetAsync(d_z, 0xFF, K * 4, c->stream));
-        e = cid_search_perfect_stripe_dev(c, stripes[r], d_k, d_c, K, (uint64_t *)d_w, (uint32_t *)d_z);
+        e = cid_search_perfect_stripe_dev(c, stripes[r], mine.ascii, mine.codes, K, (uint64_t *)d_w, (uint32_t *)d_z);
         if (e) return e;
         words[r].resize(stripes[r]->rs);
         HIP_TRY(hipMemcpyAsync(words[r].data(), d_w, (size_t)stripes[r]->rs * 8, hipMemcpyDeviceToHost, c->stream));
@@ -426,7 +405,7 @@ int cid_group_stripes_search_count(cid_group *g, cid_index *const *stripes, cons
     if (!g || !stripes || !stripes[0] || (n_kmers && !kmers)) return fail(CID_ERR_INVALID, "null argument");
     Query q;
     q.h_kmers = kmers ? kmers : reinterpret_cast<const uint8_t *>("");
-    q.h_freq = freq; q.n = n_kmers; q.k = stripes[0]->k;
+    q.h_freq = freq; q.dev.n = n_kmers; q.dev.k = stripes[0]->k;
     return stripes_search_count(g, stripes, q, hits, n_unique, sum_unique_freq, unique_colour);
 }
 
@@ -452,7 +431,7 @@ int cid_group_stripes_search_perfect(cid_group *g, cid_index *const *stripes, co
                                      int *any_row_missing) {
     if (!g || !stripes || !stripes[0] || (n_kmers && !kmers)) return fail(CID_ERR_INVALID, "null argument");
     Query q;
-    q.h_kmers = kmers; q.n = n_kmers; q.k = stripes[0]->k;
+    q.h_kmers = kmers; q.dev.n = n_kmers; q.dev.k = stripes[0]->k;
     return stripes_search_perfect(g, stripes, q, and_words_le, any_row_missing);
 }
 

@@ -34,8 +34,60 @@ uint32_t index_n_hash(const cid_index *ix);
 uint32_t index_m_size(const cid_index *ix);
 const uint64_t *index_matrix(const cid_index *ix);
 
-// Bloom insert of 2-bit codes already on the device into one colour (build.rs:62-66 with the k-mer map on the GPU)
-int index_insert_codes(cid_index *ix, const uint64_t *d_codes, size_t n, uint32_t k, uint32_t colour);
+// contiguous, balanced partition (the same rule as colorid_amd/dist.py shard_bounds): sizes differ by at most one
+inline void shard_bounds(size_t n_units, int rank, int world, size_t *lo, size_t *hi) {
+    const size_t base = n_units / (size_t)world, rem = n_units % (size_t)world;
+    *lo = (size_t)rank * base + ((size_t)rank < rem ? (size_t)rank : rem);
+    *hi = *lo + base + ((size_t)rank < rem ? 1 : 0);
+}
+
+// the same with every boundary on a multiple of 64 units (byte-string k-mers: a shard's first k-mer must sit on a 16-byte boundary)
+inline void shard_bounds64(size_t n_units, int rank, int world, size_t *lo, size_t *hi) {
+    const size_t blocks = (n_units + 63) / 64;
+    shard_bounds(blocks, rank, world, lo, hi);
+    *lo *= 64; *hi *= 64;
+    if (*lo > n_units) *lo = n_units;
+    if (*hi > n_units) *hi = n_units;
+}
+
+// k-mers on a device, in one of their two encodings: byte strings (any k; the only form for k > 32) or 2-bit codes (k <= 32).
+// A view: it owns nothing.
+struct DevKeys {
+    const uint8_t *ascii = nullptr;     // n x k bytes, 16-byte aligned
+    const uint64_t *codes = nullptr;    // n codes; exactly one of the two is set when n > 0
+    const uint32_t *counts = nullptr;   // multiplicities, or NULL
+    size_t n = 0;
+    uint32_t k = 0;
+    cid_ctx *ctx = nullptr;             // whose memory this is; NULL for a caller's device pointers
+    size_t unit() const { return ascii ? k : 8; }   // bytes per key
+    const uint8_t *bytes() const { return ascii ? ascii : reinterpret_cast<const uint8_t *>(codes); }
+    DevKeys slice(size_t lo, size_t hi) const {     // keys [lo, hi)
+        DevKeys s = *this;
+        if (ascii) s.ascii += lo * k;
+        if (codes) s.codes += lo;
+        if (counts) s.counts += lo;
+        s.n = hi - lo;
+        return s;
+    }
+    // rank's share of `world` contiguous ones; byte strings in blocks of 64 keys: a shard's first byte must sit on a 16-byte boundary
+    void shard(int rank, int world, size_t *lo, size_t *hi) const {
+        if (ascii) shard_bounds64(n, rank, world, lo, hi); else shard_bounds(n, rank, world, lo, hi);
+    }
+};
+
+// a finalized set's device arrays (codes ascending unless reordered, byte strings for k > 32; counts u32), keys->ctx the ctx they live in
+int kmerset_keys(const cid_kmerset *ks, DevKeys *keys);
+// Bloom insert of k-mers already on the device into one colour (build.rs:62-66 with the k-mer map on the GPU); waits for the stream
+int index_insert_keys(cid_index *ix, const DevKeys &keys, uint32_t colour);
+// a5 launch on device-resident inputs/outputs (zeroes the counters first); asynchronous on the ctx stream
+int search_count_launch(cid_ctx *c, const cid_index *ix, const DevKeys &keys, uint64_t *d_hits, uint64_t *d_n_unique, uint64_t *d_sum_unique_freq,
+                        uint32_t *d_unique_colour, bool zero_counters = true);
+// a4 launch: d_and (rs words) and d_missing (int) are preset here; asynchronous
+int search_perfect_launch(cid_ctx *c, const cid_index *ix, const DevKeys &keys, uint64_t *d_and, int *d_missing);
+// a5 / a4 on k-mers that are already on the device (keys.k must be the index's); outputs go to HOST buffers
+int search_count_keys(cid_ctx *c, const cid_index *ix, const DevKeys &keys, uint64_t *hits, uint64_t *n_unique, uint64_t *sum_unique_freq,
+                      uint32_t *unique_colour);
+int search_perfect_keys(cid_ctx *c, const cid_index *ix, const DevKeys &keys, uint32_t *and_words_le, int *any_row_missing);
 
 // read_id over colour stripes (ReadIdParams::zero_acc ...): which pass this launch is, and where its results go; all zero = a whole index
 struct StripePass {
@@ -69,12 +121,6 @@ int readid_long_sorted(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, 
                        size_t n_reads, uint32_t stride_d, uint32_t start_sample, const uint8_t *route, bool clear_wide, uint32_t *d_report,
                        uint32_t *d_n_kmers, uint8_t *d_status, const StripePass &sp = StripePass(), bool merge_status = false);
 
-// a5 / a4 on k-mers that are already on the device as 2-bit codes (k <= 32); outputs go to HOST buffers
-int search_count_codes(cid_ctx *c, const cid_index *ix, const uint64_t *d_codes, const uint32_t *d_counts, size_t n, uint32_t k,
-                       uint64_t *hits, uint64_t *n_unique, uint64_t *sum_unique_freq, uint32_t *unique_colour);
-int search_perfect_codes(cid_ctx *c, const cid_index *ix, const uint64_t *d_codes, size_t n, uint32_t k, uint32_t *and_words_le,
-                         int *any_row_missing);
-
 // rocPRIM behind plain calls (cid_kmerset_cold.hip — the one translation unit that includes it; its code object of some thousand kernels is
 // loaded when the first of these is called): stable LSD radix sorts on bits [b0, b1), a run-length count of sorted keys.  Asynchronous on `st`.
 int cold_sort_keys_u64(cid_ctx *c, hipStream_t st, const uint64_t *in, uint64_t *out, size_t n, unsigned b0, unsigned b1);
@@ -84,8 +130,6 @@ int cold_sort_pairs_u32_u64(cid_ctx *c, hipStream_t st, const uint32_t *kin, uin
                             unsigned b1);
 int cold_run_length_u64(cid_ctx *c, hipStream_t st, const uint64_t *sorted, size_t n, uint64_t *uniq, uint32_t *runs, uint64_t *d_n_runs);
 
-// a finalized set's device arrays (codes ascending unless reordered; counts u32) and the ctx they live in
-int kmerset_view(const cid_kmerset *ks, cid_ctx **ctx, const uint64_t **codes, const uint32_t **counts, uint64_t *n, uint32_t *k);
 // replace a finalized 2-bit-code set's contents by the merge (sort by code, add counts of equal codes) of `total` pairs on its device
 int kmerset_assign_merged(cid_kmerset *ks, const uint64_t *d_codes_in, const uint32_t *d_counts_in, size_t total);
 // d_modes[c] = the most frequent multiplicity among the k-mers whose unique colour is c (ties -> the smallest; 0 = none); asynchronous
@@ -101,13 +145,6 @@ int unique_freq_modes_begin(cid_ctx *c, const uint32_t *d_uc, const uint32_t *d_
 int unique_freq_modes_finish(cid_ctx *c, ModeWork *w, unsigned long long n_ovf, uint64_t *d_modes);
 // sorted (colour << 32 | multiplicity) keys and their k-mer counts over the k-mers with a unique colour (host vectors; synchronous)
 int unique_freq_hist(cid_ctx *c, const uint32_t *d_uc, const uint32_t *d_freq, uint64_t n, std::vector<uint64_t> &keys, std::vector<uint32_t> &counts);
-int kmerset_view_ascii(const cid_kmerset *ks, cid_ctx **ctx, const uint8_t **ascii, const uint32_t **counts, uint64_t *n, uint32_t *k);   // k > 32 sets
-
-// the same three for sets of byte-string k-mers (k > 32): d_ascii = n x k bytes on the device
-int index_insert_ascii(cid_index *ix, const uint8_t *d_ascii, size_t n, uint32_t k, uint32_t colour);
-int search_count_ascii(cid_ctx *c, const cid_index *ix, const uint8_t *d_ascii, const uint32_t *d_counts, size_t n, uint32_t k,
-                       uint64_t *hits, uint64_t *n_unique, uint64_t *sum_unique_freq, uint32_t *unique_colour);
-int search_perfect_ascii(cid_ctx *c, const cid_index *ix, const uint8_t *d_ascii, size_t n, uint32_t k, uint32_t *and_words_le, int *any_row_missing);
 
 // the non-zero rows of [row_begin, row_begin + n_rows) as .bxi row records in a host buffer (cid_kmerset.hip)
 int index_get_records(cid_ctx *c, const cid_index *ix, uint64_t row_begin, uint64_t n_rows, uint8_t *records, uint64_t *n_records);

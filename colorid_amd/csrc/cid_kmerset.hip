@@ -66,11 +66,10 @@ cid_ctx *kmerset_ctx(const cid_kmerset *ks) { return ks->ctx; }
 
 
 namespace cid {
-int kmerset_view(const cid_kmerset *ks, cid_ctx **ctx, const uint64_t **codes, const uint32_t **counts, uint64_t *n, uint32_t *k) {
+int kmerset_keys(const cid_kmerset *ks, DevKeys *keys) {
     if (!ks) return fail(CID_ERR_INVALID, "null set");
     if (!ks->finalized) return fail(CID_ERR_STATE, "k-mer set not finalized");
-    if (ks->general) return fail(CID_ERR_UNSUPPORTED, "a k_size > 32 set holds byte strings: shard it with the host-pointer group calls");
-    *ctx = ks->ctx; *codes = ks->codes; *counts = ks->counts; *n = ks->n; *k = ks->k;
+    *keys = DevKeys{ks->general ? ks->ascii : nullptr, ks->general ? nullptr : ks->codes, ks->counts, ks->n, ks->k, ks->ctx};
     return CID_OK;
 }
 }  // namespace cid
@@ -443,16 +442,6 @@ hipError_t warm_kmerset() {   // see warm_readid (cid_readid.hip): this file's k
     return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_seq_windows));
 }
 
-}  // namespace cid
-
-namespace cid {
-int kmerset_view_ascii(const cid_kmerset *ks, cid_ctx **ctx, const uint8_t **ascii, const uint32_t **counts, uint64_t *n, uint32_t *k) {
-    if (!ks) return fail(CID_ERR_INVALID, "null set");
-    if (!ks->finalized) return fail(CID_ERR_STATE, "k-mer set not finalized");
-    if (!ks->general) return fail(CID_ERR_INVALID, "not a byte-string k-mer set");
-    *ctx = ks->ctx; *ascii = ks->ascii; *counts = ks->counts; *n = ks->n; *k = ks->k;
-    return CID_OK;
-}
 }  // namespace cid
 
 namespace {
@@ -845,18 +834,16 @@ void cid_kmerset_destroy(cid_kmerset *ks) {
 }
 
 int cid_index_insert_kmerset(cid_index *ix, const cid_kmerset *ks, uint32_t colour) {
-    if (!ks) return fail(CID_ERR_INVALID, "null set");
-    if (!ks->finalized) return fail(CID_ERR_STATE, "k-mer set not finalized");
-    if (ks->general) return cid::index_insert_ascii(ix, ks->ascii, ks->n, ks->k, colour);
-    return cid::index_insert_codes(ix, ks->codes, ks->n, ks->k, colour);
+    cid::DevKeys keys;
+    const int rc = cid::kmerset_keys(ks, &keys);
+    return rc ? rc : cid::index_insert_keys(ix, keys, colour);
 }
 
 int cid_search_count_set(cid_ctx *c, const cid_index *ix, const cid_kmerset *ks, uint64_t *hits, uint64_t *n_unique,
                          uint64_t *sum_unique_freq, uint32_t *unique_colour) {
-    if (!ks) return fail(CID_ERR_INVALID, "null set");
-    if (!ks->finalized) return fail(CID_ERR_STATE, "k-mer set not finalized");
-    if (ks->general) return cid::search_count_ascii(c, ix, ks->ascii, ks->counts, ks->n, ks->k, hits, n_unique, sum_unique_freq, unique_colour);
-    return cid::search_count_codes(c, ix, ks->codes, ks->counts, ks->n, ks->k, hits, n_unique, sum_unique_freq, unique_colour);
+    cid::DevKeys keys;
+    const int rc = cid::kmerset_keys(ks, &keys);
+    return rc ? rc : cid::search_count_keys(c, ix, keys, hits, n_unique, sum_unique_freq, unique_colour);
 }
 
 
@@ -870,16 +857,15 @@ extern "C" {
 int cid_search_count_set_report(cid_ctx *c, const cid_index *ix, const cid_kmerset *ks, uint64_t *hits, uint64_t *n_unique,
                                 uint64_t *sum_unique_freq, uint64_t *mode_unique_freq) {
     if (!ks || !hits || !n_unique || !sum_unique_freq || !mode_unique_freq) return fail(CID_ERR_INVALID, "null argument");
-    if (!ks->finalized) return fail(CID_ERR_STATE, "k-mer set not finalized");
+    cid::DevKeys keys;
+    int rc = cid::kmerset_keys(ks, &keys);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(cid::ctx_device(c)));
     const uint32_t C = cid::index_n_colors(ix);
     DevBuf<uint32_t> uc(ks->ctx);
     DevBuf<uint64_t> out(ks->ctx);
-    int rc;
     if ((rc = uc.alloc(ks->n)) || (rc = out.alloc((size_t)4 * C + 2))) return rc;
-    if (ks->general) rc = cid_search_count_dev(c, ix, ks->ascii, ks->counts, ks->n, out.p, out.p + C, out.p + 2 * C, uc.p);
-    else rc = cid_search_count_codes_dev(c, ix, ks->codes, ks->counts, ks->n, out.p, out.p + C, out.p + 2 * C, uc.p);
-    if (rc) return rc;
+    if ((rc = cid::search_count_launch(c, ix, keys, out.p, out.p + C, out.p + 2 * C, uc.p))) return rc;
     // ONE copy, ONE wait: the three counter arrays, the modes as they stand and the number of multiplicities the mode table did not hold
     // come back together; only when there are such k-mers (deep coverage) a second step counts them in.  (Round 4: two waits, four copies.)
     cid::ModeWork w;
@@ -908,10 +894,9 @@ int cid_search_count_set_report(cid_ctx *c, const cid_index *ix, const cid_kmers
 }
 
 int cid_search_perfect_set(cid_ctx *c, const cid_index *ix, const cid_kmerset *ks, uint32_t *and_words_le, int *any_row_missing) {
-    if (!ks) return fail(CID_ERR_INVALID, "null set");
-    if (!ks->finalized) return fail(CID_ERR_STATE, "k-mer set not finalized");
-    if (ks->general) return cid::search_perfect_ascii(c, ix, ks->ascii, ks->n, ks->k, and_words_le, any_row_missing);
-    return cid::search_perfect_codes(c, ix, ks->codes, ks->n, ks->k, and_words_le, any_row_missing);
+    cid::DevKeys keys;
+    const int rc = cid::kmerset_keys(ks, &keys);
+    return rc ? rc : cid::search_perfect_keys(c, ix, keys, and_words_le, any_row_missing);
 }
 
 }  // extern "C"

@@ -92,13 +92,6 @@ int slot_reserve(cid_ctx *c, int s, size_t bytes, void **out);
 // copied through this arena.  NULL when the request is larger than kPinMax: the caller then lets the runtime handle its memory.
 constexpr size_t kPinMax = 64u << 20;
 uint8_t *pin_reserve(cid_ctx *c, size_t bytes, size_t cap = kPinMax);
-// a5 launch on device-resident inputs/outputs (zeroes the counters first); asynchronous on the ctx stream
-int search_count_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_codes, const uint32_t *d_freq,
-                        size_t n_kmers, uint64_t *d_hits, uint64_t *d_n_unique, uint64_t *d_sum_unique_freq, uint32_t *d_unique_colour,
-                        bool zero_counters = true);
-// a4 launch: d_and (rs words) and d_missing (int) are preset here; asynchronous
-int search_perfect_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_codes, size_t n_kmers, uint64_t *d_and,
-                          int *d_missing);
 int search_count_host_input(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint32_t *freq, size_t n_kmers, bool want_unique,
                             uint32_t *unique_colour, uint64_t **d_counters);
 int check_ready(const cid_ctx *c, const cid_index *ix);

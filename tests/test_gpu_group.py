@@ -85,6 +85,40 @@ def test_group_search_equals_single_rank_and_oracle(orc, hip_ctx, devices, n_col
     g.close()
 
 
+@pytest.mark.parametrize("k,n_kmers", [(40, 10), (31, 2)])
+def test_group_set_search_with_empty_shards(orc, k, n_kmers):
+    """A device-resident set smaller than what the ranks share out.  Byte strings (k > 32) are dealt in blocks of 64 keys, so that
+    a shard starts on a 16-byte boundary: ten of them all go to rank 0 and ranks 1 and 2 get nothing.  Two 2-bit codes over three
+    ranks leave rank 2 empty.  Counts and AND words must equal the single-rank search of the same set and the oracle."""
+    import colorid_amd
+    rng = np.random.default_rng(k)
+    oix = random_index(orc, rng, 4001, 4, k, 200, density=0.15, zero_row_frac=0.05)
+    g = colorid_amd.Group([0, 0, 0])
+    ks = colorid_amd.KmerSet(g.ctxs[0], k)
+    ks.add_seqs([km.tobytes() for km in random_kmers(rng, n_kmers, k)], 0)   # one window per sequence
+    ks.finalize()
+    km, cnt = ks.download()
+    assert len(km) == n_kmers
+    for key in km:                                                           # present in two colours: the AND is not all-zero
+        oix.insert(1, key.tobytes())
+        oix.insert(199, key.tobytes())
+    hx = _group_index(g, oix)
+    single = ks.search_count(hx)
+    multi = g.search_count_set(ks)
+    want = oix.search_count(km, cnt.astype(np.uint64))
+    assert all(np.array_equal(a, b) for a, b in zip(single, multi))
+    assert all(np.array_equal(a, b) for a, b in zip(want, multi))
+    assert multi[0][1] == n_kmers and multi[0][199] == n_kmers
+    sw, sm = ks.search_perfect(hx)
+    mw, mm = g.search_perfect_set(ks)
+    pw, pm = oix.search_perfect(km)
+    assert sm == mm == pm == 0
+    assert np.array_equal(sw, mw) and np.array_equal(pw, mw)
+    assert (int(mw[0]) >> 1) & 1 and (int(mw[199 // 32]) >> (199 % 32)) & 1
+    ks.close()
+    g.close()
+
+
 @pytest.mark.parametrize("devices", [[0, 0], [0, 0, 0, 0]])
 def test_group_readid_rows_in_input_order(orc, devices, tmp_path):
     import colorid_amd
