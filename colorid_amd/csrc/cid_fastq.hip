@@ -296,6 +296,9 @@ struct cid_fastq {
     // text (K bytes), the bound for its members (K + 31 a member) and bgzf_deflate_launch's slots (65 312 a member): ~3 K, so up to
     // ~0.75 GiB more when a whole 256 MiB stretch of one file is kept.
     bool keep_steps = false;
+    // cid_fastq_filter_matches: the kept text goes through the LZ77 coder (bgzf_deflate_launch's `matches`), which takes its tokens from
+    // the block cache too: 261 120 bytes per workgroup launched, min(members, 6 x CUs) of them (383 MiB at most on 256 CUs).
+    bool filter_matches = false;
     struct Gen {
         bool valid = false;
         uint64_t n = 0;
@@ -848,6 +851,13 @@ int cid_fastq_keep_steps(cid_fastq *fq, int on) {
     return CID_OK;
 }
 
+int cid_fastq_filter_matches(cid_fastq *fq, int on) {
+    if (!fq) return fail(CID_ERR_INVALID, "null argument");
+    if (fq->infl.active) return fail(CID_ERR_STATE, "cid_fastq_filter_matches: a step is in flight");
+    fq->filter_matches = on != 0;
+    return CID_OK;
+}
+
 int cid_fastq_filter(cid_fastq *fq, const uint8_t *keep, int file, uint8_t *members, size_t members_cap, size_t *members_bytes, size_t *n_members,
                      uint64_t *n_kept) {
     if (!fq || !members_bytes || !n_members || !n_kept || file < 0 || file >= fq->n_files) return fail(CID_ERR_INVALID, "bad argument");
@@ -882,7 +892,7 @@ int cid_fastq_filter(cid_fastq *fq, const uint8_t *keep, int file, uint8_t *memb
     if (grid > 16384) grid = 16384;
     hipLaunchKernelGGL(cid::k_fq_filter_copy, dim3(grid), dim3(256), 0, st, F, (const uint8_t *)d_keep.p, n, (const uint64_t *)off.p, d_text.p);
     HIP_TRY(hipGetLastError());
-    if ((rc = cid::bgzf_deflate_launch(c, st, d_text.p, (size_t)text_bytes, d_out.p, d_len.p, d_total.p))) { (void)hipStreamSynchronize(st); return rc; }
+    if ((rc = cid::bgzf_deflate_launch(c, st, d_text.p, (size_t)text_bytes, d_out.p, d_len.p, d_total.p, fq->filter_matches))) { (void)hipStreamSynchronize(st); return rc; }
     uint64_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, d_total.p, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));

@@ -175,7 +175,8 @@ hipError_t warm_fastq();
 hipError_t warm_deflate();
 // the text at d_text (16-byte aligned) as block-gzip members back to back at d_members (cid_bgzf_deflate_bound bytes of room), their lengths and
 // *d_total = their bytes; queued on `stream`, which must be the stream the ctx's block cache is ordered on (c->stream)
-int bgzf_deflate_launch(cid_ctx *c, hipStream_t stream, const uint8_t *d_text, size_t text_bytes, uint8_t *d_members, uint32_t *d_member_len, uint64_t *d_total);
+int bgzf_deflate_launch(cid_ctx *c, hipStream_t stream, const uint8_t *d_text, size_t text_bytes, uint8_t *d_members, uint32_t *d_member_len, uint64_t *d_total,
+                        bool matches = false);   // matches: with LZ77 matches (cid_bgzf_deflate_lz)
 hipError_t ctx_side_streams(cid_ctx *c, hipStream_t out[4]);   // created on first use; any thread
 
 }  // namespace cid

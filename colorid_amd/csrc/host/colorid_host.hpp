@@ -395,7 +395,7 @@ int device_fastq_host_threads(size_t n_files);
 // read_id / batch_id --taxon TAXON [--exclude] (the reference's read_filter, src/read_filter.rs, fused into the classifying pass): the
 // reads whose label — column 2 of their _reads.txt row — contains TAXON (--exclude: does not contain it) are written by the device
 // front end as PREFIX_TAXON.fq.gz / PREFIX_TAXON_R1.fq.gz + _R2 (cid_fastq_filter).  Set before the streamers run; on == false: none.
-struct TaxonFilter { bool on = false; std::string taxon; bool exclude = false; };
+struct TaxonFilter { bool on = false; std::string taxon; bool exclude = false; bool gz_matches = false; };   // gz_matches: --gz-matches, members with LZ77 matches
 void set_taxon_filter(const TaxonFilter &f);
 void per_read_stream_se(cid_ctx *, const std::vector<std::string> &fq, const Bigsi &b, size_t d, double fp_correct, size_t batch,
                         const std::string &prefix, uint8_t qual_offset, size_t start_sample);   // read_id_mt_pe.rs:835-951

@@ -536,7 +536,8 @@ struct FilteredOutput {
             fprintf(stderr, "Excluded %llu read pairs  with classification containing '%s' from output files\n", (unsigned long long)n_kept, g_taxon.taxon.c_str());
         else
             fprintf(stderr, "Wrote %llu read-pairs with classification containing '%s' to output files\n", (unsigned long long)n_kept, g_taxon.taxon.c_str());
-        if (g_timing) fprintf(stderr, "timing: --taxon: %.0f ms in cid_fastq_filter (waiting for the classifier in flight included) and writing the members\n", ms);
+        if (g_timing) fprintf(stderr, "timing: --taxon: %.0f ms in cid_fastq_filter (waiting for the classifier in flight included) and writing the members; coder: %s\n", ms,
+                              g_taxon.gz_matches ? "LZ77 matches (--gz-matches)" : "literals only");
     }
 };
 
@@ -548,6 +549,7 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
     FilteredOutput filtered;
     if (g_taxon.on) {
         CID_TRY(cid_fastq_keep_steps(fr, 1));
+        if (g_taxon.gz_matches) CID_TRY(cid_fastq_filter_matches(fr, 1));
         filtered.open(prefix, n_files, fq);
     }
     classifier.ids_stay_with_counted(true);

@@ -661,15 +661,17 @@ bool wants_device_front_end(const Args &a, const std::vector<std::string> &fq) {
     return ends_with(fq[0], ".gz") && one_gpu_run(a) && read_id_mt_pe::device_fastq_wanted(fq, fq.size() > 1 ? 2 : 1);
 }
 
-// --taxon TAXON [--exclude] (read_id, batch_id): the reference's read_filter fused into the classifying pass — the kept reads are cut and
-// compressed on the device (cid_fastq_filter), so only block-gzip input on one GPU is served; everything else is refused here, before the
-// GPU context is made.
+// --taxon TAXON [--exclude] [--gz-matches] (read_id, batch_id): the reference's read_filter fused into the classifying pass — the kept reads
+// are cut and compressed on the device (cid_fastq_filter; --gz-matches: with LZ77 matches, cid_fastq_filter_matches), so only block-gzip
+// input on one GPU is served; everything else is refused here, before the GPU context is made.
 read_id_mt_pe::TaxonFilter taxon_filter(const Args &a) {
     read_id_mt_pe::TaxonFilter f;
     const bool exclude = a.flags.count("exclude") != 0;
+    const bool matches = a.flags.count("gz-matches") != 0;
     if (exclude && !a.has("taxon")) die("error: --exclude needs --taxon TAXON (the classification to leave out)");
+    if (matches && !a.has("taxon")) die("error: --gz-matches needs --taxon TAXON (it chooses how the kept reads are compressed)");
     if (!a.has("taxon")) return f;
-    f.on = true; f.taxon = a.one("taxon"); f.exclude = exclude;
+    f.on = true; f.taxon = a.one("taxon"); f.exclude = exclude; f.gz_matches = matches;
     return f;
 }
 void require_filter_route(const Args &a, const std::vector<std::string> &fq) {
@@ -715,7 +717,8 @@ int cmd_read_id(int argc, char **argv) {
                                                      {'t', "threads", true, false}, {'n', "prefix", true, false}, {'d', "down_sample", true, false},
                                                      {'H', "high_mem_load", false, false}, {'p', "fp_correct", true, false},
                                                      {'Q', "quality", true, false}, {'B', "bitvector_sample", true, false},
-                                                     {0, "taxon", true, false}, {0, "exclude", false, false}}));
+                                                     {0, "taxon", true, false}, {0, "exclude", false, false},
+                                                     {0, "gz-matches", false, false}}));
     for (const char *req : {"bigsi", "query", "prefix"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const std::vector<std::string> fq = a.values.at("query");
@@ -753,7 +756,8 @@ int cmd_batch_id(int argc, char **argv) {
                                                      {'c', "batch", true, false}, {'t', "threads", true, false}, {'d', "down_sample", true, false},
                                                      {'H', "high_mem_load", false, false}, {'p', "fp_correct", true, false},
                                                      {'Q', "quality", true, false}, {'B', "bitvector_sample", true, false},
-                                                     {0, "taxon", true, false}, {0, "exclude", false, false}}));
+                                                     {0, "taxon", true, false}, {0, "exclude", false, false},
+                                                     {0, "gz-matches", false, false}}));
     for (const char *req : {"bigsi", "query", "tag"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const ClassifyFlags flags = classify_flags(a);

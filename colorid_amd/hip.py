@@ -691,15 +691,17 @@ class GroupKmerSet:
                 self.g._ksets.remove(self)
 
 
-def bgzf_deflate(ctx, text: bytes):
-    """cid_bgzf_deflate: `text` as block-gzip members written on the GPU -> (members [bytes], member_len [uint32 per member])"""
+def bgzf_deflate(ctx, text: bytes, matches=False):
+    """cid_bgzf_deflate (matches: cid_bgzf_deflate_lz, members with LZ77 matches): `text` as block-gzip members written on the GPU ->
+    (members [bytes], member_len [uint32 per member])"""
     lib = ctx.lib
     cap = lib.cid_bgzf_deflate_bound(len(text))
     buf = np.frombuffer(text, np.uint8) if len(text) else np.zeros(1, np.uint8)
     out = np.zeros(max(cap, 1), np.uint8)
     ln = np.zeros(max((len(text) + 65279) // 65280, 1), np.uint32)
     nb, nm = C.c_size_t(0), C.c_size_t(0)
-    check(lib.cid_bgzf_deflate(ctx.h, _p(buf), len(text), _p(out), cap, C.byref(nb), _p(ln), C.byref(nm)))
+    call = lib.cid_bgzf_deflate_lz if matches else lib.cid_bgzf_deflate
+    check(call(ctx.h, _p(buf), len(text), _p(out), cap, C.byref(nb), _p(ln), C.byref(nm)))
     return out[:nb.value].tobytes(), ln[:nm.value].copy()
 
 
@@ -762,6 +764,10 @@ class FastqReader:
     def keep_steps(self, on=True):
         """from the next classify_end on, an ended step stays on the device until the next one ends (what filter() reads)"""
         check(self.lib.cid_fastq_keep_steps(self.h, 1 if on else 0))
+
+    def filter_matches(self, on=True):
+        """filter() writes members with LZ77 matches (cid_bgzf_deflate_lz's) instead of literal-only ones"""
+        check(self.lib.cid_fastq_filter_matches(self.h, 1 if on else 0))
 
     def filter(self, keep, file=0):
         """the kept records (keep[r] != 0) of file `file` of the last ended step, `header\\nsequence\\n+\\nquality\\n` each, as

@@ -523,6 +523,17 @@ int cid_bgzf_deflate(cid_ctx *, const uint8_t *text, size_t text_bytes, uint8_t 
                      uint32_t *member_len, size_t *n_members);
 int cid_bgzf_deflate_dev(cid_ctx *, const uint8_t *text, size_t text_bytes, uint8_t *members, size_t members_cap, uint64_t *members_bytes,
                          uint32_t *member_len, size_t *n_members);
+/* The same two calls with LZ77 matches (read_id --taxon --gz-matches; opt-in until it has been timed): same arguments, bound, errors and
+ * stream rules.  A wave finds the matches of its piece inside the piece (length 4 to 258, distance up to 32 768, every candidate compared
+ * byte by byte; a member still inflates on its own) and codes literals, lengths and distances in one dynamic-Huffman block.  A member
+ * takes that form only when it is strictly shorter than the member cid_bgzf_deflate writes for the piece and is that member byte for
+ * byte otherwise: no member is longer than its text + 31 bytes, cid_bgzf_deflate_bound holds, and the bytes are a function of the text
+ * alone.  Scratch from the ctx's block cache while the call runs: what cid_bgzf_deflate takes, and 261 120 bytes of tokens per
+ * workgroup launched — min(members, 6 x CUs) of them. */
+int cid_bgzf_deflate_lz(cid_ctx *, const uint8_t *text, size_t text_bytes, uint8_t *members, size_t members_cap, size_t *members_bytes,
+                        uint32_t *member_len, size_t *n_members);
+int cid_bgzf_deflate_lz_dev(cid_ctx *, const uint8_t *text, size_t text_bytes, uint8_t *members, size_t members_cap, uint64_t *members_bytes,
+                            uint32_t *member_len, size_t *n_members);
 /* ---- the FASTQ front end of read_id on the device: what the reference does per read before its search — inflate
  *      (src/read_id_mt_pe.rs:848-856), take the lines four at a time (:862-879 / pairs :927-975: header, sequence, '+', quality; lines()
  *      strips "\n" and "\r\n"; an unterminated last line counts), seq::qual_mask (src/seq.rs:36-56) and the (id, [seq(, mate)]) batch
@@ -584,6 +595,11 @@ CID_CORE int cid_fastq_fetch(cid_fastq *, uint32_t *n_kmers, uint8_t *status, ui
  *                On top of that, while it runs, a filter call takes from the ctx's block cache, for K bytes of kept text: K for the
  *                kept text, K + 31 per member for the gathered members and 65 312 per member (K / 65 280 members) for the slots
  *                the members are coded into, ~3 K in all plus ~10 bytes per read of the step; given back before it returns.
+ *                With filter_matches on, also the LZ77 coder's tokens: 261 120 bytes per workgroup launched, min(members, 6 x CUs)
+ *                of them (383 MiB at most on 256 CUs).
+ *   filter_matches   on: filter sends the kept text through cid_bgzf_deflate_lz_dev (members with LZ77 matches: smaller files, a
+ *                slower launch); off (the default): through cid_bgzf_deflate_dev, today's bytes.  A reader setting like keep_steps:
+ *                CID_ERR_STATE while a step is in flight.
  *   filter       keep[n_reads] (0 / 1, the step's reads in order); for every kept read the record of file `file` is written as
  *                `header\nsequence\n+\nquality\n` (read_filter.rs:89-105: the lines as lines() gives them — "\r\n" stripped, an
  *                unterminated last line counts —, the sequence as the input has it, not quality-masked, whatever followed the '+'
@@ -592,6 +608,7 @@ CID_CORE int cid_fastq_fetch(cid_fastq *, uint32_t *n_kmers, uint8_t *status, ui
  *                CID_ERR_STATE: keep_steps is off or no step has ended yet; CID_ERR_INVALID: members_cap too small — *members_bytes
  *                then says how much room the same call needs. */
 int cid_fastq_keep_steps(cid_fastq *, int on);
+int cid_fastq_filter_matches(cid_fastq *, int on);
 int cid_fastq_filter(cid_fastq *, const uint8_t *keep, int file, uint8_t *members, size_t members_cap, size_t *members_bytes, size_t *n_members,
                      uint64_t *n_kept);
 CID_CORE void cid_fastq_destroy(cid_fastq *);

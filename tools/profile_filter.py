@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Evidence for `read_id --taxon` on 1 M x 150 bp reads with Illumina-style headers and 41 skewed quality letters:
 
-  (a) the compressor alone: tools/exp_deflate.py (HIP events around cid_bgzf_deflate_dev, the members' size, zlib level 6 over the same
-      65 280-byte pieces on 16 host threads) and, from a run of its own under rocprofv3 --kernel-trace --stats, the time per kernel;
+  (a) the compressor alone: tools/exp_deflate.py (HIP events around cid_bgzf_deflate_dev and cid_bgzf_deflate_lz_dev, the members' size,
+      zlib level 1 and level 6 over the same 65 280-byte pieces on 16 host threads; the same once more with 4 binned quality letters) and,
+      from a run of its own under rocprofv3 --kernel-trace --stats, the time per kernel;
   (b) the command line: an index of 16 random 1 Mb genomes (m = 5 M, n = 4, k = 31), the reads drawn from them with 1 % errors and
-      written as block gzip; `read_id` without the flags, `read_id --taxon genomeA` (8 of the 16 genomes: about half the reads kept) and
+      written as block gzip; `read_id` without the flags, `read_id --taxon genomeA` (8 of the 16 genomes: about half the reads kept), the
+      same with `--gz-matches` and
       `read_id` without the flags from PARENT_BIN (the parent commit's binary), alternating, REPS times each after one warm-up: the
       whole-process wall clock and the classification phase (COLORID_TIMING), then one traced --taxon run for the filter's kernels.
 
@@ -86,19 +88,27 @@ def main():
     # ---- (a) the compressor alone
     exp = [sys.executable, os.path.join(ROOT, "tools", "exp_deflate.py")]
     p, _ = run(exp, env=dict(os.environ, EXP_READS=str(R)), limit=900)
-    print(p.stdout.strip().splitlines()[-1], file=sys.stderr, flush=True)
-    dj = json.loads(p.stdout.strip().splitlines()[-1])
+    djs = [json.loads(ln) for ln in p.stdout.strip().splitlines() if ln.startswith("{")]
     with open(os.path.join(out_dir, "filter_deflate.json"), "w") as fh:
-        fh.write(json.dumps(dj) + "\n")
+        for dj in djs:
+            print(json.dumps(dj), file=sys.stderr, flush=True)
+            fh.write(json.dumps(dj) + "\n")
     os.environ["EXP_READS"] = str(R)
     stats = kernel_stats(out_dir, "filter_deflate", exp)
-    later = dj["device_ms_later"]
-    lines += ["## (a) `cid_bgzf_deflate_dev` on the reads' text, against zlib level 6", "",
-              f"text {dj['text_MB']} MB in {dj['members']} members; HIP events around the call, text and members resident: first call "
-              f"{dj['device_ms_first']} ms, then {min(later)}–{max(later)} ms ({dj['text_MB'] / 1e3 / (min(later) / 1e3):.0f} GB/s of text at the best); "
-              f"output {dj['device_out_MB']} MB = {dj['device_ratio']} x.",
-              f"zlib level 6 over the same pieces on {dj['zlib6_threads']} host threads: {dj['zlib6_ms']} ms, {dj['zlib6_out_MB']} MB = {dj['zlib6_ratio']} x.",
-              "", "Per kernel (one `rocprofv3 --kernel-trace --stats` run of the same script: six calls):", "",
+    lines += ["## (a) the compressor on the reads' text: literals only, with matches, zlib level 1 and level 6", ""]
+    for dj in djs:
+        lines += [f"Qualities: {dj['qualities']}; text {dj['text_MB']} MB in {dj['members']} members; HIP events around the call, text and members resident.", "",
+                  "| coder | time | output | ratio |", "|---|---|---|---|"]
+        for key, label in (("literals", "`cid_bgzf_deflate_dev` (literals only)"), ("matches", "`cid_bgzf_deflate_lz_dev` (LZ77 matches)")):
+            later = dj[f"{key}_ms_later"]
+            lines.append(f"| {label} | first call {dj[f'{key}_ms_first']} ms, then {min(later)}–{max(later)} ms "
+                         f"({dj['text_MB'] / 1e3 / (min(later) / 1e3):.0f} GB/s of text at the best) | {dj[f'{key}_out_MB']} MB | {dj[f'{key}_ratio']} x |")
+        for level in (1, 6):
+            lines.append(f"| zlib level {level}, {dj[f'zlib{level}_threads']} host threads | {dj[f'zlib{level}_ms']} ms | {dj[f'zlib{level}_out_MB']} MB | "
+                         f"{dj[f'zlib{level}_ratio']} x |")
+        lines += ["", f"The matches achieve {100 * dj['share_of_zlib1_saving']:.0f} % of zlib level 1's saving over the literal-only members and "
+                      f"{100 * dj['share_of_zlib6_saving']:.0f} % of level 6's.", ""]
+    lines += ["Per kernel (one `rocprofv3 --kernel-trace --stats` run of the same script: six calls of either coder per text):", "",
               "| kernel | calls | total ms | ms per call |", "|---|---|---|---|"]
     for name, r in stats.items():
         if any(k in name for k in ("k_bgzf_deflate", "k_bgzf_gather", "scan")):
@@ -112,7 +122,8 @@ def main():
         env = dict(os.environ, COLORID_TIMING="1")
         q = ["-b", str(work / "idx.bxi"), "-q", str(work / "reads.fastq.gz")]
         cmds = {"plain": [BIN, "read_id", *q, "-n", str(work / "plain")],
-                "taxon": [BIN, "read_id", *q, "-n", str(work / "taxon"), "--taxon", "genomeA"]}
+                "taxon": [BIN, "read_id", *q, "-n", str(work / "taxon"), "--taxon", "genomeA"],
+                "taxon_lz": [BIN, "read_id", *q, "-n", str(work / "taxon_lz"), "--taxon", "genomeA", "--gz-matches"]}
         if parent_bin:
             cmds["parent"] = [parent_bin, "read_id", *q, "-n", str(work / "parent")]
         run(cmds["plain"], env=env)                              # a warm-up nobody counts: index and reads come into the page cache
@@ -126,12 +137,14 @@ def main():
                 first.setdefault(tag, phases(p.stderr))
         same = all(open(work / f"taxon_{s}.txt", "rb").read() == open(work / f"plain_{s}.txt", "rb").read() for s in ("reads", "counts"))
         out_gz = os.path.getsize(work / "taxon_genomeA.fq.gz")
+        out_gz_lz = os.path.getsize(work / "taxon_lz_genomeA.fq.gz")
         cli_stats = kernel_stats(out_dir, "filter_cli", cmds["taxon"])
-        label = {"plain": "`read_id`", "taxon": "`read_id --taxon genomeA`", "parent": "`read_id`, the parent commit's binary"}
+        label = {"plain": "`read_id`", "taxon": "`read_id --taxon genomeA`", "taxon_lz": "`read_id --taxon genomeA --gz-matches`",
+                 "parent": "`read_id`, the parent commit's binary"}
         lines += ["", "## (b) the command line", "",
                   f"index: {G} genomes of {LG:,} bases, m = 5 M, n = 4, k = 31; reads: {text_bytes / 1e6:.1f} MB of FASTQ text as block gzip "
                   f"({os.path.getsize(work / 'reads.fastq.gz') / 1e6:.1f} MB); `--taxon genomeA` names {G // 2} of the {G} accessions; its output: "
-                  f"{out_gz / 1e6:.1f} MB; `_reads.txt` and `_counts.txt` equal to the run without the flags: {same}", "",
+                  f"{out_gz / 1e6:.1f} MB, with `--gz-matches` {out_gz_lz / 1e6:.1f} MB; `_reads.txt` and `_counts.txt` equal to the run without the flags: {same}", "",
                   f"| command | process wall, {REPS} alternating runs | classification phase (COLORID_TIMING) |", "|---|---|---|"]
         for tag in cmds:
             lines.append(f"| {label[tag]} | {rng_of(walls[tag], 's')} | {rng_of(cls[tag], 'ms', '{:.0f}')} |")
