@@ -142,6 +142,47 @@ uint8_t *pin_reserve(cid_ctx *c, size_t bytes, size_t cap) {
     c->pin_bytes = want;
     return c->pin;
 }
+// where a piece lies in the arena, or NULL: no arena (or no room in what was reserved of it)
+static uint8_t *piece_in(uint8_t *pin, size_t reserve, size_t &at, size_t bytes) {
+    if (!pin || at + bytes > reserve) return nullptr;
+    uint8_t *p = pin + at;
+    at = (at + bytes + 15) & ~(size_t)15;
+    return p;
+}
+int staged_upload(cid_ctx *c, std::initializer_list<HostPiece> pieces, size_t reserve) {
+    uint8_t *pin = pin_reserve(c, reserve);
+    if (pin) HIP_TRY(hipStreamSynchronize(c->stream));   // (the arena may still feed the previous call's copies)
+    size_t at = 0;
+    for (const HostPiece &p : pieces) {
+        if (!p.bytes) continue;
+        uint8_t *stage = piece_in(pin, reserve, at, p.bytes);
+        HIP_TRY(hipMemcpyAsync(p.dev, stage ? memcpy(stage, p.host, p.bytes) : p.host, p.bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    return CID_OK;
+}
+int staged_download(cid_ctx *c, std::initializer_list<DevPiece> pieces, size_t reserve) {
+    uint8_t *pin = pin_reserve(c, reserve);
+    size_t at = 0;
+    for (const DevPiece &p : pieces) {   // (in stream order behind whatever still reads the arena: no wait before them)
+        if (!p.bytes) continue;
+        uint8_t *stage = piece_in(pin, reserve, at, p.bytes);
+        HIP_TRY(hipMemcpyAsync(stage ? stage : p.host, p.dev, p.bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    at = 0;
+    for (const DevPiece &p : pieces)
+        if (uint8_t *stage = p.bytes ? piece_in(pin, reserve, at, p.bytes) : nullptr) memcpy(p.host, stage, p.bytes);
+    return CID_OK;
+}
+int store_sparse(cid_ctx *c, const uint32_t *d_report, uint32_t width, uint64_t n_rows) {
+    ctx_free(c, c->sp_start); c->sp_start = nullptr;
+    ctx_free(c, c->sp_col); c->sp_col = nullptr;
+    ctx_free(c, c->sp_cnt); c->sp_cnt = nullptr;
+    c->sp_rows = 0; c->sp_entries = 0;
+    const int rc = compact_report(c, d_report, width, n_rows, &c->sp_start, &c->sp_col, &c->sp_cnt, &c->sp_entries);
+    if (rc == CID_OK) c->sp_rows = n_rows;
+    return rc;
+}
 }  // namespace cid
 
 extern "C" {

@@ -24,6 +24,18 @@ int check_ready(const cid_ctx *c, const cid_index *ix) {
     if (ix->ctx->device != c->device) return fail(CID_ERR_INVALID, "index lives on device %d, ctx on %d", ix->ctx->device, c->device);
     return CID_OK;
 }
+int check_batch(const HostOffsets &h, uint32_t stride_d, const void *bases) {
+    if (!h.seq_off || !h.read_seq0) return fail(CID_ERR_INVALID, "null argument");
+    if (stride_d == 0) return fail(CID_ERR_INVALID, "stride_d must be >= 1");
+    if (h.n_reads == 0) return CID_OK;
+    if (h.read_seq0[h.n_reads] > h.n_seqs) return fail(CID_ERR_INVALID, "read_seq0 points past n_seqs");
+    if (h.seq_off[h.n_seqs] && !bases) return fail(CID_ERR_INVALID, "null bases");
+    return CID_OK;
+}
+int batch_fail(const BatchFault &f) {
+    static const char *const what[] = {"", "read_seq0 not monotonic at read", "read_seq0 points past n_seqs at read", "seq_off not monotonic at seq"};
+    return f.rule ? fail(CID_ERR_INVALID, "%s %llu", what[f.rule], (unsigned long long)f.at) : CID_OK;
+}
 // `search` is not defined on minimizer indices ("An index with minimizers (.mxi) is used, but not available for this
 // function", src/main.rs:569-573)
 int check_not_mini(const cid_index *ix) {

@@ -4,7 +4,10 @@
 #include "cid_api_common.hpp"
 
 using cid::check_ready;
+using cid::DevReads;
 using cid::fail;
+using cid::HostOffsets;
+using cid::ReadOut;
 using cid::slot_reserve;
 using namespace cid::slots;
 
@@ -121,10 +124,10 @@ static int readid_params(const cid_ctx *c, const cid_index *ix, uint32_t stride_
 
 using StripeArgs = cid::StripePass;
 
-static int readid_dev_impl(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const uint64_t *d_seq_off,
-                           const uint64_t *d_read_seq0, size_t n_reads, uint32_t stride_d, uint32_t start_sample,
-                           uint64_t max_read_bytes, uint64_t max_read_windows, const uint8_t *d_skip, bool clear_wide, uint32_t *d_report,
-                           uint32_t *d_n_kmers, uint8_t *d_status, const StripeArgs &sa = StripeArgs()) {
+static int readid_dev_impl(cid_ctx *c, const cid_index *ix, const DevReads &b, uint64_t max_read_bytes, uint64_t max_read_windows, const uint8_t *d_skip,
+                           bool clear_wide, const ReadOut &o, const StripeArgs &sa = StripeArgs()) {
+    const size_t n_reads = b.n_reads;
+    const uint32_t stride_d = b.stride_d, start_sample = b.start_sample;
     if (n_reads >= (1ull << 32)) return fail(CID_ERR_UNSUPPORTED, "more than 2^32 reads in one batch");
     cid::ReadIdParams pb, pp;
     int waves_b, waves_p = 0;
@@ -135,8 +138,8 @@ static int readid_dev_impl(cid_ctx *c, const cid_index *ix, const uint8_t *d_bas
     if (packable && (rc = readid_params(c, ix, stride_d, start_sample, max_read_bytes, max_read_windows, false, pp, waves_p, striped))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     auto fill = [&](cid::ReadIdParams &p, int waves) {
-        p.bases = d_bases; p.seq_off = d_seq_off; p.read_seq0 = d_read_seq0; p.n_reads = n_reads;
-        p.report = d_report; p.n_kmers = d_n_kmers; p.status = d_status; p.skip = d_skip;
+        p.bases = b.d_bases; p.seq_off = b.d_seq_off; p.read_seq0 = b.d_read_seq0; p.n_reads = n_reads;
+        p.report = o.d_report; p.n_kmers = o.d_n_kmers; p.status = o.d_status; p.skip = d_skip;
         p.zero_acc = sa.zero_acc; p.zero_in = sa.zero_in; p.zero_start = sa.zero_start;
         p.colour_base = sa.colour_base; p.report_width = sa.report_width; p.write_nohits = sa.write_nohits;
         uint64_t rpb = n_reads / ((uint64_t)c->n_cu * (uint64_t)c->tune.readid_blocks_per_cu);   // (16 -> 64 per CU: -3 %, the tail of the grid)
@@ -145,7 +148,7 @@ static int readid_dev_impl(cid_ctx *c, const cid_index *ix, const uint8_t *d_bas
         p.reads_per_block = (uint32_t)rpb;
     };
     if (ix->rs > 128 && clear_wide)   // wide rows count in place
-        HIP_TRY(hipMemsetAsync(d_report, 0, n_reads * ((size_t)ix->n_colors + 1) * 4, c->stream));
+        HIP_TRY(hipMemsetAsync(o.d_report, 0, n_reads * ((size_t)ix->n_colors + 1) * 4, c->stream));
     if (!d_skip) {   // device-pointer callers state the maxima: reads beyond them are marked and left alone (k_readid_check_caps)
         void *d_sk;
         rc = slot_reserve(c, S_ROUTE, n_reads, &d_sk); if (rc) return rc;
@@ -193,68 +196,27 @@ static uint64_t long_from(const cid_ctx *c, const cid_index *ix, uint32_t stride
     }
     return hi;
 }
-// validates host offsets; the longest read in bases and in windows
-struct ReadRoute {
-    uint64_t max_bytes = 0, max_win = 0;
-    bool any_long = false;
-};
-static int readid_route(const cid_ctx *c, const cid_index *ix, const uint64_t *seq_off, size_t n_seqs, const uint64_t *read_seq0, size_t n_reads, uint32_t stride_d,
-                        uint32_t start_sample, ReadRoute &rr) {
-    // (this loop runs on the caller's thread before anything is launched: a million reads of 150 bases took 2.1 ms in it — beside 5.2 ms of
-    // kernel — while every read paid a 64-bit division by a stride that is 1 unless -d says otherwise)
-    uint64_t max_bytes = 0, max_win = 0;
-    const uint64_t k = ix->k;
-    auto walk = [&](auto windows_of) -> int {
-        for (size_t r = 0; r < n_reads; ++r) {   // (both bounds before seq_off is read through them)
-            if (read_seq0[r + 1] < read_seq0[r]) return fail(CID_ERR_INVALID, "read_seq0 not monotonic at read %zu", r);
-            if (read_seq0[r + 1] > n_seqs) return fail(CID_ERR_INVALID, "read_seq0 points past n_seqs at read %zu", r);
-            const uint64_t s0 = read_seq0[r], s1 = read_seq0[r + 1];
-            uint64_t win = 0;
-            for (uint64_t s = s0; s < s1; ++s) {
-                if (seq_off[s + 1] < seq_off[s]) return fail(CID_ERR_INVALID, "seq_off not monotonic at seq %llu", (unsigned long long)s);
-                const uint64_t len = seq_off[s + 1] - seq_off[s];
-                if (len >= k) win += windows_of(len - k);
-            }
-            const uint64_t bytes = s1 > s0 ? seq_off[s1] - seq_off[s0] : 0;
-            if (bytes > max_bytes) max_bytes = bytes;
-            if (win > max_win) max_win = win;
-        }
-        return CID_OK;
-    };
-    const int rc_walk = stride_d == 1 ? walk([](uint64_t x) { return x + 1; }) : walk([stride_d](uint64_t x) { return x / stride_d + 1; });
-    if (rc_walk) return rc_walk;
-    rr.max_bytes = max_bytes; rr.max_win = max_win;
-    rr.any_long = max_bytes >= long_from(c, ix, stride_d, start_sample);
-    return CID_OK;
-}
-
 // A batch with long reads, everything on the device: the route (d_route: S_ROUTE), the long-read path for its reads, the LDS kernels for the
-// rest.  cap_*: the maxima a device-pointer caller stated (reads beyond them: status 3), ~0 = none.  h_*: the offsets on the host, or NULL.
-static int readid_routed(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const uint64_t *d_seq_off, const uint64_t *d_read_seq0, size_t n_reads,
-                         uint32_t stride_d, uint32_t start_sample, uint64_t cap_bytes, uint64_t cap_win, bool clear_wide, uint32_t *d_report, uint32_t *d_n_kmers,
-                         uint8_t *d_status, const StripeArgs &sa, const uint64_t *h_seq_off, const uint64_t *h_read_seq0) {
+// rest.  cap_*: the maxima a device-pointer caller stated (reads beyond them: status 3), ~0 = none.  host: the offsets on the host, or NULL.
+static int readid_routed(cid_ctx *c, const cid_index *ix, const DevReads &b, uint64_t cap_bytes, uint64_t cap_win, bool clear_wide, const ReadOut &o,
+                         const StripeArgs &sa, const HostOffsets *host) {
     int rc;
     void *d_route;
+    const size_t n_reads = b.n_reads;
     if ((rc = slot_reserve(c, S_ROUTE, n_reads + 16 + 16, &d_route))) return rc;
     uint32_t *d_stats = reinterpret_cast<uint32_t *>((uint8_t *)d_route + ((n_reads + 15) & ~(size_t)15));
-    if ((rc = cid::long_route_launch(c, d_seq_off, d_read_seq0, n_reads, ix->k, stride_d, long_from(c, ix, stride_d, start_sample), cap_bytes, cap_win,
-                                     (uint8_t *)d_route, d_stats)))
-        return rc;
+    if ((rc = cid::long_route_launch(c, b, ix->k, long_from(c, ix, b.stride_d, b.start_sample), cap_bytes, cap_win, (uint8_t *)d_route, d_stats))) return rc;
     const bool striped = sa.on();
     const size_t C1 = (size_t)ix->n_colors + 1;
     // wide rows count in place, and both kernels add into the same report: cleared once, here
-    if (ix->rs > 128 && clear_wide && !striped) HIP_TRY(hipMemsetAsync(d_report, 0, n_reads * C1 * 4, c->stream));
+    if (ix->rs > 128 && clear_wide && !striped) HIP_TRY(hipMemsetAsync(o.d_report, 0, n_reads * C1 * 4, c->stream));
     uint32_t stats[4] = {0, 0, 0, 0};
     // first: it writes a status for every read (2 = the other kernels')
-    if ((rc = cid::readid_long(c, ix, d_bases, d_seq_off, d_read_seq0, n_reads, stride_d, start_sample, (const uint8_t *)d_route, false, d_report, d_n_kmers,
-                               d_status, sa, h_seq_off, h_read_seq0, d_stats, stats)))
-        return rc;
+    if ((rc = cid::readid_long(c, ix, b, (const uint8_t *)d_route, false, o, sa, host, d_stats, stats))) return rc;
     if (stats[1])   // the reads of the LDS kernels, sized by the longest of THEM
-        if ((rc = readid_dev_impl(c, ix, d_bases, d_seq_off, d_read_seq0, n_reads, stride_d, start_sample, stats[2], stats[3] ? stats[3] : 1,
-                                  (const uint8_t *)d_route, false, d_report, d_n_kmers, d_status, sa)))
-            return rc;
+        if ((rc = readid_dev_impl(c, ix, b, stats[2], stats[3] ? stats[3] : 1, (const uint8_t *)d_route, false, o, sa))) return rc;
     if (cap_bytes != ~0ull || cap_win != ~0ull)
-        if ((rc = cid::long_beyond_launch(c, (const uint8_t *)d_route, n_reads, striped ? 0u : (uint32_t)C1, d_report, d_n_kmers, d_status))) return rc;
+        if ((rc = cid::long_beyond_launch(c, (const uint8_t *)d_route, n_reads, striped ? 0u : (uint32_t)C1, o))) return rc;
     return CID_OK;
 }
 
@@ -268,11 +230,12 @@ int cid_readid_count_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases
     if (n_reads == 0) return CID_OK;
     if (!d_bases || !d_seq_off || !d_read_seq0 || !d_report || !d_n_kmers || !d_status) return fail(CID_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
+    const DevReads b{.d_bases = d_bases, .d_seq_off = d_seq_off, .d_read_seq0 = d_read_seq0, .n_reads = n_reads, .stride_d = stride_d,
+                     .start_sample = start_sample};
+    const ReadOut o{.d_report = d_report, .d_n_kmers = d_n_kmers, .d_status = d_status};
     if (max_read_bytes >= long_from(c, ix, stride_d, start_sample))   // reads of any length: the long ones through cid_readlong.hip, in the same call
-        return readid_routed(c, ix, d_bases, d_seq_off, d_read_seq0, n_reads, stride_d, start_sample, max_read_bytes, max_read_windows, true, d_report,
-                             d_n_kmers, d_status, StripeArgs(), nullptr, nullptr);
-    return readid_dev_impl(c, ix, d_bases, d_seq_off, d_read_seq0, n_reads, stride_d, start_sample, max_read_bytes, max_read_windows, nullptr,
-                           true, d_report, d_n_kmers, d_status);
+        return readid_routed(c, ix, b, max_read_bytes, max_read_windows, true, o, StripeArgs(), nullptr);
+    return readid_dev_impl(c, ix, b, max_read_bytes, max_read_windows, nullptr, true, o);
 }
 
 // read_id over colour stripes (src/read_id_mt_pe.rs:66-165 with the absent-row stop decided over ALL colours).
@@ -285,7 +248,7 @@ __global__ void k_mask_starts(uint64_t *zero_start, uint64_t n_reads, uint64_t s
 }
 // the device-pointer pair: masks laid out [read][max_read_windows]
 static int readid_stripe_common(cid_ctx *c, const cid_index *ix, const void *d_bases, const void *d_seq_off, const void *d_read_seq0,
-                                size_t n_reads, uint64_t max_read_bytes, uint64_t max_read_windows, const uint64_t **d_zero_start) {
+                                size_t n_reads, uint32_t stride_d, uint64_t max_read_bytes, uint64_t max_read_windows, const uint64_t **d_zero_start) {
     int rc = check_ready(c, ix);
     if (rc) return rc;
     if (!d_bases || !d_seq_off || !d_read_seq0) return fail(CID_ERR_INVALID, "null argument");
@@ -294,6 +257,7 @@ static int readid_stripe_common(cid_ctx *c, const cid_index *ix, const void *d_b
         return fail(CID_ERR_UNSUPPORTED,
                     "reads of %llu bases do not fit a wave's LDS: cid_readid_stripe_zero / _count route such reads through the sort-based path",
                     (unsigned long long)max_read_bytes);
+    if (stride_d == 0) return fail(CID_ERR_INVALID, "stride_d must be >= 1");
     *d_zero_start = nullptr;
     if (n_reads == 0) return CID_OK;
     HIP_TRY(hipSetDevice(c->device));
@@ -309,15 +273,15 @@ int cid_readid_stripe_zero_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d
                                size_t n_reads, uint32_t stride_d, uint64_t max_read_bytes, uint64_t max_read_windows, uint32_t *d_zero_acc,
                                uint32_t *d_n_kmers, uint8_t *d_status) {
     const uint64_t *d_zs;
-    int rc = readid_stripe_common(c, ix, d_bases, d_seq_off, d_read_seq0, n_reads, max_read_bytes, max_read_windows, &d_zs);
+    int rc = readid_stripe_common(c, ix, d_bases, d_seq_off, d_read_seq0, n_reads, stride_d, max_read_bytes, max_read_windows, &d_zs);
     if (rc) return rc;
-    if (stride_d == 0) return fail(CID_ERR_INVALID, "stride_d must be >= 1");
     if (n_reads == 0) return CID_OK;
     if (!d_zero_acc || !d_n_kmers || !d_status) return fail(CID_ERR_INVALID, "null argument");
     StripeArgs sa;
     sa.zero_acc = d_zero_acc; sa.zero_start = d_zs; sa.report_width = ix->n_colors + 1;
-    return readid_dev_impl(c, ix, d_bases, d_seq_off, d_read_seq0, n_reads, stride_d, 0, max_read_bytes, max_read_windows, nullptr, false,
-                           reinterpret_cast<uint32_t *>(d_zero_acc) /* never written in this pass */, d_n_kmers, d_status, sa);
+    const DevReads b{.d_bases = d_bases, .d_seq_off = d_seq_off, .d_read_seq0 = d_read_seq0, .n_reads = n_reads, .stride_d = stride_d, .start_sample = 0};
+    const ReadOut o{.d_report = d_zero_acc /* never written in this pass */, .d_n_kmers = d_n_kmers, .d_status = d_status};
+    return readid_dev_impl(c, ix, b, max_read_bytes, max_read_windows, nullptr, false, o, sa);
 }
 
 int cid_readid_stripe_count_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const uint64_t *d_seq_off, const uint64_t *d_read_seq0,
@@ -325,9 +289,8 @@ int cid_readid_stripe_count_dev(cid_ctx *c, const cid_index *ix, const uint8_t *
                                 uint32_t colour_base, uint32_t n_colors_total, int write_nohits, const uint32_t *d_zero_acc, uint32_t *d_report,
                                 uint32_t *d_n_kmers, uint8_t *d_status) {
     const uint64_t *d_zs;
-    int rc = readid_stripe_common(c, ix, d_bases, d_seq_off, d_read_seq0, n_reads, max_read_bytes, max_read_windows, &d_zs);
+    int rc = readid_stripe_common(c, ix, d_bases, d_seq_off, d_read_seq0, n_reads, stride_d, max_read_bytes, max_read_windows, &d_zs);
     if (rc) return rc;
-    if (stride_d == 0) return fail(CID_ERR_INVALID, "stride_d must be >= 1");
     if ((uint64_t)colour_base + ix->n_colors > n_colors_total) return fail(CID_ERR_INVALID, "stripe [%u, +%u) outside %u colours", colour_base,
                                                                            ix->n_colors, n_colors_total);
     if (n_reads == 0) return CID_OK;
@@ -335,82 +298,50 @@ int cid_readid_stripe_count_dev(cid_ctx *c, const cid_index *ix, const uint8_t *
     StripeArgs sa;
     sa.zero_in = d_zero_acc; sa.zero_start = d_zs; sa.colour_base = colour_base; sa.report_width = n_colors_total + 1;
     sa.write_nohits = write_nohits ? 1u : 0u;
-    return readid_dev_impl(c, ix, d_bases, d_seq_off, d_read_seq0, n_reads, stride_d, start_sample, max_read_bytes, max_read_windows, nullptr, false,
-                           d_report, d_n_kmers, d_status, sa);
+    const DevReads b{.d_bases = d_bases, .d_seq_off = d_seq_off, .d_read_seq0 = d_read_seq0, .n_reads = n_reads, .stride_d = stride_d,
+                     .start_sample = start_sample};
+    const ReadOut o{.d_report = d_report, .d_n_kmers = d_n_kmers, .d_status = d_status};
+    return readid_dev_impl(c, ix, b, max_read_bytes, max_read_windows, nullptr, false, o, sa);
 }
 
 // The two stripe passes for ANY read length and stripe width: d_bases resident, offsets on the host.  Per stripe the reads are routed
 // between the LDS kernels and the sort-based path exactly as cid_readid_count routes them (the mask of a read's q-th distinct k-mer
 // sits at the same word whichever kernel writes it, so different stripes may route a read differently).  Masks: one word per
 // window, read r's at [prefix of the windows of reads 0..r-1] (cid_readid_stripe_mask_words words in all).
-static int stripe_mask_starts(uint32_t k, uint32_t stride_d, const uint64_t *seq_off, uint64_t n_seqs, const uint64_t *read_seq0, size_t n_reads,
-                              std::vector<uint64_t> &zs) {
-    zs.assign(n_reads + 1, 0);
-    for (size_t r = 0; r < n_reads; ++r) {
-        if (read_seq0[r + 1] < read_seq0[r]) return fail(CID_ERR_INVALID, "read_seq0 not monotonic at read %zu", r);
-        if (read_seq0[r + 1] > n_seqs) return fail(CID_ERR_INVALID, "read_seq0 points past n_seqs at read %zu", r);
-        uint64_t win = 0;
-        for (uint64_t s = read_seq0[r]; s < read_seq0[r + 1]; ++s) {
-            if (seq_off[s + 1] < seq_off[s]) return fail(CID_ERR_INVALID, "seq_off not monotonic at seq %llu", (unsigned long long)s);
-            const uint64_t len = seq_off[s + 1] - seq_off[s];
-            if (len >= k) win += (len - k) / stride_d + 1;
-        }
-        zs[r + 1] = zs[r] + win;
-    }
-    return CID_OK;
-}
-
 int cid_readid_stripe_mask_words(uint32_t k_size, uint32_t stride_d, const uint64_t *seq_off, const uint64_t *read_seq0, size_t n_reads, uint64_t *n_words) {
     if (!seq_off || !read_seq0 || !n_words) return fail(CID_ERR_INVALID, "null argument");
     if (stride_d == 0 || k_size == 0) return fail(CID_ERR_INVALID, "k_size and stride_d must be >= 1");
-    std::vector<uint64_t> zs;
-    const int rc = stripe_mask_starts(k_size, stride_d, seq_off, ~0ull /* the caller vouches for seq_off's length */, read_seq0, n_reads, zs);
-    if (rc) return rc;
-    *n_words = zs[n_reads] + 1;   // never empty
+    const HostOffsets h{.seq_off = seq_off, .n_seqs = ~0ull /* the caller vouches for seq_off's length */, .read_seq0 = read_seq0, .n_reads = n_reads};
+    const cid::BatchSizes z = cid::walk_batch(h, k_size, stride_d);
+    if (const int rc = cid::batch_fail(z.fault)) return rc;
+    *n_words = z.total_win + 1;   // never empty
     return CID_OK;
 }
 
-static int readid_stripe_pass(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const uint64_t *seq_off, size_t n_seqs, const uint64_t *read_seq0,
-                              size_t n_reads, uint32_t stride_d, uint32_t start_sample, StripeArgs sa, uint32_t *d_report, uint32_t *d_n_kmers,
-                              uint8_t *d_status) {
+static int readid_stripe_pass(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const HostOffsets &h, uint32_t stride_d, uint32_t start_sample,
+                              StripeArgs sa, const ReadOut &o) {
     int rc = check_ready(c, ix);
     if (rc) return rc;
-    if (!seq_off || !read_seq0) return fail(CID_ERR_INVALID, "null argument");
-    if (stride_d == 0) return fail(CID_ERR_INVALID, "stride_d must be >= 1");
+    if ((rc = cid::check_batch(h, stride_d, d_bases))) return rc;
+    const size_t n_reads = h.n_reads, n_seqs = h.n_seqs;
     if (n_reads == 0) return CID_OK;
-    if (!d_n_kmers || !d_status) return fail(CID_ERR_INVALID, "null argument");
-    if (read_seq0[n_reads] > n_seqs) return fail(CID_ERR_INVALID, "read_seq0 points past n_seqs");
-    if (seq_off[n_seqs] && !d_bases) return fail(CID_ERR_INVALID, "null bases");
-    ReadRoute rr;
-    if ((rc = readid_route(c, ix, seq_off, n_seqs, read_seq0, n_reads, stride_d, start_sample, rr))) return rc;
-    std::vector<uint64_t> zs;
-    if ((rc = stripe_mask_starts(ix->k, stride_d, seq_off, n_seqs, read_seq0, n_reads, zs))) return rc;
-    if (zs[n_reads] >= (1ull << 32)) return fail(CID_ERR_UNSUPPORTED, "more than 2^32 k-mer windows in one read_id batch");
+    if (!o.d_n_kmers || !o.d_status) return fail(CID_ERR_INVALID, "null argument");
+    std::vector<uint64_t> zs(n_reads + 1);
+    const cid::BatchSizes z = cid::walk_batch(h, ix->k, stride_d, zs.data());   // the one walk: refused, or the sizes and the masks' starts
+    if ((rc = cid::batch_fail(z.fault))) return rc;
+    if (z.total_win >= (1ull << 32)) return fail(CID_ERR_UNSUPPORTED, "more than 2^32 k-mer windows in one read_id batch");
     HIP_TRY(hipSetDevice(c->device));
     void *d_so, *d_r0, *d_zs;
-    rc = slot_reserve(c, S_SEQOFF, (n_seqs + 1) * 8, &d_so); if (rc) return rc;
-    rc = slot_reserve(c, S_READ0, (n_reads + 1) * 8, &d_r0); if (rc) return rc;
-    rc = slot_reserve(c, S_ZSTART, (n_reads + 1) * 8, &d_zs); if (rc) return rc;
-    {   // the three offset arrays through the pinned arena when they fit (cid::pin_reserve)
-        const size_t b0 = (n_seqs + 1) * 8, b1 = (n_reads + 1) * 8;
-        const uint8_t *so_src = reinterpret_cast<const uint8_t *>(seq_off), *r0_src = reinterpret_cast<const uint8_t *>(read_seq0),
-                      *zs_src = reinterpret_cast<const uint8_t *>(zs.data());
-        if (uint8_t *pin = cid::pin_reserve(c, b0 + 2 * b1 + 64)) {
-            HIP_TRY(hipStreamSynchronize(c->stream));
-            memcpy(pin, seq_off, b0); memcpy(pin + b0, read_seq0, b1); memcpy(pin + b0 + b1, zs.data(), b1);
-            so_src = pin; r0_src = pin + b0; zs_src = pin + b0 + b1;
-        }
-        HIP_TRY(hipMemcpyAsync(d_so, so_src, b0, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_r0, r0_src, b1, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_zs, zs_src, b1, hipMemcpyHostToDevice, c->stream));
-    }
+    const size_t b0 = (n_seqs + 1) * 8, b1 = (n_reads + 1) * 8;
+    if ((rc = slot_reserve(c, S_SEQOFF, b0, &d_so)) || (rc = slot_reserve(c, S_READ0, b1, &d_r0)) || (rc = slot_reserve(c, S_ZSTART, b1, &d_zs))) return rc;
+    if ((rc = cid::staged_upload(c, {{d_so, h.seq_off, b0}, {d_r0, h.read_seq0, b1}, {d_zs, zs.data(), b1}}, b0 + 2 * b1 + 64))) return rc;
     sa.zero_start = (const uint64_t *)d_zs;
-    if (rr.any_long)   // (the mask of a read's q-th distinct k-mer sits at the same word whichever kernel writes it)
-        rc = readid_routed(c, ix, d_bases, (const uint64_t *)d_so, (const uint64_t *)d_r0, n_reads, stride_d, start_sample, ~0ull, ~0ull, false, d_report,
-                           d_n_kmers, d_status, sa, seq_off, read_seq0);
+    const DevReads b{.d_bases = d_bases, .d_seq_off = (const uint64_t *)d_so, .d_read_seq0 = (const uint64_t *)d_r0, .n_reads = n_reads,
+                     .stride_d = stride_d, .start_sample = start_sample};
+    if (z.max_bases >= long_from(c, ix, stride_d, start_sample))   // (the mask of a read's q-th distinct k-mer sits at the same word whichever kernel writes it)
+        rc = readid_routed(c, ix, b, ~0ull, ~0ull, false, o, sa, &h);
     else
-        rc = readid_dev_impl(c, ix, d_bases, (const uint64_t *)d_so, (const uint64_t *)d_r0, n_reads, stride_d, start_sample, rr.max_bytes,
-                             rr.max_win ? rr.max_win : 1, nullptr, false, d_report, d_n_kmers, d_status, sa);
+        rc = readid_dev_impl(c, ix, b, z.max_bases, z.max_win ? z.max_win : 1, nullptr, false, o, sa);
     HIP_TRY(hipStreamSynchronize(c->stream));   // the host vectors leave scope
     return rc;
 }
@@ -420,8 +351,9 @@ int cid_readid_stripe_zero(cid_ctx *c, const cid_index *ix, const uint8_t *d_bas
     if (n_reads && !d_zero_acc) return fail(CID_ERR_INVALID, "null argument");
     StripeArgs sa;
     sa.zero_acc = d_zero_acc; sa.report_width = ix ? ix->n_colors + 1 : 0;
-    return readid_stripe_pass(c, ix, d_bases, seq_off, n_seqs, read_seq0, n_reads, stride_d, 0, sa,
-                              reinterpret_cast<uint32_t *>(d_zero_acc) /* never written in this pass */, d_n_kmers, d_status);
+    const HostOffsets h{.seq_off = seq_off, .n_seqs = n_seqs, .read_seq0 = read_seq0, .n_reads = n_reads};
+    const ReadOut o{.d_report = d_zero_acc /* never written in this pass */, .d_n_kmers = d_n_kmers, .d_status = d_status};
+    return readid_stripe_pass(c, ix, d_bases, h, stride_d, 0, sa, o);
 }
 
 int cid_readid_stripe_count(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const uint64_t *seq_off, size_t n_seqs, const uint64_t *read_seq0,
@@ -432,36 +364,29 @@ int cid_readid_stripe_count(cid_ctx *c, const cid_index *ix, const uint8_t *d_ba
         ix->n_colors, n_colors_total);
     StripeArgs sa;
     sa.zero_in = d_zero_acc; sa.colour_base = colour_base; sa.report_width = n_colors_total + 1; sa.write_nohits = write_nohits ? 1u : 0u;
-    return readid_stripe_pass(c, ix, d_bases, seq_off, n_seqs, read_seq0, n_reads, stride_d, start_sample, sa, d_report, d_n_kmers, d_status);
+    const HostOffsets h{.seq_off = seq_off, .n_seqs = n_seqs, .read_seq0 = read_seq0, .n_reads = n_reads};
+    const ReadOut o{.d_report = d_report, .d_n_kmers = d_n_kmers, .d_status = d_status};
+    return readid_stripe_pass(c, ix, d_bases, h, stride_d, start_sample, sa, o);
 }
 
 // bases resident, offsets on the host: routes every read between the LDS kernels and the long-read path, uploads the offsets,
-// runs the kernels into the caller's device arrays.  `d_so` / `d_r0` non-null: the offsets are on the device already (the caller
-// uploaded them together with the bases).
-static int readid_resident(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const uint64_t *seq_off, size_t n_seqs,
-                           const uint64_t *read_seq0, size_t n_reads, uint32_t stride_d, uint32_t start_sample, void *d_so, void *d_r0,
-                           uint32_t *d_rep, uint32_t *d_nk, uint8_t *d_status) {
-    int rc;
-    ReadRoute rr;
-    if ((rc = readid_route(c, ix, seq_off, n_seqs, read_seq0, n_reads, stride_d, start_sample, rr))) return rc;
-    if (!d_so) {
-        rc = slot_reserve(c, S_SEQOFF, (n_seqs + 1) * 8, &d_so); if (rc) return rc;
-        rc = slot_reserve(c, S_READ0, (n_reads + 1) * 8, &d_r0); if (rc) return rc;
-        const size_t b0 = (n_seqs + 1) * 8, b1 = (n_reads + 1) * 8;
-        const uint8_t *so_src = reinterpret_cast<const uint8_t *>(seq_off), *r0_src = reinterpret_cast<const uint8_t *>(read_seq0);
-        if (uint8_t *pin = cid::pin_reserve(c, b0 + b1 + 64)) {
-            HIP_TRY(hipStreamSynchronize(c->stream));   // (the arena may still feed the previous call's copies)
-            memcpy(pin, seq_off, b0); memcpy(pin + b0, read_seq0, b1);
-            so_src = pin; r0_src = pin + b0;
-        }
-        HIP_TRY(hipMemcpyAsync(d_so, so_src, b0, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_r0, r0_src, b1, hipMemcpyHostToDevice, c->stream));
+// runs the kernels into the caller's device arrays.  b.d_seq_off / b.d_read_seq0 non-null: the offsets are on the device already (the
+// caller uploaded them together with the bases).
+static int readid_resident(cid_ctx *c, const cid_index *ix, DevReads b, const HostOffsets &h, const ReadOut &o) {
+    const cid::BatchSizes z = cid::walk_batch(h, ix->k, b.stride_d);
+    int rc = cid::batch_fail(z.fault);
+    if (rc) return rc;
+    if (!b.d_seq_off) {
+        void *d_so, *d_r0;
+        const size_t b0 = (h.n_seqs + 1) * 8, b1 = (h.n_reads + 1) * 8;
+        if ((rc = slot_reserve(c, S_SEQOFF, b0, &d_so)) || (rc = slot_reserve(c, S_READ0, b1, &d_r0))) return rc;
+        if ((rc = cid::staged_upload(c, {{d_so, h.seq_off, b0}, {d_r0, h.read_seq0, b1}}, b0 + b1 + 64))) return rc;
+        b.d_seq_off = (const uint64_t *)d_so; b.d_read_seq0 = (const uint64_t *)d_r0;
     }
-    if (rr.any_long)   // the device routes every read between the long-read path and the LDS kernels and makes the former's work lists
-        return readid_routed(c, ix, d_bases, (const uint64_t *)d_so, (const uint64_t *)d_r0, n_reads, stride_d, start_sample, ~0ull, ~0ull, true, d_rep, d_nk,
-                             d_status, StripeArgs(), seq_off, read_seq0);
-    return readid_dev_impl(c, ix, d_bases, (const uint64_t *)d_so, (const uint64_t *)d_r0, n_reads, stride_d, start_sample, rr.max_bytes,
-                           rr.max_win ? rr.max_win : 1, nullptr, true, d_rep, d_nk, d_status);
+    // any long read: the device routes every read between the long-read path and the LDS kernels and makes the former's work lists
+    if (z.max_bases >= long_from(c, ix, b.stride_d, b.start_sample))
+        return readid_routed(c, ix, b, ~0ull, ~0ull, true, o, StripeArgs(), &h);
+    return readid_dev_impl(c, ix, b, z.max_bases, z.max_win ? z.max_win : 1, nullptr, true, o);
 }
 
 int cid_readid_count_resident(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const uint64_t *seq_off, size_t n_seqs,
@@ -469,68 +394,49 @@ int cid_readid_count_resident(cid_ctx *c, const cid_index *ix, const uint8_t *d_
                               uint32_t *d_n_kmers, uint8_t *d_status) {
     int rc = check_ready(c, ix);
     if (rc) return rc;
-    if (!seq_off || !read_seq0) return fail(CID_ERR_INVALID, "null argument");
-    if (stride_d == 0) return fail(CID_ERR_INVALID, "stride_d must be >= 1");
+    const HostOffsets h{.seq_off = seq_off, .n_seqs = n_seqs, .read_seq0 = read_seq0, .n_reads = n_reads};
+    if ((rc = cid::check_batch(h, stride_d, d_bases))) return rc;
     if (n_reads == 0) return CID_OK;
     if (!d_report || !d_n_kmers || !d_status) return fail(CID_ERR_INVALID, "null argument");
-    if (read_seq0[n_reads] > n_seqs) return fail(CID_ERR_INVALID, "read_seq0 points past n_seqs");
-    if (seq_off[n_seqs] && !d_bases) return fail(CID_ERR_INVALID, "null bases");
     HIP_TRY(hipSetDevice(c->device));
-    return readid_resident(c, ix, d_bases, seq_off, n_seqs, read_seq0, n_reads, stride_d, start_sample, nullptr, nullptr, d_report, d_n_kmers,
-                           d_status);
+    const DevReads b{.d_bases = d_bases, .d_seq_off = nullptr, .d_read_seq0 = nullptr, .n_reads = n_reads, .stride_d = stride_d, .start_sample = start_sample};
+    const ReadOut o{.d_report = d_report, .d_n_kmers = d_n_kmers, .d_status = d_status};
+    return readid_resident(c, ix, b, h, o);
 }
 
-// uploads the batch, runs the LDS kernels or the long-read path; leaves report / n_kmers / status in the ctx's device scratch
-static int readid_to_device(cid_ctx *c, const cid_index *ix, const uint8_t *bases, const uint64_t *seq_off, size_t n_seqs,
-                            const uint64_t *read_seq0, size_t n_reads, uint32_t stride_d, uint32_t start_sample, uint32_t **d_report_out,
-                            uint32_t **d_nk_out, uint8_t **d_status_out) {
+// uploads the batch (n_reads > 0), runs the LDS kernels or the long-read path; leaves report / n_kmers / status in the ctx's device scratch
+static int readid_to_device(cid_ctx *c, const cid_index *ix, const uint8_t *bases, const HostOffsets &h, uint32_t stride_d, uint32_t start_sample,
+                            ReadOut &o) {
     int rc = check_ready(c, ix);
     if (rc) return rc;
-    if (!seq_off || !read_seq0) return fail(CID_ERR_INVALID, "null argument");
-    if (stride_d == 0) return fail(CID_ERR_INVALID, "stride_d must be >= 1");
-    if (read_seq0[n_reads] > n_seqs) return fail(CID_ERR_INVALID, "read_seq0 points past n_seqs");
-    const uint64_t total_bases = seq_off[n_seqs];
-    if (total_bases && !bases) return fail(CID_ERR_INVALID, "null bases");
+    if ((rc = cid::check_batch(h, stride_d, bases))) return rc;
+    const size_t n_seqs = h.n_seqs, n_reads = h.n_reads;
+    const uint64_t total_bases = h.seq_off[n_seqs];
     HIP_TRY(hipSetDevice(c->device));
     void *d_bases, *d_so, *d_r0, *d_rep, *d_nk;
     const size_t C1 = (size_t)ix->n_colors + 1;
-    rc = slot_reserve(c, S_BASES, total_bases, &d_bases); if (rc) return rc;
-    rc = slot_reserve(c, S_SEQOFF, (n_seqs + 1) * 8, &d_so); if (rc) return rc;
-    rc = slot_reserve(c, S_READ0, (n_reads + 1) * 8, &d_r0); if (rc) return rc;
-    rc = slot_reserve(c, S_REPORT, n_reads * C1 * 4, &d_rep); if (rc) return rc;
-    rc = slot_reserve(c, S_NK, n_reads * 4 + n_reads + 16, &d_nk); if (rc) return rc;
-    {   // the batch goes through the ctx's pinned arena when it fits (cid::pin_reserve); the arena's tail is left for the results
-        // Bases that lie in page-locked memory already (cid_pinned_alloc: the CLI's batches of long reads) travel from where they are: staged,
-        // 48 MB of them were 10 ms of memcpy on the calling thread before 2 ms on the bus.
-        bool bases_locked = false;
-        if (total_bases >= ((size_t)4 << 20)) {
-            hipPointerAttribute_t at;
-            if (hipPointerGetAttributes(&at, bases) == hipSuccess) bases_locked = at.type == hipMemoryTypeHost;
-            else (void)hipGetLastError();   // (memory the runtime has never seen: not an error of this call)
-        }
-        const size_t staged_bases = bases_locked ? 0 : total_bases;
-        const size_t b_so = (staged_bases + 15) & ~(size_t)15, b_r0 = b_so + (n_seqs + 1) * 8, b_end = b_r0 + (n_reads + 1) * 8;
-        uint8_t *pin = cid::pin_reserve(c, b_end + n_reads * 5 + 64);
-        if (pin) {
-            HIP_TRY(hipStreamSynchronize(c->stream));   // (the arena may still feed the previous call's copies)
-            if (staged_bases) memcpy(pin, bases, total_bases);
-            memcpy(pin + b_so, seq_off, (n_seqs + 1) * 8);
-            memcpy(pin + b_r0, read_seq0, (n_reads + 1) * 8);
-            if (total_bases) HIP_TRY(hipMemcpyAsync(d_bases, bases_locked ? bases : pin, total_bases, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(d_so, pin + b_so, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(d_r0, pin + b_r0, (n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        } else {
-            if (total_bases) HIP_TRY(hipMemcpyAsync(d_bases, bases, total_bases, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(d_so, seq_off, (n_seqs + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(hipMemcpyAsync(d_r0, read_seq0, (n_reads + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        }
+    const size_t b_so = (n_seqs + 1) * 8, b_r0 = (n_reads + 1) * 8;
+    if ((rc = slot_reserve(c, S_BASES, total_bases, &d_bases)) || (rc = slot_reserve(c, S_SEQOFF, b_so, &d_so)) || (rc = slot_reserve(c, S_READ0, b_r0, &d_r0)) ||
+        (rc = slot_reserve(c, S_REPORT, n_reads * C1 * 4, &d_rep)) || (rc = slot_reserve(c, S_NK, n_reads * 4 + n_reads + 16, &d_nk)))
+        return rc;
+    // Bases that lie in page-locked memory already (cid_pinned_alloc: the CLI's batches of long reads) travel from where they are: staged,
+    // 48 MB of them were 10 ms of memcpy on the calling thread before 2 ms on the bus.
+    bool bases_locked = false;
+    if (total_bases >= ((size_t)4 << 20)) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, bases) == hipSuccess) bases_locked = at.type == hipMemoryTypeHost;
+        else (void)hipGetLastError();   // (memory the runtime has never seen: not an error of this call)
     }
-    uint8_t *d_status = (uint8_t *)d_nk + n_reads * 4;
-    rc = readid_resident(c, ix, (const uint8_t *)d_bases, seq_off, n_seqs, read_seq0, n_reads, stride_d, start_sample, d_so, d_r0, (uint32_t *)d_rep,
-                         (uint32_t *)d_nk, d_status);
-    if (rc) return rc;
-    *d_report_out = (uint32_t *)d_rep; *d_nk_out = (uint32_t *)d_nk; *d_status_out = d_status;
-    return CID_OK;
+    // the rest goes through the ctx's pinned arena when it fits; the arena's tail is left for the results
+    const size_t staged_bases = bases_locked ? 0 : total_bases;
+    if ((rc = cid::staged_upload(c, {{d_bases, bases, staged_bases}, {d_so, h.seq_off, b_so}, {d_r0, h.read_seq0, b_r0}},
+                                 ((staged_bases + 15) & ~(size_t)15) + b_so + b_r0 + n_reads * 5 + 64)))
+        return rc;
+    if (bases_locked) HIP_TRY(hipMemcpyAsync(d_bases, bases, total_bases, hipMemcpyHostToDevice, c->stream));
+    o = ReadOut{.d_report = (uint32_t *)d_rep, .d_n_kmers = (uint32_t *)d_nk, .d_status = (uint8_t *)d_nk + n_reads * 4};
+    const DevReads b{.d_bases = (const uint8_t *)d_bases, .d_seq_off = (const uint64_t *)d_so, .d_read_seq0 = (const uint64_t *)d_r0, .n_reads = n_reads,
+                     .stride_d = stride_d, .start_sample = start_sample};
+    return readid_resident(c, ix, b, h, o);
 }
 
 int cid_readid_count(cid_ctx *c, const cid_index *ix, const uint8_t *bases, const uint64_t *seq_off, size_t n_seqs,
@@ -544,33 +450,24 @@ int cid_readid_count(cid_ctx *c, const cid_index *ix, const uint8_t *bases, cons
     const size_t C1 = (size_t)ix->n_colors + 1;
     size_t per = (size_t)c->tune.dense_report_bytes / (C1 * 4);
     if (per == 0) per = 1;
+    const HostOffsets whole{.seq_off = seq_off, .n_seqs = n_seqs, .read_seq0 = read_seq0, .n_reads = n_reads};
     std::vector<uint64_t> so, r0v;
     for (size_t r0 = 0; r0 < n_reads; r0 += per) {
         const size_t nr = n_reads - r0 < per ? n_reads - r0 : per;
-        const uint64_t *so_p = seq_off, *r0_p = read_seq0;
+        HostOffsets h = whole;
         const uint8_t *bases_p = bases;
-        size_t ns = n_seqs;
-        if (nr != n_reads) {   // rebase the slice: its own seq_off / read_seq0 starting at 0
-            if (read_seq0[r0 + nr] > n_seqs || read_seq0[r0] > read_seq0[r0 + nr]) return fail(CID_ERR_INVALID, "read_seq0 points past n_seqs");
-            const uint64_t s0 = read_seq0[r0], s1 = read_seq0[r0 + nr];
-            ns = (size_t)(s1 - s0);
-            so.resize(ns + 1);
-            for (size_t i = 0; i <= ns; ++i) {
-                if (seq_off[s0 + i] < seq_off[s0]) return fail(CID_ERR_INVALID, "seq_off not monotonic at seq %llu", (unsigned long long)(s0 + i));
-                so[i] = seq_off[s0 + i] - seq_off[s0];
-            }
-            r0v.resize(nr + 1);
-            for (size_t i = 0; i <= nr; ++i) r0v[i] = read_seq0[r0 + i] - s0;
-            so_p = so.data(); r0_p = r0v.data();
-            bases_p = bases ? bases + seq_off[s0] : nullptr;
+        if (nr != n_reads) {   // the slice with its own seq_off / read_seq0 starting at 0
+            uint64_t base;
+            if (int rc = cid::batch_fail(cid::rebase_batch(whole, r0, r0 + nr, so, r0v, &base))) return rc;
+            h = HostOffsets{.seq_off = so.data(), .n_seqs = so.size() - 1, .read_seq0 = r0v.data(), .n_reads = nr};
+            bases_p = bases ? bases + base : nullptr;
         }
-        uint32_t *d_rep, *d_nk;
-        uint8_t *d_st;
-        int rc = readid_to_device(c, ix, bases_p, so_p, ns, r0_p, nr, stride_d, start_sample, &d_rep, &d_nk, &d_st);
+        ReadOut d;
+        int rc = readid_to_device(c, ix, bases_p, h, stride_d, start_sample, d);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(report + r0 * C1, d_rep, nr * C1 * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(n_kmers + r0, d_nk, nr * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(status + r0, d_st, nr, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(report + r0 * C1, d.d_report, nr * C1 * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(n_kmers + r0, d.d_n_kmers, nr * 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(status + r0, d.d_status, nr, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     return CID_OK;
@@ -586,27 +483,13 @@ int cid_readid_count_sparse(cid_ctx *c, const cid_index *ix, const uint8_t *base
     if (ix && (double)n_reads * ((double)ix->n_colors + 1.0) * 4.0 > 64.0 * (double)(1ull << 30))
         return fail(CID_ERR_UNSUPPORTED, "%zu reads x %u colours need more than 64 GiB of dense report rows on the device: use smaller batches",
                     n_reads, ix->n_colors);
-    uint32_t *d_rep, *d_nk;
-    uint8_t *d_st;
-    int rc = readid_to_device(c, ix, bases, seq_off, n_seqs, read_seq0, n_reads, stride_d, start_sample, &d_rep, &d_nk, &d_st);
+    ReadOut d;
+    const HostOffsets h{.seq_off = seq_off, .n_seqs = n_seqs, .read_seq0 = read_seq0, .n_reads = n_reads};
+    int rc = readid_to_device(c, ix, bases, h, stride_d, start_sample, d);
     if (rc) return rc;
-    cid::ctx_free(c, c->sp_start); c->sp_start = nullptr;
-    cid::ctx_free(c, c->sp_col); c->sp_col = nullptr;
-    cid::ctx_free(c, c->sp_cnt); c->sp_cnt = nullptr;
-    rc = cid::compact_report(c, d_rep, ix->n_colors + 1, n_reads, &c->sp_start, &c->sp_col, &c->sp_cnt, &c->sp_entries);
-    if (rc) return rc;
-    c->sp_rows = n_reads;
-    if (uint8_t *pin = cid::pin_reserve(c, n_reads * 5 + 64)) {   // (inputs are on the device by now: the arena is free again)
-        HIP_TRY(hipMemcpyAsync(pin, d_nk, n_reads * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(pin + n_reads * 4, d_st, n_reads, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        memcpy(n_kmers, pin, n_reads * 4);
-        memcpy(status, pin + n_reads * 4, n_reads);
-    } else {
-        HIP_TRY(hipMemcpyAsync(n_kmers, d_nk, n_reads * 4, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(status, d_st, n_reads, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
+    if ((rc = cid::store_sparse(c, d.d_report, ix->n_colors + 1, n_reads))) return rc;
+    // (inputs are on the device by now: the arena is free again)
+    if ((rc = cid::staged_download(c, {{n_kmers, d.d_n_kmers, n_reads * 4}, {status, d.d_status, n_reads}}, n_reads * 5 + 64))) return rc;
     *n_entries = c->sp_entries;
     return CID_OK;
 }
@@ -617,23 +500,6 @@ int cid_readid_sparse_fetch(cid_ctx *c, uint64_t *row_start, uint32_t *colours, 
     if (c->sp_entries && (!colours || !counts)) return fail(CID_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
     const size_t b_rs = (c->sp_rows + 1) * 8, b_e = c->sp_entries * 4;
-    if (uint8_t *pin = cid::pin_reserve(c, b_rs + 2 * b_e + 64)) {
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        HIP_TRY(hipMemcpyAsync(pin, c->sp_start, b_rs, hipMemcpyDeviceToHost, c->stream));
-        if (b_e) {
-            HIP_TRY(hipMemcpyAsync(pin + b_rs, c->sp_col, b_e, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipMemcpyAsync(pin + b_rs + b_e, c->sp_cnt, b_e, hipMemcpyDeviceToHost, c->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        memcpy(row_start, pin, b_rs);
-        if (b_e) { memcpy(colours, pin + b_rs, b_e); memcpy(counts, pin + b_rs + b_e, b_e); }
-        return CID_OK;
-    }
-    HIP_TRY(hipMemcpy(row_start, c->sp_start, (c->sp_rows + 1) * 8, hipMemcpyDeviceToHost));
-    if (c->sp_entries) {
-        HIP_TRY(hipMemcpy(colours, c->sp_col, c->sp_entries * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(counts, c->sp_cnt, c->sp_entries * 4, hipMemcpyDeviceToHost));
-    }
-    return CID_OK;
+    return cid::staged_download(c, {{row_start, c->sp_start, b_rs}, {colours, c->sp_col, b_e}, {counts, c->sp_cnt, b_e}}, b_rs + 2 * b_e + 64);
 }
 }  // extern "C"

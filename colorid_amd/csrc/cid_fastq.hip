@@ -734,13 +734,8 @@ static int fastq_end(cid_fastq *fq, uint64_t *n_reads, uint64_t *n_entries, uint
     if (in.classify) {
         if (fq->fetch_stream) HIP_TRY(hipStreamSynchronize(fq->fetch_stream));   // (a fetch of the step before never outlives its call; belt and braces)
         drop_results(fq);
-        cid::ctx_free(c, c->sp_start); c->sp_start = nullptr;
-        cid::ctx_free(c, c->sp_col); c->sp_col = nullptr;
-        cid::ctx_free(c, c->sp_cnt); c->sp_cnt = nullptr;
-        c->sp_rows = 0; c->sp_entries = 0;
-        rc = cid::compact_report(c, in.report, in.n_colors + 1, n, &c->sp_start, &c->sp_col, &c->sp_cnt, &c->sp_entries);
+        rc = cid::store_sparse(c, in.report, in.n_colors + 1, n);
         if (rc) { (void)hipStreamSynchronize(st); drop_inflight(fq); return rc; }
-        c->sp_rows = n;
         fq->d_nk = in.nk; fq->d_status = in.status; fq->d_ids = in.ids; fq->d_id_off = in.id_off;
         in.nk = nullptr; in.status = nullptr; in.ids = nullptr; in.id_off = nullptr;
         fq->n_reads = n; fq->id_bytes = in.total_ids;

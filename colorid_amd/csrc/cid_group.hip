@@ -313,7 +313,8 @@ int cid_group_readid_count_sparse(cid_group *g, cid_index *const *replicas, cons
     if (rc) return rc;
     if (!n_entries || !seq_off || !read_seq0 || (n_reads && (!n_kmers || !status))) return fail(CID_ERR_INVALID, "null argument");
     *n_entries = 0;
-    if (n_reads && read_seq0[n_reads] > n_seqs) return fail(CID_ERR_INVALID, "read_seq0 points past n_seqs");
+    const cid::HostOffsets whole{.seq_off = seq_off, .n_seqs = n_seqs, .read_seq0 = read_seq0, .n_reads = n_reads};
+    if (n_reads && (rc = cid::check_batch(whole, stride_d, bases))) return rc;
     const int n = (int)g->ctx.size();
     g->sp_striped = false;
     rc = for_each_rank(g, [&](int r) -> int {
@@ -322,18 +323,11 @@ int cid_group_readid_count_sparse(cid_group *g, cid_index *const *replicas, cons
         const size_t nr = hi - lo;
         g->sp_rows[r] = nr; g->sp_entries[r] = 0;
         // the shard re-based to its own offsets (every entry checked before seq_off is read through it)
-        for (size_t i = lo; i < hi; ++i)
-            if (read_seq0[i] > read_seq0[i + 1] || read_seq0[i + 1] > n_seqs) return fail(CID_ERR_INVALID,
-                "read_seq0 not monotonic or past n_seqs at read %zu", i);
-        const uint64_t s0 = read_seq0[lo], s1 = read_seq0[hi];
-        std::vector<uint64_t> so(s1 - s0 + 1), r0(nr + 1);
-        for (size_t i = 0; i <= s1 - s0; ++i) {
-            if (seq_off[s0 + i] < seq_off[s0]) return fail(CID_ERR_INVALID, "seq_off not monotonic");
-            so[i] = seq_off[s0 + i] - seq_off[s0];
-        }
-        for (size_t i = 0; i <= nr; ++i) r0[i] = read_seq0[lo + i] - s0;
+        std::vector<uint64_t> so, r0;
+        uint64_t base;
+        if (int bad = cid::batch_fail(cid::rebase_batch(whole, lo, hi, so, r0, &base))) return bad;
         uint64_t ne = 0;
-        const int e = cid_readid_count_sparse(g->ctx[r], replicas[r], bases ? bases + seq_off[s0] : nullptr, so.data(), s1 - s0, r0.data(), nr, stride_d,
+        const int e = cid_readid_count_sparse(g->ctx[r], replicas[r], bases ? bases + base : nullptr, so.data(), so.size() - 1, r0.data(), nr, stride_d,
                                               start_sample, n_kmers + lo, status + lo, &ne);
         g->sp_entries[r] = ne;
         return e;

@@ -451,19 +451,18 @@ int cid_group_stripes_readid_count_sparse(cid_group *g, cid_index *const *stripe
     Stripes st;
     int rc = check_stripes(g, stripes, st);
     if (rc) return rc;
-    if (!n_entries || !seq_off || !read_seq0 || (n_reads && (!n_kmers || !status))) return fail(CID_ERR_INVALID, "null argument");
+    if (!n_entries || (n_reads && (!n_kmers || !status))) return fail(CID_ERR_INVALID, "null argument");
     *n_entries = 0;
-    if (stride_d == 0) return fail(CID_ERR_INVALID, "stride_d must be >= 1");
+    const cid::HostOffsets h{.seq_off = seq_off, .n_seqs = n_seqs, .read_seq0 = read_seq0, .n_reads = n_reads};
+    if ((rc = cid::check_batch(h, stride_d, bases))) return rc;
     g->sp_striped = true;
     g->sp_base = st.base;
     for (int r = 0; r < st.n; ++r) { g->sp_rows[r] = n_reads; g->sp_entries[r] = 0; g->ctx[r]->sp_rows = 0; g->ctx[r]->sp_entries = 0; }
     if (n_reads == 0) return CID_OK;
-    for (size_t r = 0; r < n_reads; ++r)   // before seq_off is read through any entry
-        if (read_seq0[r] > read_seq0[r + 1] || read_seq0[r + 1] > n_seqs) return fail(CID_ERR_INVALID, "read_seq0 not monotonic or past n_seqs at read %zu", r);
+    const cid::BatchSizes sizes = cid::walk_batch(h, stripes[0]->k, stride_d);   // before seq_off is read through any entry
+    if ((rc = cid::batch_fail(sizes.fault))) return rc;
     const uint64_t total_bases = seq_off[n_seqs];
-    if (total_bases && !bases) return fail(CID_ERR_INVALID, "null bases");
-    uint64_t zn64 = 0;   // one mask word per k-mer window of the batch (validates the offsets too)
-    if ((rc = cid_readid_stripe_mask_words(stripes[0]->k, stride_d, seq_off, read_seq0, n_reads, &zn64))) return rc;
+    const uint64_t zn64 = sizes.total_win + 1;   // one mask word per k-mer window of the batch; never empty
     uint32_t widest = 0;
     for (int r = 0; r < st.n; ++r) widest = stripes[r]->n_colors > widest ? stripes[r]->n_colors : widest;
     if ((double)n_reads * ((double)widest + 1.0) * 4.0 > 64.0 * (double)(1ull << 30) || (double)zn64 * 4.0 > 64.0 * (double)(1ull << 30))
@@ -479,15 +478,7 @@ int cid_group_stripes_readid_count_sparse(cid_group *g, cid_index *const *stripe
         int e = cid::slot_reserve(c, S_BASES, total_bases + 16, &d_b); if (e) return e;
         e = cid::slot_reserve(c, S_NK, n_reads * 4 + n_reads + 16, &d_nk); if (e) return e;
         e = cid::slot_reserve(c, S_UC, zn * 4, &d_zz); if (e) return e;
-        if (total_bases) {   // through the rank's pinned arena when the batch fits (cid::pin_reserve)
-            const uint8_t *src = bases;
-            if (uint8_t *pin = cid::pin_reserve(c, total_bases)) {
-                HIP_TRY(hipStreamSynchronize(c->stream));
-                memcpy(pin, bases, total_bases);
-                src = pin;
-            }
-            HIP_TRY(hipMemcpyAsync(d_b, src, total_bases, hipMemcpyHostToDevice, c->stream));
-        }
+        if ((e = cid::staged_upload(c, {{d_b, bases, total_bases}}, total_bases))) return e;   // through the rank's pinned arena when the batch fits
         HIP_TRY(hipMemsetAsync(d_zz, 0xFF, zn * 4, c->stream));
         dv[r] = Dev{(const uint8_t *)d_b, (uint32_t *)d_nk, (uint8_t *)d_nk + n_reads * 4};
         d_z[r] = (uint32_t *)d_zz;
@@ -505,12 +496,7 @@ int cid_group_stripes_readid_count_sparse(cid_group *g, cid_index *const *stripe
         e = cid_readid_stripe_count(c, stripes[r], dv[r].bases, seq_off, n_seqs, read_seq0, n_reads, stride_d, start_sample, 0, Cr,
                                     r == 0 ? 1 : 0, d_z[r], (uint32_t *)d_rep, dv[r].nk, dv[r].status);
         if (e) return e;
-        cid::ctx_free(c, c->sp_start); c->sp_start = nullptr;
-        cid::ctx_free(c, c->sp_col); c->sp_col = nullptr;
-        cid::ctx_free(c, c->sp_cnt); c->sp_cnt = nullptr;
-        e = cid::compact_report(c, (const uint32_t *)d_rep, Cr + 1, n_reads, &c->sp_start, &c->sp_col, &c->sp_cnt, &c->sp_entries);
-        if (e) return e;
-        c->sp_rows = n_reads;
+        if ((e = cid::store_sparse(c, (const uint32_t *)d_rep, Cr + 1, n_reads))) return e;
         g->sp_entries[r] = c->sp_entries;
         if (r == 0) {
             HIP_TRY(hipMemcpyAsync(n_kmers, dv[r].nk, n_reads * 4, hipMemcpyDeviceToHost, c->stream));

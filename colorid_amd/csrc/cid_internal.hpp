@@ -2,6 +2,7 @@
 #pragma once
 #include <vector>
 #include "cid_kernels.hpp"
+#include "cid_readbatch.hpp"
 
 struct cid_ctx;
 struct cid_index;
@@ -98,28 +99,36 @@ struct StripePass {
     bool on() const { return zero_acc || zero_in; }
 };
 
+// a batch of reads on a device (bases AND offsets), and the device arrays a read_id launch leaves its results in
+struct DevReads {
+    const uint8_t *d_bases = nullptr;
+    const uint64_t *d_seq_off = nullptr, *d_read_seq0 = nullptr;
+    size_t n_reads = 0;
+    uint32_t stride_d = 1, start_sample = 0;
+};
+struct ReadOut { uint32_t *d_report = nullptr, *d_n_kmers = nullptr; uint8_t *d_status = nullptr; };
+
 // read_id for reads that do not fit (or badly fit) a wave's LDS (cid_readlong.hip): per-read k-mer sets by workgroup-wide LDS hash
 // tables, the ordered search by slices of a read.  Everything — bases AND offsets — is on the device; the work lists are made there
 // (round 6).  d_route == NULL: every read; else only reads with d_route[r] == 1 — the others get status 2 and nothing else is written
-// for them.  clear_wide: zero the whole report first when rows are wider than 128 words (those kernels count in place).  h_seq_off /
-// h_read_seq0: the same offsets on the host when the caller has them (NULL: downloaded IF a read needs the sorting path).
+// for them.  clear_wide: zero the whole report first when rows are wider than 128 words (those kernels count in place).  host: the
+// same offsets on the host when the caller has them (NULL: downloaded IF a read needs the sorting path).
 // d_route_stats (4 words, long_route_launch's) come down into route_stats with the plan's totals.  Waits for the stream twice: for the
 // lists' sizes (64 bytes) before its kernels, and at its end.
-int readid_long(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const uint64_t *d_seq_off, const uint64_t *d_read_seq0,
-                size_t n_reads, uint32_t stride_d, uint32_t start_sample, const uint8_t *d_route, bool clear_wide, uint32_t *d_report,
-                uint32_t *d_n_kmers, uint8_t *d_status, const StripePass &sp = StripePass(), const uint64_t *h_seq_off = nullptr,
-                const uint64_t *h_read_seq0 = nullptr, const uint32_t *d_route_stats = nullptr, uint32_t *route_stats = nullptr);
+int readid_long(cid_ctx *c, const cid_index *ix, const DevReads &b, const uint8_t *d_route, bool clear_wide, const ReadOut &o,
+                const StripePass &sp = StripePass(), const HostOffsets *host = nullptr, const uint32_t *d_route_stats = nullptr,
+                uint32_t *route_stats = nullptr);
 // d_route[r] = 1: read r has at least long_from bases (the long-read path's), 0: the LDS kernels', 3: beyond cap_bytes / cap_win (what a
 // device-pointer caller stated as maxima; long_beyond_launch gives those status 3 and an empty row).  d_stats[4]: long reads, LDS-kernel
 // reads, the longest of the latter in bases and in windows.  Asynchronous.
-int long_route_launch(cid_ctx *c, const uint64_t *d_seq_off, const uint64_t *d_read_seq0, size_t n_reads, uint32_t k, uint32_t stride_d, uint64_t long_from,
-                      uint64_t cap_bytes, uint64_t cap_win, uint8_t *d_route, uint32_t *d_stats);
-int long_beyond_launch(cid_ctx *c, const uint8_t *d_route, size_t n_reads, uint32_t report_width, uint32_t *d_report, uint32_t *d_n_kmers, uint8_t *d_status);
+int long_route_launch(cid_ctx *c, const DevReads &b, uint32_t k, uint64_t long_from, uint64_t cap_bytes, uint64_t cap_win, uint8_t *d_route,
+                      uint32_t *d_stats);
+int long_beyond_launch(cid_ctx *c, const uint8_t *d_route, size_t n_reads, uint32_t report_width, const ReadOut &o);
 // the same by a global radix sort of every window of the batch (cid_kmerset_cold.hip; round 1's path): byte-string keys — k > 32, or the
-// reads with a lower-case base that readid_long hands back (merge_status: only the routed reads' statuses are written).  Offsets on the host.
-int readid_long_sorted(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const uint64_t *seq_off, const uint64_t *read_seq0,
-                       size_t n_reads, uint32_t stride_d, uint32_t start_sample, const uint8_t *route, bool clear_wide, uint32_t *d_report,
-                       uint32_t *d_n_kmers, uint8_t *d_status, const StripePass &sp = StripePass(), bool merge_status = false);
+// reads with a lower-case base that readid_long hands back (merge_status: only the routed reads' statuses are written).  Of b the bases are
+// read on the device; the offsets are host's.
+int readid_long_sorted(cid_ctx *c, const cid_index *ix, const DevReads &b, const HostOffsets &host, const uint8_t *route, bool clear_wide,
+                       const ReadOut &o, const StripePass &sp = StripePass(), bool merge_status = false);
 
 // rocPRIM behind plain calls (cid_kmerset_cold.hip — the one translation unit that includes it; its code object of some thousand kernels is
 // loaded when the first of these is called): stable LSD radix sorts on bits [b0, b1), a run-length count of sorted keys.  Asynchronous on `st`.
@@ -152,6 +161,8 @@ int index_get_records(cid_ctx *c, const cid_index *ix, uint64_t row_begin, uint6
 // dense report rows (device) -> per-row (colour, count) lists, ascending colour; outputs are ctx_alloc'ed for the caller (return them with ctx_free)
 int compact_report(cid_ctx *c, const uint32_t *d_report, uint32_t width, uint64_t n_rows, uint64_t **d_row_start, uint32_t **d_colours,
                    uint32_t **d_counts, uint64_t *n_entries);
+// ... as the ctx's sparse result (what cid_readid_sparse_fetch hands out), in place of the one it held
+int store_sparse(cid_ctx *c, const uint32_t *d_report, uint32_t width, uint64_t n_rows);
 
 // block-gzip members on the device (cid_inflate.hip): member i = in[in_off, +in_len) (header, DEFLATE data, CRC-32, ISIZE), its text to
 // out[out_off, +out_len); status[i] = 0 or the reason it is corrupt.  Asynchronous on `stream`.

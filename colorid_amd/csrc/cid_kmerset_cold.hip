@@ -295,9 +295,11 @@ hipError_t warm_cold() {
     return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_merge_status));
 }
 
-int readid_long_sorted(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const uint64_t *seq_off, const uint64_t *read_seq0,
-                       size_t n_reads, uint32_t stride_d, uint32_t start_sample, const uint8_t *route, bool clear_wide, uint32_t *d_report,
-                       uint32_t *d_n_kmers, uint8_t *d_status, const StripePass &sp, bool merge_status) {
+int readid_long_sorted(cid_ctx *c, const cid_index *ix, const DevReads &b, const HostOffsets &host, const uint8_t *route, bool clear_wide,
+                       const ReadOut &o, const StripePass &sp, bool merge_status) {
+    const uint8_t *d_bases = b.d_bases; const uint64_t *seq_off = host.seq_off, *read_seq0 = host.read_seq0;
+    const size_t n_reads = b.n_reads; const uint32_t stride_d = b.stride_d, start_sample = b.start_sample;
+    uint32_t *d_report = o.d_report, *d_n_kmers = o.d_n_kmers; uint8_t *d_status = o.d_status;
     const uint32_t k = index_k(ix);
     hipStream_t st = ctx_stream(c);
     const uint32_t msz = index_m_size(ix);           // > 0: the sets hold minimizers of length msz

@@ -1,5 +1,6 @@
 // The objects behind the ABI's opaque handles, shared by the translation units that implement them (cid_api_*.hip, cid_group*.hip).
 #pragma once
+#include <initializer_list>
 #include <vector>
 
 #include "cid_internal.hpp"
@@ -92,9 +93,22 @@ int slot_reserve(cid_ctx *c, int s, size_t bytes, void **out);
 // copied through this arena.  NULL when the request is larger than kPinMax: the caller then lets the runtime handle its memory.
 constexpr size_t kPinMax = 64u << 20;
 uint8_t *pin_reserve(cid_ctx *c, size_t bytes, size_t cap = kPinMax);
+// A few arrays between the caller's memory and the device, on the ctx stream, through pin_reserve(c, reserve): the pieces lie 16-byte
+// aligned from the arena's start (reserve covers them and whatever tail the caller keeps for later).  Without an arena (pin_staging = 0,
+// over the cap, an open inflate batch) they are copied straight between the two.  Pieces of no bytes are skipped.
+// Up: waits for the stream BEFORE it writes the arena, asynchronous after that — without an arena the caller's arrays are read until the
+// stream has run.  Down: has waited for the stream when it returns.
+struct HostPiece { void *dev; const void *host; size_t bytes; };
+struct DevPiece { void *host; const void *dev; size_t bytes; };
+int staged_upload(cid_ctx *c, std::initializer_list<HostPiece> pieces, size_t reserve);
+int staged_download(cid_ctx *c, std::initializer_list<DevPiece> pieces, size_t reserve);
 int search_count_host_input(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint32_t *freq, size_t n_kmers, bool want_unique,
                             uint32_t *unique_colour, uint64_t **d_counters);
 int check_ready(const cid_ctx *c, const cid_index *ix);
+// what every entry that takes a batch's offsets on the host checks before it looks into them: the arrays are there, the stride is
+// positive and — with reads in the batch — read_seq0 ends inside seq_off and a batch with bases has some (`bases`: host or device)
+int check_batch(const HostOffsets &h, uint32_t stride_d, const void *bases);
+int batch_fail(const BatchFault &f);   // a walk's or a rebase's refusal as the error of the call
 int index_put_records_slice(cid_index *ix, const uint8_t *records, size_t n_records, uint32_t n_colors_total, uint32_t colour_base);
 int check_not_mini(const cid_index *ix);
 }  // namespace cid

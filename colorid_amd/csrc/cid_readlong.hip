@@ -1172,45 +1172,46 @@ hipError_t warm_readlong() {
     return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_long_route));
 }
 
-int long_route_launch(cid_ctx *c, const uint64_t *d_seq_off, const uint64_t *d_read_seq0, size_t n_reads, uint32_t k, uint32_t stride_d, uint64_t long_from,
-                      uint64_t cap_bytes, uint64_t cap_win, uint8_t *d_route, uint32_t *d_stats) {
+int long_route_launch(cid_ctx *c, const DevReads &b, uint32_t k, uint64_t long_from, uint64_t cap_bytes, uint64_t cap_win, uint8_t *d_route,
+                      uint32_t *d_stats) {
     hipStream_t st = ctx_stream(c);
     HIP_TRY(hipMemsetAsync(d_stats, 0, 16, st));
-    hipLaunchKernelGGL(k_long_route, dim3(grid_for_n(n_reads)), dim3(256), 0, st, d_seq_off, d_read_seq0, (uint64_t)n_reads, k, stride_d, long_from, cap_bytes, cap_win,
-                       d_route, d_stats);
+    hipLaunchKernelGGL(k_long_route, dim3(grid_for_n(b.n_reads)), dim3(256), 0, st, b.d_seq_off, b.d_read_seq0, (uint64_t)b.n_reads, k, b.stride_d, long_from, cap_bytes,
+                       cap_win, d_route, d_stats);
     HIP_TRY(hipGetLastError());
     return CID_OK;
 }
-int long_beyond_launch(cid_ctx *c, const uint8_t *d_route, size_t n_reads, uint32_t report_width, uint32_t *d_report, uint32_t *d_n_kmers, uint8_t *d_status) {
-    hipLaunchKernelGGL(k_long_beyond_rows, dim3((unsigned)((n_reads + 3) / 4)), dim3(256), 0, ctx_stream(c), d_route, (uint64_t)n_reads, report_width, d_report,
-                       d_n_kmers, d_status);
+int long_beyond_launch(cid_ctx *c, const uint8_t *d_route, size_t n_reads, uint32_t report_width, const ReadOut &o) {
+    hipLaunchKernelGGL(k_long_beyond_rows, dim3((unsigned)((n_reads + 3) / 4)), dim3(256), 0, ctx_stream(c), d_route, (uint64_t)n_reads, report_width, o.d_report,
+                       o.d_n_kmers, o.d_status);
     HIP_TRY(hipGetLastError());
     return CID_OK;
 }
 
 // The sorting path for the reads listed in h_route (all of them: NULL): it walks the offsets on the host — a device-pointer caller's come down first.
-static int long_sorted_for(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const uint64_t *d_seq_off, const uint64_t *d_read_seq0, size_t n_reads,
-                           uint32_t stride_d, uint32_t start_sample, const uint8_t *h_route, bool clear_wide, uint32_t *d_report, uint32_t *d_n_kmers,
-                           uint8_t *d_status, const StripePass &sp, const uint64_t *h_seq_off, const uint64_t *h_read_seq0, bool merge_status) {
+static int long_sorted_for(cid_ctx *c, const cid_index *ix, const DevReads &b, const uint8_t *h_route, bool clear_wide, const ReadOut &o, const StripePass &sp,
+                           const HostOffsets *host, bool merge_status) {
     std::vector<uint64_t> so, r0;
-    if (!h_seq_off || !h_read_seq0) {
+    HostOffsets down;
+    if (!host) {
         hipStream_t st = ctx_stream(c);
-        r0.resize(n_reads + 1);
-        HIP_TRY(hipMemcpyAsync(r0.data(), d_read_seq0, (n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
+        r0.resize(b.n_reads + 1);
+        HIP_TRY(hipMemcpyAsync(r0.data(), b.d_read_seq0, (b.n_reads + 1) * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        so.resize(r0[n_reads] + 1);
-        HIP_TRY(hipMemcpyAsync(so.data(), d_seq_off, so.size() * 8, hipMemcpyDeviceToHost, st));
+        so.resize(r0[b.n_reads] + 1);
+        HIP_TRY(hipMemcpyAsync(so.data(), b.d_seq_off, so.size() * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        h_seq_off = so.data(); h_read_seq0 = r0.data();
+        down = HostOffsets{.seq_off = so.data(), .n_seqs = r0[b.n_reads], .read_seq0 = r0.data(), .n_reads = b.n_reads};
+        host = &down;
     }
-    return readid_long_sorted(c, ix, d_bases, h_seq_off, h_read_seq0, n_reads, stride_d, start_sample, h_route, clear_wide, d_report, d_n_kmers, d_status, sp,
-                              merge_status);
+    return readid_long_sorted(c, ix, b, *host, h_route, clear_wide, o, sp, merge_status);
 }
 
-int readid_long(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const uint64_t *d_seq_off, const uint64_t *d_read_seq0, size_t n_reads,
-                uint32_t stride_d, uint32_t start_sample, const uint8_t *d_route, bool clear_wide, uint32_t *d_report, uint32_t *d_n_kmers,
-                uint8_t *d_status, const StripePass &sp, const uint64_t *h_seq_off, const uint64_t *h_read_seq0, const uint32_t *d_route_stats,
-                uint32_t *route_stats) {
+int readid_long(cid_ctx *c, const cid_index *ix, const DevReads &b, const uint8_t *d_route, bool clear_wide, const ReadOut &o, const StripePass &sp,
+                const HostOffsets *host, const uint32_t *d_route_stats, uint32_t *route_stats) {
+    const uint8_t *d_bases = b.d_bases; const uint64_t *d_seq_off = b.d_seq_off, *d_read_seq0 = b.d_read_seq0;
+    const size_t n_reads = b.n_reads; const uint32_t stride_d = b.stride_d, start_sample = b.start_sample;
+    uint32_t *d_report = o.d_report, *d_n_kmers = o.d_n_kmers; uint8_t *d_status = o.d_status;
     const uint32_t k = index_k(ix);
     hipStream_t st = ctx_stream(c);
     if (n_reads >= (1ull << 31)) return fail(CID_ERR_UNSUPPORTED, "more than 2^31 reads in one batch");
@@ -1223,8 +1224,7 @@ int readid_long(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const u
             HIP_TRY(hipStreamSynchronize(st));
             for (uint8_t &b : h_route) b = b == 1 ? 1 : 0;
         }
-        return long_sorted_for(c, ix, d_bases, d_seq_off, d_read_seq0, n_reads, stride_d, start_sample, d_route ? h_route.data() : nullptr, clear_wide, d_report,
-                               d_n_kmers, d_status, sp, h_seq_off, h_read_seq0, false);
+        return long_sorted_for(c, ix, b, d_route ? h_route.data() : nullptr, clear_wide, o, sp, host, false);
     }
     const uint32_t msz = index_m_size(ix);
     const uint32_t key_len = msz ? msz : k;
@@ -1464,8 +1464,7 @@ int readid_long(cid_ctx *c, const cid_index *ix, const uint8_t *d_bases, const u
         std::vector<uint8_t> h_redo(n_reads);
         HIP_TRY(hipMemcpyAsync(h_redo.data(), d_redo.p, n_reads, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        return long_sorted_for(c, ix, d_bases, d_seq_off, d_read_seq0, n_reads, stride_d, start_sample, h_redo.data(), false, d_report, d_n_kmers, d_status, sp,
-                               h_seq_off, h_read_seq0, true);
+        return long_sorted_for(c, ix, b, h_redo.data(), false, o, sp, host, true);
     }
     return CID_OK;
 }
