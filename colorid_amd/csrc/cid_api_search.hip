@@ -123,6 +123,45 @@ int search_segments_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kme
     return CID_OK;
 }
 
+
+// The coverage search's two launches, device-resident inputs and outputs, asynchronous on the ctx stream.  d_rows: one row of rs u64 per
+// window; the host form gathers a slice chunk by chunk (d_kmers, d_flags and d_rows then start at the chunk's first window) and
+// computes the statistics once over the whole slice.
+int fill_cover_params(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, uint64_t n_kmers, cid::CoverParams &q) {
+    int rc = fill_search_params(c, ix, caller_keys(ix, d_kmers, nullptr, nullptr, n_kmers), q.s);
+    if (rc) return rc;
+    q.s.c_pad = 0;   // no histogram: the k-mer image and the hash rows are all the LDS the gather needs
+    q.s.wave_bytes = (cid::kmer_img_bytes(ix->k) + cid::kWave * ix->n_hash * 4u + 15u) & ~15u;
+    return CID_OK;
+}
+
+int search_cover_rows_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint8_t *d_flags, uint64_t n_kmers, uint64_t *d_rows) {
+    cid::CoverParams q{};
+    int rc = fill_cover_params(c, ix, d_kmers, n_kmers, q);
+    if (rc) return rc;
+    q.flags = d_flags; q.rows = d_rows;
+    HIP_TRY(cid::launch_cover_rows(q, c->stream));
+    return CID_OK;
+}
+
+int search_cover_stats_launch(cid_ctx *c, const cid_index *ix, const uint64_t *d_seg_off, const uint8_t *d_flags, size_t n_segs, uint64_t n_kmers,
+                              const uint64_t *d_rows, cid_cover *d_out) {
+    cid::CoverParams q{};
+    int rc = fill_cover_params(c, ix, nullptr, 0, q);
+    if (rc) return rc;
+    q.s.n_kmers = n_kmers;
+    q.flags = d_flags; q.rows = const_cast<uint64_t *>(d_rows); q.seg_off = d_seg_off; q.n_segs = n_segs; q.out = reinterpret_cast<uint32_t *>(d_out);
+    HIP_TRY(cid::launch_cover_stats(q, c->stream));
+    return CID_OK;
+}
+
+// one wave per (segment, 64-colour word): the grid's limit
+int check_cover_grid(const cid_index *ix, size_t n_segs) {
+    if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
+    if ((uint64_t)n_segs * ix->w64 >= (1ull << 33)) return fail(CID_ERR_INVALID, "%zu segments x %u colour words: 2^33 or more", n_segs, ix->w64);
+    return CID_OK;
+}
+
 }  // namespace
 
 namespace cid {
@@ -415,6 +454,83 @@ int cid_search_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, c
         HIP_TRY(hipMemcpyAsync(hits + s0 * C, d_hits, (s1 - s0) * C * 4, hipMemcpyDeviceToHost, c->stream));
         if (any_row_missing) HIP_TRY(hipMemcpyAsync(any_row_missing + s0, d_miss, s1 - s0, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return CID_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ coverage search (cid_cover.hip)
+
+int cid_search_cover_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_seg_off, const uint8_t *d_flags, size_t n_segs,
+                         uint64_t n_kmers, cid_cover *d_out) {
+    int rc = check_segments_index(c, ix);
+    if (rc) return rc;
+    if (n_segs == 0) return CID_OK;
+    if (!d_seg_off || !d_out || (n_kmers && !d_kmers)) return fail(CID_ERR_INVALID, "null argument");
+    if (!aligned16(d_out)) return fail(CID_ERR_INVALID, "d_out must be 16-byte aligned");
+    if ((rc = check_cover_grid(ix, n_segs))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    void *d_rows;
+    rc = slot_reserve(c, S_WORDS, (size_t)n_kmers * ix->rs * 8, &d_rows); if (rc) return rc;
+    rc = search_cover_rows_launch(c, ix, d_kmers, d_flags, n_kmers, (uint64_t *)d_rows); if (rc) return rc;
+    return search_cover_stats_launch(c, ix, d_seg_off, d_flags, n_segs, n_kmers, (const uint64_t *)d_rows, d_out);
+}
+
+// Host-pointer form.  The call is cut at whole segments into slices whose device scratch (8 * rs bytes per window) plus output (32 bytes per
+// segment and colour) fit dense_report_bytes: a segment's windows are never split, so the run statistics need no stitching.  A slice's
+// k-mers go up in chunks of upload_chunk_bytes, one k_cover_rows launch per chunk (chunks start on a tile boundary); its flags and offsets
+// go up whole, and one k_cover_stats launch ends the slice.
+int cid_search_cover(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint64_t *seg_off, const uint8_t *flags, size_t n_segs,
+                     cid_cover *out) {
+    int rc = check_segments_index(c, ix);
+    if (rc) return rc;
+    if (n_segs == 0) return CID_OK;
+    if (!seg_off || !out) return fail(CID_ERR_INVALID, "null argument");
+    if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
+    if (seg_off[0] != 0) return fail(CID_ERR_INVALID, "seg_off[0] must be 0");
+    for (size_t s = 0; s < n_segs; ++s) {
+        if (seg_off[s + 1] < seg_off[s]) return fail(CID_ERR_INVALID, "seg_off decreases at segment %zu", s);
+        if (seg_off[s + 1] - seg_off[s] >= (1ull << 32) - 128) return fail(CID_ERR_INVALID, "segment %zu has 2^32 - 128 windows or more", s);
+    }
+    if (seg_off[n_segs] && !kmers) return fail(CID_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t C = ix->n_colors, k = ix->k, row_bytes = (size_t)ix->rs * 8, cell_bytes = C * sizeof(cid_cover);
+    const unsigned long long budget = c->tune.dense_report_bytes;
+    const size_t chunk = upload_chunk_kmers(c, k);
+    std::vector<uint64_t> loc;
+    for (size_t s0 = 0; s0 < n_segs;) {
+        size_t s1 = s0;
+        while (s1 < n_segs && (seg_off[s1 + 1] - seg_off[s0]) * row_bytes + (s1 + 1 - s0) * cell_bytes <= budget) ++s1;
+        if (s1 == s0)
+            return fail(CID_ERR_UNSUPPORTED, "segment %zu (%llu windows, %zu colours) needs %llu bytes of device scratch and output: more than dense_report_bytes = %llu",
+                        s0, (unsigned long long)(seg_off[s0 + 1] - seg_off[s0]), C,
+                        (unsigned long long)((seg_off[s0 + 1] - seg_off[s0]) * row_bytes + cell_bytes), budget);
+        if ((rc = check_cover_grid(ix, s1 - s0))) return rc;
+        const uint64_t w_first = seg_off[s0], n_win = seg_off[s1] - w_first;
+        loc.resize(s1 - s0 + 1);
+        for (size_t s = s0; s <= s1; ++s) loc[s - s0] = seg_off[s] - w_first;
+        void *d_k = nullptr, *d_rows = nullptr, *d_fl = nullptr, *d_off, *d_out;
+        rc = slot_reserve(c, S_SEQOFF, loc.size() * 8, &d_off); if (rc) return rc;
+        rc = slot_reserve(c, S_REPORT, (s1 - s0) * cell_bytes, &d_out); if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(d_off, loc.data(), loc.size() * 8, hipMemcpyHostToDevice, c->stream));
+        if (n_win) {
+            rc = slot_reserve(c, S_KMERS, std::min<uint64_t>(chunk, n_win) * k, &d_k); if (rc) return rc;
+            rc = slot_reserve(c, S_WORDS, n_win * row_bytes, &d_rows); if (rc) return rc;
+            if (flags) {
+                rc = slot_reserve(c, S_NK, n_win, &d_fl); if (rc) return rc;
+                HIP_TRY(hipMemcpyAsync(d_fl, flags + w_first, n_win, hipMemcpyHostToDevice, c->stream));
+            }
+        }
+        for (uint64_t w0 = 0; w0 < n_win; w0 += chunk) {
+            const uint64_t nw = std::min<uint64_t>(chunk, n_win - w0);
+            HIP_TRY(hipMemcpyAsync(d_k, kmers + (w_first + w0) * k, nw * k, hipMemcpyHostToDevice, c->stream));
+            rc = search_cover_rows_launch(c, ix, (const uint8_t *)d_k, d_fl ? (const uint8_t *)d_fl + w0 : nullptr, nw, (uint64_t *)d_rows + w0 * ix->rs);
+            if (rc) return rc;
+        }
+        rc = search_cover_stats_launch(c, ix, (const uint64_t *)d_off, (const uint8_t *)d_fl, s1 - s0, n_win, (const uint64_t *)d_rows, (cid_cover *)d_out);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(out + s0 * C, d_out, (s1 - s0) * cell_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        s0 = s1;
     }
     return CID_OK;
 }

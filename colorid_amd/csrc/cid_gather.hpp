@@ -243,13 +243,14 @@ struct VCount {
     }
 };
 
-// Steps 1+2 of the header comment for one tile.  Returns nothing; fills ridx[s*64 + lane].
+// Steps 1+2 of the header comment for one tile.  Returns nothing; fills ridx[s*64 + lane].  A lane with `skip` set hashes nothing —
+// its k-mer's bytes may be anything — and gets row 0 like a lane past the end.
 __device__ __forceinline__ void stage_and_hash(uint32_t *img, uint32_t *ridx, const uint8_t *kmers, const uint64_t *codes,
                                                uint64_t n_kmers, uint64_t first, uint32_t k, uint32_t n, const ModMagic &mm,
-                                               int lane) {
+                                               int lane, bool skip = false) {
     wave_lds_fence();  // previous tile's readers are done with img/ridx
     if (codes) {  // packed input: 8 bytes per k-mer, ASCII re-expanded in registers (no LDS image)
-        if (first + lane < n_kmers) {
+        if (first + lane < n_kmers && !skip) {
             const uint64_t lsb = rev_fields(codes[first + lane], k);
             xxh3_seeds_from(CodeReader{lsb}, k, n, HashSel::of(mm), [&](uint32_t s, uint64_t h) { ridx[s * kWave + lane] = (uint32_t)mod_m(h, mm); });
         } else {
@@ -260,7 +261,7 @@ __device__ __forceinline__ void stage_and_hash(uint32_t *img, uint32_t *ridx, co
     }
     stage_kmers(img, kmers, n_kmers, first, k, lane);
     wave_lds_fence();
-    if (first + lane < n_kmers) {
+    if (first + lane < n_kmers && !skip) {
         xxh3_seeds(img, (uint32_t)lane * k, k, n, HashSel::of(mm), [&](uint32_t s, uint64_t h) {
             ridx[s * kWave + lane] = (uint32_t)mod_m(h, mm);
         });

@@ -178,6 +178,20 @@ struct SegmentParams {
     uint8_t *missing;          // [n_segs], or nullptr
 };
 hipError_t launch_search_segments(const SegmentParams &p, hipStream_t stream);
+// Coverage search (cid_cover.hip): the segmented search with the windows kept in order.  k_cover_rows writes every window's AND words to
+// rows[window * s.rs + word] (zeros for a window whose flag byte lacks bit 0); k_cover_stats turns the bits of segment s = windows
+// [seg_off[s], seg_off[s+1]) into out[s * n_colors + c], eight u32 per cell (include/colorid_hip.h: cid_cover).  Of `s` only the index,
+// the k-mers, wave_bytes (image + hash rows; c_pad = 0) and tiles_per_block are used; rows of at most 128 words.
+struct CoverParams {
+    SearchParams s;
+    const uint8_t *flags;      // [s.n_kmers] bit 0 = the window holds a k-mer, bit 1 = first window of its segment with that k-mer; or nullptr = 3 everywhere
+    uint64_t *rows;            // [s.n_kmers][s.rs]
+    const uint64_t *seg_off;   // [n_segs + 1], non-decreasing, seg_off[n_segs] <= s.n_kmers
+    uint64_t n_segs;           // n_segs * s.w64 < 2^33
+    uint32_t *out;             // [n_segs][n_colors][8]
+};
+hipError_t launch_cover_rows(const CoverParams &p, hipStream_t stream);
+hipError_t launch_cover_stats(const CoverParams &p, hipStream_t stream);
 hipError_t launch_put_rows(uint64_t *mat, uint32_t rs, const uint64_t *d_row_ids, const uint32_t *d_words, uint32_t w32,
                            uint64_t n_rows, hipStream_t stream);
 hipError_t launch_put_records(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, uint32_t w_off, uint32_t w32_take,

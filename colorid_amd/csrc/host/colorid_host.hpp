@@ -55,6 +55,9 @@ class KmerMap {
 int64_t auto_cutoff_from_histogram(const std::map<uint64_t, uint64_t> &histo, uint64_t n_distinct);
 void kmerize_vector(const std::vector<std::string> &v, size_t d, KmerMap &out);   // kmer.rs:87-125
 bool kmerize_string(const std::string &l, KmerMap &out);                          // kmer.rs:271-299 (false = None)
+// kmerize_vector({seq}, 1, out) with every window kept in place: k bytes (the k-mer, or filler for a window with a non-ACGT base) and one
+// flag byte (CID_WIN_VALID, CID_WIN_FIRST) per window, appended to keys / flags (`search -g -m --coverage`)
+void kmerize_windows(const std::string &seq, KmerMap &out, std::vector<uint8_t> &keys, std::vector<uint8_t> &flags);
 void kmers_from_fq_qual(const std::string &path, uint8_t q, KmerMap &out);        // kmer.rs:461-510
 void kmers_fq_pe_qual(const std::string &p1, const std::string &p2, uint8_t q, KmerMap &out);  // kmer.rs:581-655
 
@@ -385,6 +388,7 @@ namespace batch_search_pe {
 void batch_search(cid_ctx *, const std::vector<std::string> &files1, const std::vector<std::string> &files2, const Bigsi &b,
                   int64_t filter, double cov, bool gene_search, uint8_t qual_offset);     // batch_search_pe.rs:9-179
 void batch_search_mf(cid_ctx *, const std::vector<std::string> &files, const Bigsi &b, double cov);   // -g -m: every FASTA record its own query
+void batch_search_cover(cid_ctx *, const std::vector<std::string> &files, const Bigsi &b, double cov);   // -g -m --coverage: + where on the record
 }
 namespace read_id_mt_pe {
 // block-gzip (BGZF) fastq input on one GPU takes the device front end (cid_fastq_*) unless COLORID_DEVICE_FASTQ=0

@@ -505,4 +505,64 @@ void batch_search_pe::batch_search_mf(cid_ctx *ctx, const std::vector<std::strin
     batch.flush(ctx, b, emit);
 }
 
+// `search -g -m --coverage`: the rows of -g -m, selected the same way and with the same first four columns, and five more that say WHERE on
+// the record the accession hits: bases covered / record length, the longest covered stretch in bases, the number of stretches, the first
+// and the last covered base (1-based).  The record's windows go up in sequence order (kmerize_windows), batched as SegmentBatch batches
+// them: one cid_search_cover call per batch, one segment per record, 32 bytes per (record, accession) coming back.
+struct CoverBatch {
+    std::vector<uint8_t> keys, flags;
+    std::vector<uint64_t> off{0};
+    struct Record { std::string label; size_t n_kmers, length; };
+    std::vector<Record> records;
+    void push(const std::string &label, const std::string &seq, uint32_t k) {   // a record without windows is an empty segment
+        KmerMap km(k);
+        kmerize_windows(seq, km, keys, flags);
+        off.push_back(flags.size());
+        records.push_back(Record{label, km.size(), seq.size()});
+    }
+    bool full(size_t n_colors) const { return keys.size() >= SegmentBatch::kKmerBytes || records.size() * n_colors * sizeof(cid_cover) >= SegmentBatch::kHitsBytes; }
+    template <typename Emit>
+    void flush(cid_ctx *ctx, const Bigsi &b, Emit &&emit) {
+        const size_t n = records.size(), C = b.colors.size();
+        if (n == 0) return;
+        std::vector<cid_cover> cells(n * C);
+        CID_TRY(cid_search_cover(ctx, b.index, keys.data(), off.data(), flags.data(), n, cells.data()));
+        for (size_t i = 0; i < n; ++i) emit(records[i], cells.data() + i * C);
+        keys.clear();
+        flags.clear();
+        off.assign(1, 0);
+        records.clear();
+    }
+};
+
+void batch_search_pe::batch_search_cover(cid_ctx *ctx, const std::vector<std::string> &files, const Bigsi &b, double cov) {
+    const size_t C = b.colors.size();
+    const uint32_t k = (uint32_t)b.k_size;
+    CoverBatch batch;
+    auto emit = [&](const CoverBatch::Record &r, const cid_cover *row) {
+        if (r.n_kmers == 0) {
+            fprintf(stderr, "Warning! no kmers in query '%s'; maybe your kmer length is larger than your query length?\n", r.label.c_str());
+            return;
+        }
+        for (size_t c = 0; c < C; ++c) {   // generate_report_gene's rows and columns first
+            const cid_cover &h = row[c];
+            if (!h.kmers_hit) continue;
+            const double gene_match = (double)h.kmers_hit / (double)r.n_kmers;
+            if (gene_match >= cov)
+                printf("%s\t%s\t%zu\t%.3f\t%.3f\t%u\t%u\t%u\t%u\n", r.label.c_str(), b.colors[c].c_str(), r.n_kmers, gene_match,
+                       (double)h.bases_covered / (double)r.length, h.longest_run + k - 1, h.n_runs, h.first_window + 1, h.last_window + k);
+        }
+    };
+    for (const std::string &file : files) {
+        fprintf(stderr, "%s\nCounting k-mers, this may take a while!\n", file.c_str());
+        std::vector<std::string> labels, seqs;
+        read_fasta_mf(file, labels, seqs);
+        for (size_t i = 0; i < labels.size(); ++i) {
+            batch.push(labels[i], i < seqs.size() ? seqs[i] : std::string(), k);
+            if (batch.full(C)) batch.flush(ctx, b, emit);
+        }
+    }
+    batch.flush(ctx, b, emit);
+}
+
 }  // namespace colorid

@@ -1349,6 +1349,35 @@ void kmerize_vector(const std::vector<std::string> &v, size_t d, KmerMap &out) {
     for (const std::string &l : v) walk(reinterpret_cast<const uint8_t *>(l.data()), l.size(), d, true, true, out);
 }
 
+// `search -g -m --coverage`: walk()'s windows of one record (d = 1, N-filtered, upper-cased) with the windows kept in place.  Every window
+// appends k bytes to `keys` — the canonical k-mer, or k times 'N' for a window with a non-ACGT base — and one byte to `flags`:
+// CID_WIN_VALID for a window that holds a k-mer, | CID_WIN_FIRST when `out` (the record's own map) had not seen it.
+void kmerize_windows(const std::string &seq, KmerMap &out, std::vector<uint8_t> &keys, std::vector<uint8_t> &flags) {
+    const size_t k = out.k(), len = seq.size();
+    if (len < k) return;
+    const uint8_t *l = reinterpret_cast<const uint8_t *>(seq.data());
+    std::vector<uint8_t> rcbuf(len);
+    for (size_t i = 0; i < len; ++i) rcbuf[i] = switch_base(l[len - 1 - i]);
+    size_t bad_until = 0;   // windows starting below this hold a non-ACGT base
+    for (size_t i = 0; i < k - 1; ++i) if (!good_base(l[i])) bad_until = i + 1;
+    for (size_t i = 0; i + k <= len; ++i) {
+        if (!good_base(l[i + k - 1])) bad_until = i + k;
+        const size_t at = keys.size();
+        if (i < bad_until) {
+            keys.insert(keys.end(), k, (uint8_t)'N');
+            flags.push_back(0);
+            continue;
+        }
+        const uint8_t *fwd = l + i, *rc = rcbuf.data() + (len - (i + k));
+        const uint8_t *pick = memcmp(fwd, rc, k) < 0 ? fwd : rc;
+        keys.insert(keys.end(), pick, pick + k);
+        for (size_t t = at; t < at + k; ++t) keys[t] = (keys[t] >= 'a' && keys[t] <= 'z') ? (uint8_t)(keys[t] - 32) : keys[t];
+        const size_t before = out.size();
+        out.add(keys.data() + at);
+        flags.push_back((uint8_t)(CID_WIN_VALID | (out.size() > before ? CID_WIN_FIRST : 0)));
+    }
+}
+
 bool kmerize_string(const std::string &l, KmerMap &out) {
     if (l.size() < out.k()) return false;
     walk(reinterpret_cast<const uint8_t *>(l.data()), l.size(), 1, false, true, out);

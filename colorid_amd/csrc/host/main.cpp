@@ -564,10 +564,21 @@ int cmd_search(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, with_common({{'b', "bigsi", true, false}, {'q', "query", true, true}, {'r', "reverse", true, true},
                                                      {'f', "filter", true, false}, {'p', "p_shared", true, false}, {'g', "gene_search", false, false},
                                                      {'s', "perfect_search", false, false}, {'m', "multi_fasta", false, false},
-                                                     {'Q', "quality", true, false}}));
+                                                     {'Q', "quality", true, false}, {0, "coverage", false, false}}));
     for (const char *req : {"bigsi", "query"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const std::vector<std::string> files1 = a.values.at("query");
+    // -g -m --coverage: where on each record an accession hits (cid_search_cover).  FASTA records on one GPU; everything else is refused
+    // here, before the GPU context is made
+    const bool coverage = a.flags.count("coverage") != 0;
+    if (coverage) {
+        if (!a.flags.count("gene_search") || !a.flags.count("multi_fasta") || a.flags.count("perfect_search"))
+            die("error: --coverage needs -g -m (every FASTA record its own query) and does not go with -s");
+        for (const std::string &f : files1)
+            if (ends_with(f, "gz")) die("error: --coverage takes FASTA queries, not reads: %s", f.c_str());
+        if (a.has("gpus") || a.has("devices") || a.has("placement"))
+            die("error: --coverage runs on one GPU: it does not go with --gpus, --devices or --placement");
+    }
     const std::vector<std::string> files2 = a.has("reverse") && a.one("reverse") != "none" ? a.values.at("reverse") : std::vector<std::string>{};
     const int64_t filter = num_or<int64_t>(a, "filter", -1);
     const double cov = num_or<double>(a, "p_shared", 0.35);
@@ -602,7 +613,11 @@ int cmd_search(int argc, char **argv) {
     replicate(gpus, b);
     warm.join();
     phase_done("index load");
-    if (a.flags.count("perfect_search")) {
+    if (coverage) {
+        if (b.colors.size() > 8192)
+            die("error: --coverage serves indices of at most 8192 accessions; %s has %zu", a.one("bigsi").c_str(), b.colors.size());
+        batch_search_pe::batch_search_cover(ctx, files1, b, cov);
+    } else if (a.flags.count("perfect_search")) {
         if (a.flags.count("multi_fasta")) perfect_search::batch_search_mf(ctx, files1, b);
         else perfect_search::batch_search(ctx, files1, b);
     } else if (a.flags.count("gene_search") && a.flags.count("multi_fasta") &&
@@ -887,6 +902,11 @@ int main(int argc, char **argv) {
     const std::string cmd = argv[1];
     if (cmd == "--help" || cmd == "-h" || cmd == "help") {
         printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
+               "SEARCH:\n"
+               "    search -b idx.bxi -q panel.fasta -g -m [-p 0.35]               every FASTA record its own gene query\n"
+               "    search -b idx.bxi -q panel.fasta -g -m --coverage [-p 0.35]    the same rows, and where on the record the accession hits:\n"
+               "                             bases covered / record length, longest covered stretch (bases), stretches, first and last\n"
+               "                             covered base (1-based); one GPU, FASTA queries, at most 8192 accessions\n\n"
                "ENVIRONMENT:\n"
                "    COLORID_FAST_EXIT=1      leave without the GPU runtime's teardown once the results are written, closed and flushed\n"
                "                             (-0.05 to -0.15 s per run); =0, or COLORID_FULL_TEARDOWN=1: always the orderly exit\n"

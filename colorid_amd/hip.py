@@ -7,6 +7,11 @@ import numpy as np
 from ._lib import CID_ERR_INVALID, check, load_library, vp
 
 NOT_UNIQUE = 0xFFFFFFFF
+WIN_VALID, WIN_FIRST = 1, 2     # cid_search_cover's flag bits
+COVER_NONE = 0xFFFFFFFF         # first_window / last_window of a (segment, colour) without a hit
+# one cell of cid_search_cover's output (include/colorid_hip.h: cid_cover)
+COVER_DTYPE = np.dtype([(f, "<u4") for f in ("kmers_hit", "windows_hit", "bases_covered", "n_runs", "longest_run", "first_window", "last_window",
+                                             "reserved")])
 
 
 def _p(a):
@@ -203,6 +208,23 @@ class Index:
     def search_segments_dev(self, d_kmers, d_seg_off, n_segs, n_kmers, d_hits, d_missing=None):
         check(self.lib.cid_search_segments_dev(self.ctx.h, self.h, vp(d_kmers), vp(d_seg_off), n_segs, n_kmers, vp(d_hits),
                                                vp(d_missing) if d_missing else None))
+
+    # ---- coverage search: where on each query a colour hits
+    def search_cover(self, kmers, seg_off, flags=None):
+        """kmers: one canonical k-mer per window, in sequence order; segment s = windows [seg_off[s], seg_off[s+1]); flags: one byte per
+        window (WIN_VALID | WIN_FIRST; None = both everywhere) -> structured array [n_segs, n_colors] of COVER_DTYPE"""
+        kmers = np.ascontiguousarray(kmers, np.uint8).reshape(-1, self.k)
+        seg_off = np.ascontiguousarray(seg_off, np.uint64)
+        f = None if flags is None else np.ascontiguousarray(flags, np.uint8)
+        assert f is None or len(f) == len(kmers)
+        n_segs = len(seg_off) - 1
+        out = np.zeros((n_segs, self.n_colors), COVER_DTYPE)
+        check(self.lib.cid_search_cover(self.ctx.h, self.h, _p(kmers), _p(seg_off), _p(f), n_segs, _p(out)))
+        return out
+
+    def search_cover_dev(self, d_kmers, d_seg_off, d_flags, n_segs, n_kmers, d_out):
+        check(self.lib.cid_search_cover_dev(self.ctx.h, self.h, vp(d_kmers) if d_kmers else None, vp(d_seg_off) if d_seg_off else None,
+                                            vp(d_flags) if d_flags else None, n_segs, n_kmers, vp(d_out) if d_out else None))
 
     # ---- a6/a7/a9/a10
     def readid_count(self, bases, seq_off, read_seq0, d=1, start_sample=3):

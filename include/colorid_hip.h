@@ -204,6 +204,40 @@ int cid_search_segments(cid_ctx *, const cid_index *, const uint8_t *kmers, cons
 int cid_search_segments_dev(cid_ctx *, const cid_index *, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs,
                             uint64_t n_kmers, uint32_t *d_hits, uint8_t *d_any_row_missing);
 
+/* ---- Coverage search (EXTENDED): WHERE on each query an accession hits (`search -g -m --coverage`).  The segmented search with the
+ *      windows kept in sequence order.  A segment is one record: L windows numbered 0 .. L-1, window w covers bases [w, w + k_size).
+ *      `kmers` holds one canonical upper-case k-mer per window, in order (k_size ASCII bytes each), segment s = windows
+ *      [seg_off[s], seg_off[s+1]).  `flags` has one byte per window:
+ *        CID_WIN_VALID  the window holds a k-mer.  A window with a non-ACGT base stays in place with this bit clear; its k_size bytes
+ *                       may be anything, they are never hashed.
+ *        CID_WIN_FIRST  the first window of its segment that holds this k-mer (meaningful only together with VALID).
+ *      flags == NULL: every window is VALID and FIRST.
+ *      P[w][c] = window w is VALID and colour c is set in the AND of the num_hash rows of its k-mer.  An invalid window is absent for
+ *      every colour and breaks runs.  out[s * n_colors + c] is, for segment s and colour c:
+ *        kmers_hit      windows with P and FIRST: cid_search_segments' counter for the segment's distinct k-mers
+ *        windows_hit    windows with P
+ *        bases_covered  size of the union of [w, w + k_size) over the windows with P = windows_hit + the sum over interior gaps of
+ *                       min(gap, k_size - 1) + (k_size - 1 if any window hit); a gap = the absent windows between two consecutive runs
+ *        n_runs         maximal runs of consecutive windows with P
+ *        longest_run    windows of the longest run
+ *        first_window, last_window   lowest and highest w with P; both CID_COVER_NONE when there is none
+ *        reserved       0
+ *      An empty segment gives the "none" row (zeros, first_window = last_window = CID_COVER_NONE); n_segs == 0 is CID_OK.
+ *      Errors as cid_search_segments; CID_ERR_UNSUPPORTED also for a host-form segment that does not fit the budget below.
+ *      _dev: everything in device memory, d_kmers 16-byte aligned, n_kmers = d_seg_off[n_segs] windows; asynchronous on the ctx stream;
+ *      8 * row_stride_words bytes of ctx scratch per window.  The host form cuts the call at whole segments into slices whose scratch
+ *      plus output fit "dense_report_bytes", and uploads a slice's k-mers in chunks of "upload_chunk_bytes". ---- */
+#define CID_WIN_VALID 1
+#define CID_WIN_FIRST 2
+#define CID_COVER_NONE 0xFFFFFFFFu
+typedef struct cid_cover {
+    uint32_t kmers_hit, windows_hit, bases_covered, n_runs, longest_run, first_window, last_window, reserved;
+} cid_cover;
+int cid_search_cover(cid_ctx *, const cid_index *, const uint8_t *kmers, const uint64_t *seg_off, const uint8_t *flags, size_t n_segs,
+                     cid_cover *out);
+int cid_search_cover_dev(cid_ctx *, const cid_index *, const uint8_t *d_kmers, const uint64_t *d_seg_off, const uint8_t *d_flags,
+                         size_t n_segs, uint64_t n_kmers, cid_cover *d_out);
+
 /* Same, for k-mers given as 2-bit codes (k_size <= 32): one u64 per canonical UPPER-CASE k-mer, base 0 in the most
  * significant of the 2*k_size low bits, A,C,G,T = 0..3 (8 bytes of input per k-mer instead of k_size). */
 int cid_search_count_codes_dev(cid_ctx *, const cid_index *, const uint64_t *d_codes, const uint32_t *d_freq,
