@@ -44,6 +44,7 @@ SIGNATURES = {
     "cid_index_put_records_mapped": (C.c_int, [vp, vp, C.c_size_t, C.c_uint32, vp]),
     "cid_index_put_records_subset": (C.c_int, [vp, vp, C.c_size_t, C.c_uint32, vp]),
     "cid_index_put_records_folded": (C.c_int, [vp, vp, C.c_size_t, C.c_uint64]),
+    "cid_index_put_records_grouped": (C.c_int, [vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]),
     "cid_index_put_index_folded": (C.c_int, [vp, vp]),
     "cid_index_device_matrix": (C.c_int, [vp, C.POINTER(vp), C.POINTER(C.c_uint64)]),
     "cid_index_finalize": (C.c_int, [vp]),

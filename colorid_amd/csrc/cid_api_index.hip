@@ -249,6 +249,61 @@ int cid_index_put_records_folded(cid_index *ix, const uint8_t *records, size_t n
         });
 }
 
+// `collapse`: file colour c -> index colour group_of[c], any many-to-one map onto the index's colours; the plan is built once per call
+// (cid_collapse.hpp).  Each piece is checked on the device against the FILE's shape (k_pairs_check) before k_put_records_grouped stores
+// its rows and counts its columns, and the piece's counts are added to the caller's arrays when the piece is done: a refused piece
+// changes neither the matrix nor the counters.  One slot holds the counters (zeroed before every piece), the plan's words and its items.
+int cid_index_put_records_grouped(cid_index *ix, const uint8_t *records, size_t n_records, uint32_t n_colors_file, const uint32_t *group_of,
+                                  uint64_t *bits_file, uint64_t *bits_index) {
+    if (!ix || (n_records && !records) || !group_of) return fail(CID_ERR_INVALID, "null argument");
+    if (ix->finalized) return fail(CID_ERR_STATE, "index already finalized");
+    if (n_colors_file == 0) return fail(CID_ERR_INVALID, "a file of 0 colours");
+    if (n_colors_file > (1u << 20)) return fail(CID_ERR_UNSUPPORTED, "a file of %u colours > 2^20", n_colors_file);
+    std::vector<cid::GroupWord> words;
+    std::vector<cid::GroupItem> items;
+    uint32_t at = 0;
+    switch (cid::build_group_plan(group_of, n_colors_file, ix->n_colors, words, items, at)) {
+    case cid::kGroupPlanBeyond: return fail(CID_ERR_INVALID, "group_of[%u] = %u >= n_colors %u", at, group_of[at], ix->n_colors);
+    case cid::kGroupPlanEmpty: return fail(CID_ERR_INVALID, "index colour %u has no member among the file's %u colours", at, n_colors_file);
+    case cid::kGroupPlanOk: break;
+    }
+    if (n_records == 0) return CID_OK;
+    cid_ctx *c = ix->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool count = bits_file || bits_index;
+    const size_t n_cnt = (size_t)n_colors_file + ix->n_colors;
+    const size_t cnt_bytes = count ? (8 * n_cnt + 15) / 16 * 16 : 0, words_bytes = words.size() * sizeof(cid::GroupWord),
+                 items_bytes = items.size() * sizeof(cid::GroupItem);
+    void *d_plan;
+    int rc = slot_reserve(c, S_ROWIDS, cnt_bytes + words_bytes + items_bytes, &d_plan);   // counters (8 B each), words (8 B), items (12 B)
+    if (rc) return rc;
+    uint8_t *d_words = (uint8_t *)d_plan + cnt_bytes;
+    HIP_TRY(hipMemcpyAsync(d_words, words.data(), words_bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(d_words + words_bytes, items.data(), items_bytes, hipMemcpyHostToDevice, c->stream));
+    cid::GroupedParams p{};
+    p.mat32 = reinterpret_cast<uint32_t *>(ix->mat); p.rs = ix->rs;
+    p.w32_rec = (n_colors_file + 31u) / 32u; p.w32_out = ix->w32; p.n_colors_file = n_colors_file; p.n_colors = ix->n_colors;
+    p.words = (const cid::GroupWord *)d_words; p.items = (const cid::GroupItem *)(d_words + words_bytes);
+    p.counts = count ? (unsigned long long *)d_plan : nullptr;
+    std::vector<uint64_t> got(count ? n_cnt : 0);
+    // four threads a record (a workgroup of 256 walks tiles of 64): far from stage_records' thread cap
+    return stage_records(
+        c, records, n_records, p.w32_rec, 4,
+        [&](const uint32_t *d_rec, size_t nr, uint32_t *d_err) {
+            return cid::launch_pairs_check(d_rec, p.w32_rec, nr, ix->m, n_colors_file, d_err, c->stream);
+        },
+        [&](const uint32_t *d_rec, size_t nr) {
+            if (count) HIP_TRY(hipMemsetAsync(d_plan, 0, 8 * n_cnt, c->stream));
+            p.rec32 = d_rec; p.n_records = nr;
+            HIP_TRY(cid::launch_put_records_grouped(p, c->n_cu, c->stream));
+            if (count) HIP_TRY(hipMemcpyAsync(got.data(), d_plan, 8 * n_cnt, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));   // the slot is the next piece's upload buffer
+            for (uint32_t f = 0; bits_file && f < n_colors_file; ++f) bits_file[f] += got[f];
+            for (uint32_t g = 0; bits_index && g < ix->n_colors; ++g) bits_index[g] += got[n_colors_file + g];
+            return (int)CID_OK;
+        });
+}
+
 int cid_index_put_index_folded(cid_index *dst, const cid_index *src) {
     if (!dst || !src) return fail(CID_ERR_INVALID, "null argument");
     if (dst->finalized) return fail(CID_ERR_STATE, "index already finalized");

@@ -133,6 +133,93 @@ __global__ __launch_bounds__(kFoldBlock) void k_put_records_folded(uint32_t *mat
     }
 }
 
+// `collapse`: the colours of a file with n_colors_file colours through an arbitrary many-to-one map into a narrower index: output bit
+// (row, g) = OR of the record's bits over the members of g (the plan: cid_collapse.hpp), and in the same pass how many records have
+// each file colour and each output colour set — every output row is complete once its record is applied.  The piece was checked against
+// the FILE's shape before this runs (k_pairs_check under stage_records), so nothing is checked here.
+// A workgroup of four waves walks tiles_per_block tiles of 64 consecutive records, lane = record.  p.staged (64 records fit in
+// kGroupTileWords of LDS): the tile is loaded front to back, coalesced, and laid down at an odd stride of rws words per record, so that
+// the 32 lanes of a half wave reading one word of 32 records hit 32 different banks; else (records of more than 121 words) a lane reads its
+// record's words from global memory.  Wave v owns the file words and the output words == v mod 4: it evaluates its output words through the
+// plan and stores each once, with a plain store — no atomics on the matrix; bits at and beyond n_colors stay zero because no item has
+// them.  A column's count over the tile is __popcll(__ballot(bit)), 32 ballots a word, lane b keeping bit b's: staged, they add up in LDS
+// counters that only the owning wave touches (plain read-modify-write) and are flushed once per workgroup, one 64-bit atomicAdd per
+// non-zero column; unstaged, the counters do not fit and lanes 0..31 add the tile's counts to global memory (256 contiguous bytes).
+// BOUND: an LDS counter takes at most 64 * tiles_per_block <= 2^22.
+constexpr uint32_t kGroupBlock = 256, kGroupWaves = kGroupBlock / kWave;
+constexpr uint32_t kGroupTileWords = 8192;   // 32 KiB of records; the counters beside them take at most 2 * 32 * 121 words
+__device__ __forceinline__ uint32_t column_counts(uint32_t v, uint32_t lane) {   // lane b < 32 returns how many lanes have bit b of v set
+    uint32_t mine = 0;
+#pragma unroll 8   // (all 32 at once keep 32 ballots in scalar registers: they spill)
+    for (uint32_t b = 0; b < 32u; ++b) {
+        const uint32_t n = (uint32_t)__popcll(__ballot((v >> b) & 1u));
+        if (lane == b) mine = n;
+    }
+    return mine;
+}
+__global__ __launch_bounds__(kGroupBlock) void k_put_records_grouped(GroupedParams p) {
+    extern __shared__ __align__(16) uint32_t grouped_lds[];
+    const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    const uint32_t rw = (uint32_t)record_words(p.w32_rec), rws = rw | 1u;
+    uint32_t *tile = grouped_lds;                                      // [64][rws], staged only
+    uint32_t *cnt = grouped_lds + (p.staged ? kWave * rws : 0u);      // [32 * w32_rec] file colours, [32 * w32_out] output colours, staged only
+    const uint32_t n_cnt = p.staged && p.counts ? 32u * (p.w32_rec + p.w32_out) : 0u;
+    for (uint32_t i = threadIdx.x; i < n_cnt; i += kGroupBlock) cnt[i] = 0;
+    const uint64_t n_tiles = (p.n_records + kWave - 1) / kWave;
+    const uint64_t tile0 = (uint64_t)blockIdx.x * p.tiles_per_block;
+    const uint64_t tile1 = tile0 + p.tiles_per_block < n_tiles ? tile0 + p.tiles_per_block : n_tiles;
+    for (uint64_t t = tile0; t < tile1; ++t) {
+        const uint64_t r0 = t * kWave;
+        const uint32_t nr = p.n_records - r0 < kWave ? (uint32_t)(p.n_records - r0) : kWave;
+        const uint32_t *src = p.rec32 + r0 * rw;
+        __syncthreads();   // the waves are done with the previous tile (and the counters are zero)
+        if (p.staged) {
+            const uint32_t n_words = nr * rw, dq = kGroupBlock / rw, dr = kGroupBlock % rw;
+            uint32_t r = threadIdx.x / rw, q = threadIdx.x % rw;
+            for (uint32_t i = threadIdx.x; i < n_words; i += kGroupBlock) {
+                tile[r * rws + q] = src[i];
+                q += dr;
+                r += dq;
+                if (q >= rw) { q -= rw; ++r; }
+            }
+        }
+        __syncthreads();
+        const bool have = lane < nr;
+        const uint32_t *mine = src + (uint64_t)lane * rw;
+        auto word = [&](uint32_t s) { return p.staged ? tile[lane * rws + kRecordPayload + s] : mine[kRecordPayload + s]; };
+        if (p.counts)
+            for (uint32_t s = wave; s < p.w32_rec; s += kGroupWaves) {
+                const uint32_t n = column_counts(have ? word(s) : 0u, lane);
+                if (lane < 32u) {
+                    if (p.staged) cnt[32u * s + lane] += n;
+                    else if (n && 32u * s + lane < p.n_colors_file) atomicAdd(&p.counts[32u * s + lane], (unsigned long long)n);
+                }
+            }
+        const uint64_t row = have ? (p.staged ? (uint64_t)tile[lane * rws] | ((uint64_t)tile[lane * rws + 1] << 32) : record_row(mine)) : 0;
+        for (uint32_t j = wave; j < p.w32_out; j += kGroupWaves) {
+            uint32_t out = 0;
+            if (have) {
+                out = group_word(p.words[j], p.items, word);
+                p.mat32[row * (2ull * p.rs) + j] = out;   // (row < bloom_size: the piece was checked)
+            }
+            if (!p.counts) continue;   // (the same in every lane)
+            const uint32_t n = column_counts(out, lane);
+            if (lane < 32u) {
+                if (p.staged) cnt[32u * (p.w32_rec + j) + lane] += n;
+                else if (n && 32u * j + lane < p.n_colors) atomicAdd(&p.counts[p.n_colors_file + 32u * j + lane], (unsigned long long)n);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n_cnt; i += kGroupBlock) {
+        const uint32_t n = cnt[i];
+        if (n == 0) continue;
+        const uint32_t f = 32u * p.w32_rec;
+        if (i < f) { if (i < p.n_colors_file) atomicAdd(&p.counts[i], (unsigned long long)n); }
+        else if (i - f < p.n_colors) atomicAdd(&p.counts[p.n_colors_file + (i - f)], (unsigned long long)n);
+    }
+}
+
 // The same from a resident index of factor * m_dst rows and the same colours: one thread per (output row, u32 word) ORs the word of the
 // source rows row, row + m_dst, row + 2 m_dst, ... in registers — neighbouring threads read neighbouring words of every source slice — and
 // ORs the result into the output once; zero results (all-zero source rows) touch nothing.  With one chunk (gridDim.y == 1) each output
@@ -263,6 +350,23 @@ hipError_t launch_put_records_folded(uint64_t *mat, uint32_t rs, const uint32_t 
     if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;   // (a piece of stage_records is 256 MiB: at most 2^24 records)
     hipLaunchKernelGGL(k_put_records_folded, dim3((unsigned)grid), dim3(kFoldBlock), 0, stream, reinterpret_cast<uint32_t *>(mat), rs, d_records,
                        w32_rec, (uint32_t)rpb, n_records, mod);
+    return hipGetLastError();
+}
+
+// Tiles of 64 records; a workgroup walks enough of them that about eight workgroups per CU exist — each flushes its counters once — and
+// at most 2^16, the bound of the kernel's 32-bit LDS counters.  (A piece of stage_records is 256 MiB: at most 2^24 records, 2^18 tiles.)
+hipError_t launch_put_records_grouped(GroupedParams p, int n_cu, hipStream_t stream) {
+    if (p.n_records == 0) return hipSuccess;
+    const uint32_t rws = (uint32_t)record_words(p.w32_rec) | 1u;
+    p.staged = kWave * (uint64_t)rws <= kGroupTileWords ? 1u : 0u;
+    const uint64_t n_tiles = (p.n_records + kWave - 1) / kWave;
+    const uint64_t target = (uint64_t)(n_cu > 0 ? n_cu : 256) * 8;
+    const uint64_t tpb = std::min<uint64_t>(std::max<uint64_t>(1, (n_tiles + target - 1) / target), 1ull << 16);
+    const uint64_t grid = (n_tiles + tpb - 1) / tpb;
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    p.tiles_per_block = (uint32_t)tpb;
+    const size_t shmem = p.staged ? 4ull * (kWave * rws + (p.counts ? 32u * (p.w32_rec + p.w32_out) : 0u)) : 0;   // <= 32 KiB + 2 * 128 * 121 B
+    hipLaunchKernelGGL(k_put_records_grouped, dim3((unsigned)grid), dim3(kGroupBlock), shmem, stream, p);
     return hipGetLastError();
 }
 

@@ -2,6 +2,8 @@
 #pragma once
 #include "cid_device.hpp"
 
+#include "cid_collapse.hpp"   // (after the HIP runtime: CID_HD)
+
 namespace cid {
 
 constexpr int kBlock = 256;  // 4 waves; every wave works on its own 64-k-mer tiles
@@ -215,6 +217,21 @@ hipError_t launch_put_records_subset(uint64_t *mat, uint32_t rs, const uint32_t 
 hipError_t launch_put_records_folded(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, uint64_t n_records,
                                      const ModMagic &mod, hipStream_t stream);
 hipError_t launch_fold_rows(uint64_t *dst, const uint64_t *src, uint32_t rs, uint32_t w32, uint64_t m_dst, uint64_t factor, hipStream_t stream);
+// `collapse`: checked records of a file with n_colors_file colours through the many-to-one plan of cid_collapse.hpp into the index's
+// n_colors colours, rows stored (k_put_records_grouped).  counts: n_colors_file + n_colors u64 counters that the records with a file
+// colour / an output colour set are ADDED to, or nullptr.  The launcher fills in tiles_per_block and staged; n_cu sizes the grid.
+struct GroupedParams {
+    uint32_t *mat32;
+    uint32_t rs;
+    const uint32_t *rec32;
+    uint32_t w32_rec, w32_out, n_colors_file, n_colors;
+    const GroupWord *words;
+    const GroupItem *items;
+    uint64_t n_records;
+    uint32_t tiles_per_block, staged;
+    unsigned long long *counts;
+};
+hipError_t launch_put_records_grouped(GroupedParams p, int n_cu, hipStream_t stream);
 // `compare`: shared[i][j] += popcount(column i & column j) over the rows of one source (k_pairs).  The rows are w32 u32 words at
 // rows + row*stride + off (u32 units): a chunk of file records (stride 6 + w32, off 4) or a resident index's matrix (stride 2*rs, off 0).
 // shared: n_colors x n_colors u64 counters, row-major; only i <= j is added to.  The launcher fills in the grid fields.

@@ -2,6 +2,7 @@
 // and the index builder (src/build.rs:15-130) with the Bloom inserts done on the GPU.
 #include <algorithm>
 #include <cerrno>
+#include <cmath>
 #include <cstdarg>
 #include <cstring>
 #include <future>
@@ -296,7 +297,7 @@ Bigsi read_bigsi(cid_ctx *ctx, const std::string &path, int hash_variant, bool m
 
 namespace {
 
-// What `merge`, `subset`, `compare` and `fold` (cmd) have in common: the input index of a command that streams row records.  Its checks read only
+// What `merge`, `subset`, `compare`, `fold` and `collapse` (cmd) have in common: the input index of a command that streams row records.  Its checks read only
 // the header and the n_ref_kmers tail (the tail lies at header_end + n_rows x record_bytes), so a refusal costs no GPU context and no
 // pass over the rows.
 bool is_mxi(const std::string &p) { return p.size() >= 4 && p.compare(p.size() - 4, 4, ".mxi") == 0; }
@@ -465,6 +466,110 @@ void subset_records(cid_ctx *ctx, Bigsi &out, const SubsetInput &in) {
     stream_input("subset", "read", in, [&](const uint8_t *src, size_t nr) {
         return cid_index_put_records_subset(out.index, src, nr, (uint32_t)in.meta.colors.size(), in.keep_words.data());
     });
+}
+
+// collapse: no counterpart in the reference.  Beside the input's own checks, every refusal comes from the groups file.
+Bigsi collapse_check(const std::string &in_path, const std::string &out_path, const std::string &groups_path, CollapseInput &in) {
+    in.path = in_path;
+    const uint64_t file_size = stat_input("collapse", in.path, &out_path, "collapsed index");
+    // the groups file: `accession TAB group` on every non-empty line; what follows a second TAB is ignored
+    std::map<std::string, std::string> group_of_name;
+    {
+        FILE *f = fopen(groups_path.c_str(), "rb");
+        if (!f) die("collapse: can't open the groups file %s", groups_path.c_str());
+        std::string text;
+        char buf[1 << 16];
+        for (size_t got; (got = fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, got);
+        fclose(f);
+        uint64_t line_no = 0;
+        for (size_t p = 0; p < text.size();) {
+            size_t e = text.find('\n', p);
+            if (e == std::string::npos) e = text.size();
+            std::string line = text.substr(p, e - p);
+            p = e + 1;
+            ++line_no;
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (line.empty()) continue;
+            const size_t t1 = line.find('\t');
+            if (t1 == std::string::npos)
+                die("collapse: line %llu of %s has no TAB ('%s'): expected accession TAB group", (unsigned long long)line_no, groups_path.c_str(), line.c_str());
+            const size_t t2 = line.find('\t', t1 + 1);
+            const std::string acc = line.substr(0, t1), group = line.substr(t1 + 1, t2 == std::string::npos ? std::string::npos : t2 - t1 - 1);
+            if (acc.empty()) die("collapse: line %llu of %s has an empty accession name (group %s)", (unsigned long long)line_no, groups_path.c_str(), group.c_str());
+            if (group.empty()) die("collapse: line %llu of %s has an empty group name (accession %s)", (unsigned long long)line_no, groups_path.c_str(), acc.c_str());
+            if (!group_of_name.emplace(acc, group).second) die("collapse: %s lists accession %s twice", groups_path.c_str(), acc.c_str());
+        }
+    }
+    read_input_meta("collapse", in, file_size);
+    const Bigsi &a = in.meta;
+    if (a.colors.size() > (1u << 20))
+        die("collapse: %s holds %zu accessions, more than an index holds (2^20 = 1048576)", in.path.c_str(), a.colors.size());
+    std::map<std::string, uint32_t> colour_of;
+    for (uint32_t c = 0; c < a.colors.size(); ++c)
+        if (!colour_of.emplace(a.colors[c], c).second) die_accession_twice("collapse", in.path, a.colors[c]);
+    for (const auto &kv : group_of_name)
+        if (!colour_of.count(kv.first)) die("collapse: accession %s of %s is not in %s", kv.first.c_str(), groups_path.c_str(), in.path.c_str());
+    // a group may carry an accession's name only when the file puts that accession into it: two colours must not end under one name
+    for (const auto &kv : group_of_name) {
+        if (!colour_of.count(kv.second)) continue;
+        const auto own = group_of_name.find(kv.second);
+        if (own == group_of_name.end() || own->second != kv.second)
+            die("collapse: group %s of %s (accession %s) carries the name of accession %s of %s, which is not a member of it", kv.second.c_str(),
+                groups_path.c_str(), kv.first.c_str(), kv.second.c_str(), in.path.c_str());
+    }
+    std::map<std::string, std::vector<uint32_t>> groups;   // iterates in byte order, as tab_to_map: build's colour numbering
+    for (uint32_t c = 0; c < a.colors.size(); ++c) {
+        const auto it = group_of_name.find(a.colors[c]);
+        groups[it == group_of_name.end() ? a.colors[c] : it->second].push_back(c);
+    }
+    Bigsi out;
+    out.bloom_size = a.bloom_size; out.num_hash = a.num_hash; out.k_size = a.k_size; out.m_size = a.m_size;
+    in.group_of.assign(a.colors.size(), 0u);
+    for (auto &kv : groups) {
+        for (const uint32_t c : kv.second) in.group_of[c] = (uint32_t)out.colors.size();
+        out.colors.push_back(kv.first);
+        in.members.push_back(std::move(kv.second));
+    }
+    out.n_ref_kmers.assign(out.colors.size(), 0);
+    return out;
+}
+
+uint64_t collapse_n_ref(uint64_t bloom_size, uint64_t num_hash, const std::vector<uint64_t> &n_i, const std::vector<uint64_t> &bits_i,
+                        uint64_t bits_group) {
+    if (n_i.size() == 1) return n_i[0];
+    uint64_t sum = 0, most = 0;
+    bool full = bits_group >= bloom_size;
+    for (size_t i = 0; i < n_i.size(); ++i) {
+        if (n_i[i] == 0) return 0;
+        sum += n_i[i];
+        most = std::max(most, n_i[i]);
+        full = full || bits_i[i] >= bloom_size;
+    }
+    if (full) return sum;
+    const double m = (double)bloom_size, n = (double)num_hash;
+    auto est = [&](uint64_t x) { return -(m / n) * std::log1p(-(double)x / m); };
+    double members = 0.0;
+    for (const uint64_t x : bits_i) members += est(x);
+    if (!(members > 0.0)) return sum;   // empty columns: nothing to estimate from
+    const double v = std::floor((double)sum * est(bits_group) / members + 0.5);
+    return v <= (double)most ? most : v >= (double)sum ? sum : (uint64_t)v;
+}
+
+void collapse_records(cid_ctx *ctx, Bigsi &out, CollapseInput &in) {
+    create_output_index(ctx, out);
+    const Bigsi &a = in.meta;
+    fprintf(stderr, "Collapsing %zu accessions of %s into %zu groups\n", a.colors.size(), in.path.c_str(), out.colors.size());
+    in.bits_file.assign(a.colors.size(), 0);
+    in.bits_index.assign(out.colors.size(), 0);
+    stream_input("collapse", "read", in, [&](const uint8_t *src, size_t nr) {
+        return cid_index_put_records_grouped(out.index, src, nr, (uint32_t)a.colors.size(), in.group_of.data(), in.bits_file.data(),
+                                             in.bits_index.data());
+    });
+    for (size_t g = 0; g < out.colors.size(); ++g) {
+        std::vector<uint64_t> n_i, bits_i;
+        for (const uint32_t c : in.members[g]) { n_i.push_back(a.n_ref_kmers[c]); bits_i.push_back(in.bits_file[c]); }
+        out.n_ref_kmers[g] = collapse_n_ref(a.bloom_size, a.num_hash, n_i, bits_i, in.bits_index[g]);
+    }
 }
 
 // fold: no counterpart in the reference.  Beside the input's own checks, every refusal comes from the requested size.

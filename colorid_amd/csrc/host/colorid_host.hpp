@@ -309,7 +309,7 @@ Bigsi read_bigsi(cid_ctx *ctx, const std::string &path, int hash_variant, bool m
 // map the index file and start touching its pages — call it before the GPU context is made; read_bigsi then uploads from the mapping
 void bigsi_read_ahead(const std::string &path);
 void save_bigsi(const std::string &path, const Bigsi &b);                                           // bigsi.rs:51-57
-// The input index of a command that streams row records (`merge`, `subset`, `compare`, `fold`), as the command's _check read it
+// The input index of a command that streams row records (`merge`, `subset`, `compare`, `fold`, `collapse`), as the command's _check read it
 struct IndexInput {
     std::string path;
     Bigsi meta;          // header, colours and n_ref_kmers; no device index
@@ -334,6 +334,28 @@ struct SubsetInput : IndexInput {
 };
 Bigsi subset_check(const std::string &in_path, const std::string &out_path, const std::string &list_path, bool exclude, SubsetInput &in);
 void subset_records(cid_ctx *ctx, Bigsi &out, const SubsetInput &in);
+// `collapse` (no reference counterpart): several accessions of one index as one colour — the file `build` writes over a reference list
+// with one line per group whose FASTA is the members' FASTA files joined (the Bloom filter of a union is the OR of the filters).  The
+// groups file is text, `accession TAB group` per line; an accession it does not list stays a group of its own under its own name, so a
+// listed accession alone in a group is a rename.  collapse_check reads the header, the n_ref_kmers tail and the groups file and refuses
+// before any GPU work, naming file and accession or group; it returns the output's metadata — colours in byte order of the group names,
+// n_ref_kmers still zero — and the map.  collapse_records makes the index on ctx, streams the input's records through
+// cid_index_put_records_grouped (not finalized) and fills in the columns' bit counts and the output's n_ref_kmers (collapse_n_ref): the
+// device holds the OUTPUT index and one upload chunk, never the input's matrix.
+struct CollapseInput : IndexInput {
+    std::vector<uint32_t> group_of;               // input colour -> output colour
+    std::vector<std::vector<uint32_t>> members;   // output colour -> its input colours, ascending
+    std::vector<uint64_t> bits_file, bits_index;  // set bits per input / output column (collapse_records)
+};
+Bigsi collapse_check(const std::string &in_path, const std::string &out_path, const std::string &groups_path, CollapseInput &in);
+void collapse_records(cid_ctx *ctx, Bigsi &out, CollapseInput &in);
+// The n_ref_kmers of a group: the union's size is not in the index, so it is estimated from fill.  est(X) = -(m/n) ln(1 - X/m) is the
+// number of keys that set X of a filter's m bits with n hashes.  One member: its own count.  A member without a count (0: `build -m`
+// from reads): 0.  A full column (X == m) among the members or the group: the sum of the members' counts.  Else
+// round(sum n_i * est(X_group) / sum est(X_i)) — the ratio, since the keys of an .mxi are minimizers while n_ref_kmers counts k-mers —
+// clamped to [max n_i, sum n_i].
+uint64_t collapse_n_ref(uint64_t bloom_size, uint64_t num_hash, const std::vector<uint64_t> &n_i, const std::vector<uint64_t> &bits_i,
+                        uint64_t bits_group);
 // `compare` (no reference counterpart): which accessions of an index are (nearly) the same Bloom filter.  compare_check reads the header
 // and the n_ref_kmers tail and refuses before any GPU work (file missing, truncated, an accession twice).  compare_records makes the pair
 // counters on ctx, streams the input's records through cid_pairs_add_records and returns the symmetric n x n matrix shared[i][j] =

@@ -7,7 +7,8 @@
 // file `build` writes over the union of their reference lists); subset (chosen accessions of an index as an index of their own, the
 // file `build` writes over the kept lines of the reference list); compare (all-pairs similarity of an index's accessions: which of
 // them are duplicates — the question before `subset -x`); fold (an index at a smaller Bloom size that divides its own, the file
-// `build -s` writes at that size: an over-sized index shrunk, or two indices brought to one size before `merge`).
+// `build -s` writes at that size: an over-sized index shrunk, or two indices brought to one size before `merge`); collapse (several
+// accessions of an index as one colour, the rows `build` writes over the members' sequences joined: strain-level index -> taxon-level).
 // Minimizer indices (.mxi): build -m [-v M], info, read_id, batch_id.  Not provided (outside the query path): read_filter.
 #include <algorithm>
 #include <cctype>
@@ -560,6 +561,66 @@ int cmd_compare(int argc, char **argv) {
     return 0;
 }
 
+// collapse: -b OUT -i in.bxi -g GROUPS.tsv writes OUT.bxi (OUT.mxi for an .mxi input): one colour per group of accessions, row r colour g
+// the OR of row r over the members of g — the row records `build` writes over a reference list with one line per group whose FASTA is
+// the members' FASTA files joined; colours in byte order of the group names, same Bloom size, hashes, k and minimizer size.  GROUPS.tsv:
+// `accession TAB group` per line; an unlisted accession stays a group of its own, a listed one alone in its group is renamed.  The
+// union's k-mer count is not in the index: n_ref_kmers of a group of several is estimated from fill (collapse_n_ref).  OUT_groups.tsv
+// reports per output colour: group, members, n_ref_kmers, n_ref_sum (the members' counts added), bits, fill = bits/M, fp_stated =
+// false_prob(M, N, n_ref_kmers) (as `info`), fp_measured = fill^N — collapsing raises fill; `fold -p` is the tool that sizes an index by
+// that bound.  Everything that would refuse it is checked on the header, the n_ref_kmers tail and the groups file before the GPU is
+// opened; the rows then go to the device one upload chunk at a time: the device holds the output index, never the input's matrix.
+int cmd_collapse(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, with_common({{'b', "bigsi", true, false}, {'i', "input", true, true}, {'g', "groups", true, false}}));
+    for (const char *req : {"bigsi", "input", "groups"})
+        if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
+    for (const char *k : {"gpus", "devices", "placement"})
+        if (a.has(k)) die("collapse runs on one GPU (--device D): --%s is not provided", k);
+    if (a.values.at("groups").size() != 1) die("collapse takes one groups file, got %zu for --groups", a.values.at("groups").size());
+    const std::vector<std::string> &paths = a.values.at("input");
+    if (paths.size() != 1) die("collapse takes exactly one input index (-i in.bxi), got %zu: %s ...", paths.size(), paths[1].c_str());
+    const bool minimizer = ends_with(paths[0], ".mxi");
+    const std::string out = a.one("bigsi") + (minimizer ? ".mxi" : ".bxi"), report = a.one("bigsi") + "_groups.tsv";
+    CollapseInput in;
+    Bigsi b = collapse_check(paths[0], out, a.one("groups"), in);
+    phase_done("input checked");
+    printf(" Input index : %s\n Bigsi file : %s\nK-mer size: %llu\nBloom filter parameters: num hashes %llu, filter size %llu\n", in.path.c_str(),
+           out.c_str(), (unsigned long long)b.k_size, (unsigned long long)b.num_hash, (unsigned long long)b.bloom_size);
+    if (minimizer) printf("Build with minimizers, minimizer size: %llu\n", (unsigned long long)b.m_size);
+    printf("Accessions: %zu in %zu groups\n", in.meta.colors.size(), b.colors.size());
+    bigsi_read_ahead(in.path);   // pages come in beside the runtime's start-up, as for `search`
+    cid_ctx *ctx = make_ctx(a);
+    phase_done("GPU context");
+    collapse_records(ctx, b, in);
+    phase_done("records streamed and collapsed");
+    if (cid_index_finalize(b.index) != CID_OK) die("cid_index_finalize: %s", cid_last_error());
+    phase_done("finalize");
+    printf("Saving BIGSI to file.\n");
+    save_bigsi(out, b);
+    phase_done("index written");
+    {
+        FILE *f = compare_out(report);
+        const double M = (double)b.bloom_size, N = (double)b.num_hash;
+        fprintf(f, "group\tmembers\tn_ref_kmers\tn_ref_sum\tbits\tfill\tfp_stated\tfp_measured\n");
+        for (size_t g = 0; g < b.colors.size(); ++g) {
+            std::string members;
+            uint64_t sum = 0;
+            for (const uint32_t c : in.members[g]) {
+                members += (members.empty() ? "" : ",") + in.meta.colors[c];
+                sum += in.meta.n_ref_kmers[c];
+            }
+            const double fill = (double)in.bits_index[g] / M;
+            fprintf(f, "%s\t%s\t%llu\t%llu\t%llu\t%.6f\t%.6f\t%.6f\n", b.colors[g].c_str(), members.c_str(), (unsigned long long)b.n_ref_kmers[g],
+                    (unsigned long long)sum, (unsigned long long)in.bits_index[g], fill, false_prob(M, N, (double)b.n_ref_kmers[g]), std::pow(fill, N));
+        }
+        compare_close(f, report);
+    }
+    phase_done("report written");
+    cid_index_destroy(b.index);
+    cid_ctx_destroy(ctx);
+    return 0;
+}
+
 int cmd_search(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, with_common({{'b', "bigsi", true, false}, {'q', "query", true, true}, {'r', "reverse", true, true},
                                                      {'f', "filter", true, false}, {'p', "p_shared", true, false}, {'g', "gene_search", false, false},
@@ -896,17 +957,22 @@ int main(int argc, char **argv) {
     // src/main.rs:16-20: init_log() prints this banner on stdout before anything else
     printf("\n ************** initializing logger *****************\n\n");
     if (argc < 2) {
-        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare> [FLAGS]\n");
+        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare|collapse> [FLAGS]\n");
         return 1;
     }
     const std::string cmd = argv[1];
     if (cmd == "--help" || cmd == "-h" || cmd == "help") {
-        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
+        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare|collapse> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
                "SEARCH:\n"
                "    search -b idx.bxi -q panel.fasta -g -m [-p 0.35]               every FASTA record its own gene query\n"
                "    search -b idx.bxi -q panel.fasta -g -m --coverage [-p 0.35]    the same rows, and where on the record the accession hits:\n"
                "                             bases covered / record length, longest covered stretch (bases), stretches, first and last\n"
                "                             covered base (1-based); one GPU, FASTA queries, at most 8192 accessions\n\n"
+               "INDEX MAINTENANCE:\n"
+               "    collapse -b OUT -i idx.bxi -g groups.tsv      several accessions as one colour (groups.tsv: accession TAB group per line;\n"
+               "                             unlisted accessions stay as they are, a group of one is a rename): rows are the OR of the\n"
+               "                             members' rows, n_ref_kmers is estimated from fill; OUT_groups.tsv reports fill and\n"
+               "                             false-positive rates per group (see fold -p); one GPU\n\n"
                "ENVIRONMENT:\n"
                "    COLORID_FAST_EXIT=1      leave without the GPU runtime's teardown once the results are written, closed and flushed\n"
                "                             (-0.05 to -0.15 s per run); =0, or COLORID_FULL_TEARDOWN=1: always the orderly exit\n"
@@ -927,6 +993,7 @@ int main(int argc, char **argv) {
     if (cmd == "subset") return leave(cmd_subset(argc, argv));
     if (cmd == "fold") return leave(cmd_fold(argc, argv));
     if (cmd == "compare") return leave(cmd_compare(argc, argv));
+    if (cmd == "collapse") return leave(cmd_collapse(argc, argv));
     if (cmd == "debug-kmers") return cmd_debug_kmers(argc, argv);
     if (cmd == "debug-records") return cmd_debug_records(argc, argv);
     if (cmd == "batch_id") return leave(cmd_batch_id(argc, argv));

@@ -133,6 +133,21 @@ class Index:
         buf = np.frombuffer(records, np.uint8)
         check(self.lib.cid_index_put_records_folded(self.h, _p(buf), len(records) // rec, bloom_size_file))
 
+    def put_records_grouped(self, records: bytes, n_colors_file, group_of, bits_file=None, bits_index=None):
+        """raw records of a file with n_colors_file colours, stored with file colour c OR-ed into index colour group_of[c]: any
+        many-to-one map onto the index's colours (`colorid collapse`).  bits_file (uint64[n_colors_file]) and bits_index
+        (uint64[n_colors]), where given, are increased in place by the number of records with each file / index colour set"""
+        rec = 24 + 4 * ((n_colors_file + 31) // 32)
+        assert len(records) % rec == 0
+        buf = np.frombuffer(records, np.uint8)
+        gmap = np.ascontiguousarray(group_of, np.uint32)
+        assert len(gmap) == n_colors_file
+        for a, n in ((bits_file, n_colors_file), (bits_index, self.n_colors)):
+            assert a is None or (a.dtype == np.uint64 and a.flags.c_contiguous and a.flags.writeable and len(a) == n)
+        check(self.lib.cid_index_put_records_grouped(self.h, _p(buf) if len(records) else None, len(records) // rec, n_colors_file, _p(gmap),
+                                                     None if bits_file is None else _p(bits_file),
+                                                     None if bits_index is None else _p(bits_index)))
+
     def put_index_folded(self, src):
         """the rows of a finalized index of the same colours whose Bloom size is a multiple of this one's, OR-ed into row % bloom_size"""
         check(self.lib.cid_index_put_index_folded(self.h, src.h))

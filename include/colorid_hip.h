@@ -129,6 +129,24 @@ int cid_index_put_records_subset(cid_index *, const uint8_t *records, size_t n_r
  * CID_ERR_INVALID: null argument, bloom_size_file 0 or not a multiple of the index's bloom_size, or a malformed record
  * (cid_index_put_records' message); CID_ERR_STATE after finalize. */
 int cid_index_put_records_folded(cid_index *, const uint8_t *records, size_t n_records, uint64_t bloom_size_file);
+/* `colorid collapse`: several colours of a file as one colour of this index.  The records (cid_index_put_records' format) are those of a
+ * file with n_colors_file colours; file colour c becomes index colour group_of[c] (n_colors_file entries, each < the index's n_colors):
+ * ANY many-to-one map — it need not be monotonic, so renaming and reordering colours are the case of singleton groups — but every index
+ * colour must have at least one member.  Bit g of a stored row is the OR of the record's bits over the members of g: the Bloom filter
+ * of a union of k-mer sets is the OR of the members' filters, so this is the row `build` writes over the members' sequences joined.
+ * The records are taken as cid_index_put_records_subset takes them (256 MiB pieces through the ctx's upload buffer) and checked as
+ * cid_index_put_records checks them, on the device, against the FILE's shape before a piece is applied: a refused piece changes neither
+ * the matrix nor the counters.  Rows are STORED, not OR-ed: a file holds each row once, rows never put stay zero.  Call it once per
+ * chunk of a file, in any split (0 records included), then cid_index_finalize.
+ * bits_file (n_colors_file counters) and bits_index (n_colors counters) may each be NULL; else bits_file[c] is increased by the number
+ * of the call's records with file colour c set and bits_index[g] by the number with index colour g set — over a whole file the
+ * population counts of the input's and the output's columns, counted in the pass that stores the rows; exact integers, independent of
+ * scheduling.  Device memory: the index, one upload chunk, the plan (at most 12 * n_colors_file + 8 * ceil(n_colors / 32) bytes) and
+ * 8 * (n_colors_file + n_colors) bytes of counters, never the file's matrix.
+ * CID_ERR_INVALID: null argument, n_colors_file 0, a group_of entry >= n_colors, an index colour without a member, or a malformed record
+ * (cid_index_put_records' message); CID_ERR_UNSUPPORTED: n_colors_file > 2^20; CID_ERR_STATE after finalize. */
+int cid_index_put_records_grouped(cid_index *, const uint8_t *records, size_t n_records, uint32_t n_colors_file,
+                                  const uint32_t *group_of, uint64_t *bits_file, uint64_t *bits_index);
 /* The same from a resident, finalized index `src` of the same n_colors on the same device (its all-zero rows contribute nothing), OR-ed
  * into `dst`.  Device memory: both indices, nothing else.
  * CID_ERR_INVALID: null argument, a source that is not finalized, of another n_colors, on another device, or whose bloom_size is not a
