@@ -86,6 +86,8 @@ SIGNATURES = {
     "cid_bgzf_deflate_dev": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(C.c_size_t)]),
     "cid_bgzf_deflate_lz": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.POINTER(C.c_size_t)]),
     "cid_bgzf_deflate_lz_dev": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.POINTER(C.c_size_t)]),
+    "cid_bgzf_deflate_segments_bound": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "cid_bgzf_deflate_segments": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, C.POINTER(C.c_size_t)]),
     "cid_kmerset_create": (C.c_int, [vp, C.c_uint32, C.POINTER(vp)]),
     "cid_kmerset_add_seqs": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_int]),
     "cid_kmerset_add_seqs_dev": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_uint64, C.c_int]),
@@ -158,6 +160,7 @@ SIGNATURES = {
     "cid_fastq_keep_steps": (C.c_int, [vp, C.c_int]),
     "cid_fastq_filter_matches": (C.c_int, [vp, C.c_int]),
     "cid_fastq_filter": (C.c_int, [vp, vp, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    "cid_fastq_split": (C.c_int, [vp, vp, C.c_uint32, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp, C.POINTER(C.c_size_t)]),
     "cid_fastq_destroy": (None, [vp]),
     "cid_timer_start": (C.c_int, [vp]),
     "cid_timer_stop_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),

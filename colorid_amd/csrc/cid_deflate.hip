@@ -28,6 +28,14 @@
 //   HLIT + HDIST lengths (trailing unused symbols trimmed, no run codes) -> the member's size; the size of TODAY's member for the same
 //   piece is computed beside it by the same code as k_bgzf_deflate, and the LZ form is written only when it is strictly shorter:
 //   otherwise the member is k_bgzf_deflate's, byte for byte -> the tokens coded 256 a round through the same ring.
+//
+// Both kernels are templates over WHERE the pieces lie: DefContig — piece mi at mi x 65 280 of one text, the form above — or DefTable —
+// an (offset, length) per piece, for several texts in one buffer that are each cut from their own start (cid_bgzf_deflate_segments,
+// cid_fastq_split: read_id --split; no member spans two texts).  Everything behind the piece's (src, n) is the same code.
+#include <cstring>
+
+#include <vector>
+
 #include "cid_api_common.hpp"
 #include "cid_scan.hpp"
 
@@ -369,14 +377,35 @@ __device__ __forceinline__ void def_write(DefLds &S, uint8_t *slot, const uint8_
     }
 }
 
-__global__ __launch_bounds__(64) void k_bgzf_deflate(const uint8_t *text, uint64_t text_bytes, uint32_t n_members, uint8_t *slots, uint32_t *member_len,
-                                                     CrcShift1K shift) {
+// Where the pieces lie.  DefContig: one text cut every kDefBlock bytes (piece mi at mi * kDefBlock, the last one shorter).  DefTable: a
+// table of (offset, length) per piece — several texts in one buffer, each cut from ITS start (cid_bgzf_deflate_segments,
+// cid_fastq_split); every offset is a multiple of 16, as every piece of the contiguous form is.
+struct DefContig {
+    const uint8_t *text;
+    uint64_t text_bytes;
+    __device__ __forceinline__ const uint8_t *operator()(uint32_t mi, uint32_t &n) const {
+        const uint64_t left = text_bytes - (uint64_t)mi * kDefBlock;
+        n = left < kDefBlock ? (uint32_t)left : kDefBlock;   // >= 1
+        return text + (uint64_t)mi * kDefBlock;
+    }
+};
+struct DefTable {
+    const uint8_t *text;
+    const uint64_t *piece_off;
+    const uint32_t *piece_len;   // 1 .. kDefBlock
+    __device__ __forceinline__ const uint8_t *operator()(uint32_t mi, uint32_t &n) const {
+        n = piece_len[mi];
+        return text + piece_off[mi];
+    }
+};
+
+template <typename Pieces>
+__global__ __launch_bounds__(64) void k_bgzf_deflate(Pieces pieces, uint32_t n_members, uint8_t *slots, uint32_t *member_len, CrcShift1K shift) {
     __shared__ DefLds S;
     const uint32_t lane = threadIdx.x;
     for (uint32_t mi = blockIdx.x; mi < n_members; mi += gridDim.x) {
-        const uint8_t *src = text + (uint64_t)mi * kDefBlock;
-        const uint64_t left = text_bytes - (uint64_t)mi * kDefBlock;
-        const uint32_t n = left < kDefBlock ? (uint32_t)left : kDefBlock;   // >= 1
+        uint32_t n;
+        const uint8_t *src = pieces(mi, n);
         uint8_t *slot = slots + (uint64_t)mi * kDefSlot;
         __syncthreads();
         const uint32_t crc = def_crc(S, src, n, shift, lane);
@@ -433,16 +462,16 @@ __device__ __forceinline__ uint32_t lz_dist_sym(uint32_t m, uint32_t &eb, uint32
 __device__ __forceinline__ uint32_t lz_len_extra(uint32_t sym) { return sym < 265u || sym == 285u ? 0u : (sym - 261u) >> 2; }
 __device__ __forceinline__ uint32_t lz_dist_extra(uint32_t sym) { return sym < 4u ? 0u : (sym - 2u) >> 1; }
 
-__global__ __launch_bounds__(64) void k_bgzf_deflate_lz(const uint8_t *text, uint64_t text_bytes, uint32_t n_members, uint8_t *slots, uint32_t *member_len,
-                                                        uint32_t *tokens, CrcShift1K shift) {
+template <typename Pieces>
+__global__ __launch_bounds__(64) void k_bgzf_deflate_lz(Pieces pieces, uint32_t n_members, uint8_t *slots, uint32_t *member_len, uint32_t *tokens,
+                                                        CrcShift1K shift) {
     __shared__ LzLds L;
     DefLds &S = L.d;
     const uint32_t lane = threadIdx.x;
     uint32_t *tok = tokens + (uint64_t)blockIdx.x * kDefBlock;   // this workgroup's tokens: one per text byte at most
     for (uint32_t mi = blockIdx.x; mi < n_members; mi += gridDim.x) {
-        const uint8_t *src = text + (uint64_t)mi * kDefBlock;
-        const uint64_t left = text_bytes - (uint64_t)mi * kDefBlock;
-        const uint32_t n = left < kDefBlock ? (uint32_t)left : kDefBlock;   // >= 1
+        uint32_t n;
+        const uint8_t *src = pieces(mi, n);
         uint8_t *slot = slots + (uint64_t)mi * kDefSlot;
         __syncthreads();
         const uint32_t crc = def_crc(S, src, n, shift, lane);
@@ -624,6 +653,41 @@ struct DefLenIn {   // the members' lengths and a zero behind them
     __device__ uint64_t operator()(uint64_t i) const { return i < n ? p[i] : 0ull; }
 };
 
+// ---- several texts in one call (cid_bgzf_deflate_segments, cid_fastq_split): segment s holds seg_len[s] bytes at base[s] of one buffer and
+// is cut every kDefBlock bytes from ITS start, so no member spans two segments.  Two scans over the segments give every segment its base
+// (the lengths rounded up to 16: every piece then starts on a multiple of 16, as every piece of the contiguous form does — kDefBlock is
+// 16 x 4 080) and the index of its first piece; a zero behind the last segment leaves the two totals in element n.
+struct DefSegRoomIn {
+    const uint64_t *len;
+    uint64_t n;
+    __device__ uint64_t operator()(uint64_t i) const { return i < n ? (len[i] + 15ull) & ~15ull : 0ull; }
+};
+struct DefSegPiecesIn {
+    const uint64_t *len;
+    uint64_t n;
+    __device__ uint64_t operator()(uint64_t i) const { return i < n ? (len[i] + kDefBlock - 1) / kDefBlock : 0ull; }
+};
+// piece p: the segment it belongs to is the last one whose first piece is not behind p (empty segments repeat their successor's index
+// and are passed over); its text begins (p - first) x kDefBlock into the segment
+__global__ __launch_bounds__(256) void k_bgzf_piece_table(const uint64_t *seg_len, const uint64_t *base, const uint64_t *piece_first, uint32_t n_segs,
+                                                          uint32_t n_pieces, uint64_t *piece_off, uint32_t *piece_len) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pieces) return;
+    uint32_t lo = 0, hi = n_segs;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (piece_first[mid] <= p) lo = mid; else hi = mid;
+    }
+    const uint64_t at = (uint64_t)(p - (uint32_t)piece_first[lo]) * kDefBlock, left = seg_len[lo] - at;
+    piece_off[p] = base[lo] + at;
+    piece_len[p] = left < kDefBlock ? (uint32_t)left : kDefBlock;
+}
+// seg_off[s] = where segment s's members begin in the gathered output (element n_segs: the total)
+__global__ __launch_bounds__(256) void k_bgzf_seg_off(const uint64_t *member_off, const uint64_t *piece_first, uint32_t n_segs, uint64_t *seg_off) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s <= n_segs) seg_off[s] = member_off[piece_first[s]];
+}
+
 static CrcShift1K make_crc_shift_1k() {
     uint32_t tab[256];
     for (uint32_t i = 0; i < 256; ++i) {
@@ -642,22 +706,17 @@ static CrcShift1K make_crc_shift_1k() {
 
 hipError_t warm_deflate() {
     hipFuncAttributes a;
-    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_bgzf_deflate));
-    return e != hipSuccess ? e : hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_bgzf_deflate_lz));
+    const hipError_t e = hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_bgzf_deflate<DefContig>));
+    return e != hipSuccess ? e : hipFuncGetAttributes(&a, reinterpret_cast<const void *>(k_bgzf_deflate_lz<DefContig>));
 }
 
 size_t bgzf_deflate_members(size_t text_bytes) { return (text_bytes + kDefBlock - 1) / kDefBlock; }
 
-// d_text (16-byte aligned) -> d_members (>= cid_bgzf_deflate_bound bytes), d_member_len [n], *d_total = the members' bytes; scratch from
-// the ctx's block cache, returned behind the kernels on the same stream.  matches: k_bgzf_deflate_lz (its tokens: 261 120 bytes per
-// workgroup launched, more scratch of the same kind)
-int bgzf_deflate_launch(cid_ctx *c, hipStream_t st, const uint8_t *d_text, size_t text_bytes, uint8_t *d_members, uint32_t *d_member_len, uint64_t *d_total,
-                        bool matches) {
-    const size_t n = bgzf_deflate_members(text_bytes);
-    if (n == 0) {
-        if (d_total) HIP_TRY(hipMemsetAsync(d_total, 0, 8, st));
-        return CID_OK;
-    }
+// the n pieces `pieces` names -> d_members, d_member_len [n], *d_total; with d_seg_off, also where the members of each of n_segs segments
+// begin (d_piece_first [n_segs + 1]: a segment's first piece).  Scratch from the ctx's block cache, returned behind the kernels on the same stream
+template <typename Pieces>
+static int deflate_run(cid_ctx *c, hipStream_t st, Pieces pieces, size_t n, uint8_t *d_members, uint32_t *d_member_len, uint64_t *d_total, bool matches,
+                       const uint64_t *d_piece_first, size_t n_segs, uint64_t *d_seg_off) {
     if (n >= (1ull << 31)) return fail(CID_ERR_UNSUPPORTED, "cid_bgzf_deflate: more than 2^31 members in one call");
     static const CrcShift1K shift = make_crc_shift_1k();
     void *slots = nullptr, *off = nullptr, *state = nullptr, *tokens = nullptr;
@@ -670,10 +729,9 @@ int bgzf_deflate_launch(cid_ctx *c, hipStream_t st, const uint8_t *d_text, size_
     if (matches && (rc = ctx_alloc(c, (size_t)grid * kDefBlock * 4, &tokens))) { ctx_free(c, slots); ctx_free(c, off); ctx_free(c, state); return rc; }
     auto done = [&](int code) { ctx_free(c, slots); ctx_free(c, off); ctx_free(c, state); if (tokens) ctx_free(c, tokens); return code; };
     if (matches)
-        hipLaunchKernelGGL(k_bgzf_deflate_lz, dim3(grid), dim3(64), 0, st, d_text, (uint64_t)text_bytes, (uint32_t)n, (uint8_t *)slots, d_member_len,
-                           (uint32_t *)tokens, shift);
+        hipLaunchKernelGGL(k_bgzf_deflate_lz<Pieces>, dim3(grid), dim3(64), 0, st, pieces, (uint32_t)n, (uint8_t *)slots, d_member_len, (uint32_t *)tokens, shift);
     else
-        hipLaunchKernelGGL(k_bgzf_deflate, dim3(grid), dim3(64), 0, st, d_text, (uint64_t)text_bytes, (uint32_t)n, (uint8_t *)slots, d_member_len, shift);
+        hipLaunchKernelGGL(k_bgzf_deflate<Pieces>, dim3(grid), dim3(64), 0, st, pieces, (uint32_t)n, (uint8_t *)slots, d_member_len, shift);
     hipError_t e = hipGetLastError();
     // off[i] = the bytes of the members before i (the element behind the last one is zero: its prefix is the total)
     if (e == hipSuccess) e = scan_launch(DefLenIn{d_member_len, n}, ScanOutU64{(uint64_t *)off, 0ull}, n + 1, (uint64_t *)state, st);
@@ -682,8 +740,59 @@ int bgzf_deflate_launch(cid_ctx *c, hipStream_t st, const uint8_t *d_text, size_
                            (const uint64_t *)off, (uint32_t)n, d_members, d_total);
         e = hipGetLastError();
     }
+    if (e == hipSuccess && d_seg_off) {
+        hipLaunchKernelGGL(k_bgzf_seg_off, dim3((unsigned)((n_segs + 256) / 256)), dim3(256), 0, st, (const uint64_t *)off, d_piece_first, (uint32_t)n_segs, d_seg_off);
+        e = hipGetLastError();
+    }
     if (e != hipSuccess) return done(fail(CID_ERR_HIP, "cid_bgzf_deflate: %s", hipGetErrorString(e)));
     return done(CID_OK);
+}
+
+// d_text (16-byte aligned) -> d_members (>= cid_bgzf_deflate_bound bytes), d_member_len [n], *d_total = the members' bytes; scratch from
+// the ctx's block cache, returned behind the kernels on the same stream.  matches: k_bgzf_deflate_lz (its tokens: 261 120 bytes per
+// workgroup launched, more scratch of the same kind)
+int bgzf_deflate_launch(cid_ctx *c, hipStream_t st, const uint8_t *d_text, size_t text_bytes, uint8_t *d_members, uint32_t *d_member_len, uint64_t *d_total,
+                        bool matches) {
+    const size_t n = bgzf_deflate_members(text_bytes);
+    if (n == 0) {
+        if (d_total) HIP_TRY(hipMemsetAsync(d_total, 0, 8, st));
+        return CID_OK;
+    }
+    return deflate_run(c, st, DefContig{d_text, (uint64_t)text_bytes}, n, d_members, d_member_len, d_total, matches, nullptr, 0, nullptr);
+}
+
+int bgzf_segments_layout(cid_ctx *c, hipStream_t st, const uint64_t *d_seg_len, size_t n_segs, uint64_t *d_base, uint64_t *d_piece_first) {
+    if (n_segs >= (1ull << 31)) return fail(CID_ERR_UNSUPPORTED, "cid_bgzf_deflate_segments: more than 2^31 segments in one call");
+    void *state = nullptr;
+    int rc;
+    if ((rc = ctx_alloc(c, scan_state_words(n_segs + 1) * 8, &state))) return rc;
+    hipError_t e = scan_launch(DefSegRoomIn{d_seg_len, n_segs}, ScanOutU64{d_base, 0ull}, n_segs + 1, (uint64_t *)state, st);
+    if (e == hipSuccess) e = scan_launch(DefSegPiecesIn{d_seg_len, n_segs}, ScanOutU64{d_piece_first, 0ull}, n_segs + 1, (uint64_t *)state, st);
+    ctx_free(c, state);
+    return e == hipSuccess ? CID_OK : fail(CID_ERR_HIP, "cid_bgzf_deflate_segments: %s", hipGetErrorString(e));
+}
+
+int bgzf_deflate_segments_launch(cid_ctx *c, hipStream_t st, const uint8_t *d_text, const uint64_t *d_seg_len, const uint64_t *d_base,
+                                 const uint64_t *d_piece_first, size_t n_segs, size_t n_pieces, uint8_t *d_members, uint32_t *d_member_len, uint64_t *d_total,
+                                 uint64_t *d_seg_off, bool matches) {
+    if (n_pieces == 0) {
+        if (d_total) HIP_TRY(hipMemsetAsync(d_total, 0, 8, st));
+        if (d_seg_off) HIP_TRY(hipMemsetAsync(d_seg_off, 0, (n_segs + 1) * 8, st));
+        return CID_OK;
+    }
+    if (n_pieces >= (1ull << 31)) return fail(CID_ERR_UNSUPPORTED, "cid_bgzf_deflate: more than 2^31 members in one call");
+    void *piece_off = nullptr, *piece_len = nullptr;
+    int rc;
+    if ((rc = ctx_alloc(c, n_pieces * 8, &piece_off))) return rc;
+    if ((rc = ctx_alloc(c, n_pieces * 4, &piece_len))) { ctx_free(c, piece_off); return rc; }
+    hipLaunchKernelGGL(k_bgzf_piece_table, dim3((unsigned)((n_pieces + 255) / 256)), dim3(256), 0, st, d_seg_len, d_base, d_piece_first, (uint32_t)n_segs,
+                       (uint32_t)n_pieces, (uint64_t *)piece_off, (uint32_t *)piece_len);
+    const hipError_t e = hipGetLastError();
+    rc = e != hipSuccess ? fail(CID_ERR_HIP, "cid_bgzf_deflate_segments: %s", hipGetErrorString(e))
+                         : deflate_run(c, st, DefTable{d_text, (const uint64_t *)piece_off, (const uint32_t *)piece_len}, n_pieces, d_members, d_member_len, d_total,
+                                       matches, d_piece_first, n_segs, d_seg_off);
+    ctx_free(c, piece_off); ctx_free(c, piece_len);
+    return rc;
 }
 
 }  // namespace cid
@@ -757,6 +866,67 @@ int cid_bgzf_deflate_lz_dev(cid_ctx *c, const uint8_t *d_text, size_t text_bytes
 int cid_bgzf_deflate_lz(cid_ctx *c, const uint8_t *text, size_t text_bytes, uint8_t *members, size_t members_cap, size_t *members_bytes,
                         uint32_t *member_len, size_t *n_members) {
     return deflate_host(c, text, text_bytes, members, members_cap, members_bytes, member_len, n_members, true);
+}
+
+size_t cid_bgzf_deflate_segments_bound(size_t text_bytes, size_t n_segs) { return text_bytes + 31 * (text_bytes / cid::kDefBlock + n_segs); }
+
+int cid_bgzf_deflate_segments(cid_ctx *c, const uint8_t *text, const uint64_t *seg_off, size_t n_segs, int matches, uint8_t *members, size_t members_cap,
+                              size_t *members_bytes, uint32_t *member_len, uint64_t *seg_member_first, size_t *n_members) {
+    if (!c || !members_bytes || !n_members || (n_segs && (!seg_off || !seg_member_first))) return fail(CID_ERR_INVALID, "null argument");
+    *members_bytes = 0; *n_members = 0;
+    if (n_segs == 0) return CID_OK;
+    // every segment's base in the staged text and its first piece: what the two scans give on the device (from there come the tables
+    // the kernels read; from here the staging and the sizes, without a readback)
+    std::vector<uint64_t> len(n_segs), base(n_segs + 1, 0);
+    size_t np = 0;
+    for (size_t s = 0; s < n_segs; ++s) {
+        if (seg_off[s + 1] < seg_off[s]) return fail(CID_ERR_INVALID, "cid_bgzf_deflate_segments: segment %zu ends before it begins", s);
+        len[s] = seg_off[s + 1] - seg_off[s];
+        base[s + 1] = base[s] + ((len[s] + 15) & ~(uint64_t)15);
+        np += cid::bgzf_deflate_members((size_t)len[s]);
+    }
+    for (size_t s = 0; s <= n_segs; ++s) seg_member_first[s] = 0;
+    const size_t text_bytes = (size_t)(seg_off[n_segs] - seg_off[0]), room = (size_t)base[n_segs];
+    if (np == 0) return CID_OK;
+    *n_members = np;
+    if (!text || !members || !member_len) return fail(CID_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<uint8_t> staged(room);
+    for (size_t s = 0; s < n_segs; ++s) if (len[s]) memcpy(staged.data() + base[s], text + seg_off[s], (size_t)len[s]);
+    const size_t bound = cid_bgzf_deflate_segments_bound(text_bytes, n_segs);
+    std::vector<void *> held;
+    auto take = [&](size_t bytes, void **p) { const int rc = cid::ctx_alloc(c, bytes, p); if (!rc) held.push_back(*p); return rc; };
+    auto done = [&](int code) {
+        (void)hipStreamSynchronize(c->stream);
+        for (void *p : held) cid::ctx_free(c, p);
+        return code;
+    };
+    void *d_text = nullptr, *d_seg_len = nullptr, *d_base = nullptr, *d_first = nullptr, *d_out = nullptr, *d_len = nullptr, *d_total = nullptr;
+    int rc;
+    if ((rc = take(room + 16, &d_text)) || (rc = take(n_segs * 8, &d_seg_len)) || (rc = take((n_segs + 1) * 8, &d_base)) || (rc = take((n_segs + 1) * 8, &d_first)) ||
+        (rc = take(bound + 16, &d_out)) || (rc = take(np * 4, &d_len)) || (rc = take(16, &d_total)))
+        return done(rc);
+    hipStream_t st = c->stream;
+    hipError_t e = hipMemcpyAsync(d_text, staged.data(), room, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_seg_len, len.data(), n_segs * 8, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return done(fail(CID_ERR_HIP, "cid_bgzf_deflate_segments: %s", hipGetErrorString(e)));
+    if ((rc = cid::bgzf_segments_layout(c, st, (const uint64_t *)d_seg_len, n_segs, (uint64_t *)d_base, (uint64_t *)d_first))) return done(rc);
+    if ((rc = cid::bgzf_deflate_segments_launch(c, st, (const uint8_t *)d_text, (const uint64_t *)d_seg_len, (const uint64_t *)d_base, (const uint64_t *)d_first, n_segs,
+                                                np, (uint8_t *)d_out, (uint32_t *)d_len, (uint64_t *)d_total, nullptr, matches != 0)))
+        return done(rc);
+    uint64_t total = 0;
+    e = hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(member_len, d_len, np * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(seg_member_first, d_first, (n_segs + 1) * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return done(fail(CID_ERR_HIP, "cid_bgzf_deflate_segments: %s", hipGetErrorString(e)));
+    *members_bytes = (size_t)total;
+    if (total > members_cap)
+        return done(fail(CID_ERR_INVALID, "cid_bgzf_deflate_segments: the members take %llu bytes, the buffer holds %zu (cid_bgzf_deflate_segments_bound: %zu)",
+                         (unsigned long long)total, members_cap, bound));
+    e = hipMemcpy(members, d_out, (size_t)total, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return done(fail(CID_ERR_HIP, "cid_bgzf_deflate_segments: %s", hipGetErrorString(e)));
+    return done(CID_OK);
 }
 
 }  // extern "C"

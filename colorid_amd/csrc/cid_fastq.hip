@@ -189,38 +189,64 @@ __global__ __launch_bounds__(256) void k_fq_ids(FqFile f0, uint64_t n_reads, con
 }
 // cid_fastq_filter: the bytes record r of a file takes in the output, `header\nsequence\n+\nquality\n` (the reference's format!,
 // src/read_filter.rs:89-105: the lines as lines() gives them, whatever followed the '+' dropped), or none when the read is not kept
+__device__ __forceinline__ uint64_t fq_record_bytes(const FqFile &f, uint64_t r) {
+    uint32_t b, e;
+    uint64_t bytes = 5;
+    fq_line(f, 4 * r, b, e); bytes += e - b;
+    fq_line(f, 4 * r + 1, b, e); bytes += e - b;
+    fq_line(f, 4 * r + 3, b, e); bytes += e - b;
+    return bytes;
+}
 struct FqKeepIn {
     FqFile f;
     const uint8_t *keep;
     uint64_t n;
-    __device__ uint64_t operator()(uint64_t r) const {
-        if (r >= n || !keep[r]) return 0ull;
-        uint32_t b, e;
-        uint64_t bytes = 5;
-        fq_line(f, 4 * r, b, e); bytes += e - b;
-        fq_line(f, 4 * r + 1, b, e); bytes += e - b;
-        fq_line(f, 4 * r + 3, b, e); bytes += e - b;
-        return bytes;
-    }
+    __device__ uint64_t operator()(uint64_t r) const { return r >= n || !keep[r] ? 0ull : fq_record_bytes(f, r); }
 };
-// one wave per kept record: its three lines (the sequence as the input has it, not quality-masked) to out[off[r] ..)
+// cid_fastq_split: the same over the reads in output order — element j is record order[j]
+struct FqOrderIn {
+    FqFile f;
+    const uint32_t *order;
+    uint64_t n;
+    __device__ uint64_t operator()(uint64_t j) const { return j >= n ? 0ull : fq_record_bytes(f, order[j]); }
+};
+// one wave: record r's three lines (the sequence as the input has it, not quality-masked) to o
+__device__ __forceinline__ void fq_copy_record(const FqFile &f, uint64_t r, uint8_t *o, uint32_t lane) {
+    uint32_t b, e;
+    fq_line(f, 4 * r, b, e);
+    for (uint32_t j = lane; j < e - b; j += 64) o[j] = f.text[b + j];
+    o += e - b;
+    if (lane == 0) o[0] = '\n';
+    fq_line(f, 4 * r + 1, b, e);
+    for (uint32_t j = lane; j < e - b; j += 64) o[1 + j] = f.text[b + j];
+    o += 1 + (e - b);
+    if (lane == 0) { o[0] = '\n'; o[1] = '+'; o[2] = '\n'; }
+    fq_line(f, 4 * r + 3, b, e);
+    for (uint32_t j = lane; j < e - b; j += 64) o[3 + j] = f.text[b + j];
+    if (lane == 0) o[3 + (e - b)] = '\n';
+}
+// one wave per kept record, to out[off[r] ..)
 __global__ __launch_bounds__(256) void k_fq_filter_copy(FqFile f, const uint8_t *keep, uint64_t n, const uint64_t *off, uint8_t *out) {
     const uint32_t lane = threadIdx.x & 63;
-    for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (uint64_t)gridDim.x * 4) {
-        if (!keep[r]) continue;
-        uint8_t *o = out + off[r];
-        uint32_t b, e;
-        fq_line(f, 4 * r, b, e);
-        for (uint32_t j = lane; j < e - b; j += 64) o[j] = f.text[b + j];
-        o += e - b;
-        if (lane == 0) o[0] = '\n';
-        fq_line(f, 4 * r + 1, b, e);
-        for (uint32_t j = lane; j < e - b; j += 64) o[1 + j] = f.text[b + j];
-        o += 1 + (e - b);
-        if (lane == 0) { o[0] = '\n'; o[1] = '+'; o[2] = '\n'; }
-        fq_line(f, 4 * r + 3, b, e);
-        for (uint32_t j = lane; j < e - b; j += 64) o[3 + j] = f.text[b + j];
-        if (lane == 0) o[3 + (e - b)] = '\n';
+    for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (uint64_t)gridDim.x * 4)
+        if (keep[r]) fq_copy_record(f, r, out + off[r], lane);
+}
+// cid_fastq_split: bin b holds the reads order[bin_first[b] .. bin_first[b + 1]), off[j] = the bytes of the records before order[j];
+// bin_len[b] = the bytes of its records (k_fq_split_bin_len), and one wave per record copies it to base[b] + its offset inside the bin
+__global__ __launch_bounds__(256) void k_fq_split_bin_len(const uint64_t *off, const uint32_t *bin_first, uint32_t n_bins, uint64_t *bin_len) {
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < n_bins) bin_len[b] = off[bin_first[b + 1]] - off[bin_first[b]];
+}
+__global__ __launch_bounds__(256) void k_fq_split_copy(FqFile f, const uint32_t *order, uint64_t n, const uint64_t *off, const uint32_t *bin_first, uint32_t n_bins,
+                                                       const uint64_t *base, uint8_t *out) {
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint64_t j = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); j < n; j += (uint64_t)gridDim.x * 4) {
+        uint32_t lo = 0, hi = n_bins;   // the last bin that begins at or before j (empty bins begin where their successor does)
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (bin_first[mid] <= j) lo = mid; else hi = mid;
+        }
+        fq_copy_record(f, order[j], out + base[lo] + (off[j] - off[bin_first[lo]]), lane);
     }
 }
 
@@ -309,7 +335,7 @@ struct cid_fastq {
     hipStream_t fetch_stream = nullptr;   // results leave beside the classifier of the NEXT step, not behind it
     // CID_FASTQ_TIMING=1: host time per part of a step, printed when the reader is destroyed
     bool timing = false;
-    double ms_part[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double ms_part[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // [7 ..]: the parts of cid_fastq_split
     uint64_t n_steps = 0;
 };
 
@@ -419,6 +445,9 @@ void cid_fastq_destroy(cid_fastq *fq) {
         fprintf(stderr, "cid_fastq: %llu steps; host ms: waiting for the inflate %.1f, member checks + text append %.1f, line ends + record count %.1f, "
                 "records + scans %.1f, pack + launch of the classifier %.1f, report compaction + drain %.1f, carry %.1f\n", (unsigned long long)fq->n_steps,
                 fq->ms_part[0], fq->ms_part[1], fq->ms_part[2], fq->ms_part[3], fq->ms_part[4], fq->ms_part[5], fq->ms_part[6]);
+    if (fq->timing && fq->ms_part[7] > 0)
+        fprintf(stderr, "cid_fastq: cid_fastq_split: host ms ordering the reads by bin (counting sort) %.1f, order up + sizes and layout + first wait %.1f, "
+                "scratch + copy + coder + second wait %.1f, members to the host %.1f\n", fq->ms_part[7], fq->ms_part[8], fq->ms_part[9], fq->ms_part[10]);
     cid_ctx *c = fq->ctx;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
@@ -898,6 +927,88 @@ int cid_fastq_filter(cid_fastq *fq, const uint8_t *keep, int file, uint8_t *memb
                     (unsigned long long)total, members_cap);
     HIP_TRY(hipMemcpyAsync(members, d_out.p, (size_t)total, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return CID_OK;
+}
+
+int cid_fastq_split(cid_fastq *fq, const uint32_t *bin, uint32_t n_bins, int file, uint8_t *members, size_t members_cap, size_t *members_bytes,
+                    uint64_t *bin_off, uint64_t *bin_reads, size_t *n_members) {
+    if (!fq || !members_bytes || !n_members || file < 0 || file >= fq->n_files) return fail(CID_ERR_INVALID, "bad argument");
+    *members_bytes = 0; *n_members = 0;
+    if (n_bins == 0) return fail(CID_ERR_INVALID, "cid_fastq_split: no bins");
+    if (n_bins == CID_SPLIT_DROP) return fail(CID_ERR_INVALID, "cid_fastq_split: %u bins: that value marks a dropped read", n_bins);
+    if (!bin_off || !bin_reads) return fail(CID_ERR_INVALID, "null argument");
+    if (!fq->keep_steps) return fail(CID_ERR_STATE, "cid_fastq_split: the reader keeps no steps (cid_fastq_keep_steps)");
+    if (!fq->gen.valid) return fail(CID_ERR_STATE, "cid_fastq_split: no finished step to split");
+    const uint64_t n = fq->gen.n;
+    if (n && !bin) return fail(CID_ERR_INVALID, "null argument");
+    // ---- the order (host): a stable counting sort of the step's reads by bin — one pass to count, one to place
+    PartClock pc(fq);
+    std::vector<uint32_t> first((size_t)n_bins + 1, 0);
+    uint64_t kept = 0;
+    for (uint64_t r = 0; r < n; ++r) {
+        const uint32_t b = bin[r];
+        if (b == CID_SPLIT_DROP) continue;
+        if (b >= n_bins) return fail(CID_ERR_INVALID, "cid_fastq_split: read %llu goes to bin %u of %u", (unsigned long long)r, b, n_bins);
+        ++first[(size_t)b + 1];
+        ++kept;
+    }
+    for (uint32_t b = 0; b < n_bins; ++b) { bin_reads[b] = first[(size_t)b + 1]; bin_off[b] = 0; first[(size_t)b + 1] += first[b]; }
+    bin_off[n_bins] = 0;
+    if (kept == 0) return CID_OK;
+    if (!fq->gen.text[file] || !fq->gen.nl[file]) return fail(CID_ERR_STATE, "cid_fastq_split: the step's text was not kept (its _end failed)");
+    std::vector<uint32_t> order((size_t)kept), at(first.begin(), first.end() - 1);
+    for (uint64_t r = 0; r < n; ++r)
+        if (bin[r] != CID_SPLIT_DROP) order[at[bin[r]]++] = (uint32_t)r;
+    pc.lap(7);
+    cid_ctx *c = fq->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;   // (behind a classifier launched since: the step's buffers and the block cache are this stream's)
+    int rc;
+    Buf<uint8_t> d_text(c), d_out(c);
+    Buf<uint64_t> off(c), state(c), bin_len(c), base(c), piece_first(c), d_bin_off(c), d_total(c);
+    Buf<uint32_t> d_order(c), d_first(c), d_len(c);
+    if ((rc = d_order.alloc(kept)) || (rc = d_first.alloc((size_t)n_bins + 1)) || (rc = off.alloc(kept + 1)) || (rc = state.alloc(cid::scan_state_words(kept + 1))) ||
+        (rc = bin_len.alloc(n_bins)) || (rc = base.alloc((size_t)n_bins + 1)) || (rc = piece_first.alloc((size_t)n_bins + 1)) ||
+        (rc = d_bin_off.alloc((size_t)n_bins + 1)) || (rc = d_total.alloc(2)))
+        return rc;
+    // (pageable sources: either copy has left the host's vectors when its call returns)
+    HIP_TRY(hipMemcpyAsync(d_order.p, order.data(), kept * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_first.p, first.data(), ((size_t)n_bins + 1) * 4, hipMemcpyHostToDevice, st));
+    const cid::FqFile F{fq->gen.text[file], fq->gen.nl[file], nullptr, fq->gen.len[file]};
+    // ---- sizes and layout (device): the records' offsets in output order, every bin's bytes, its 16-byte-aligned base and first piece
+    HIP_TRY(cid::scan_launch(cid::FqOrderIn{F, d_order.p, kept}, cid::ScanOutU64{off.p, 0ull}, kept + 1, state.p, st));
+    hipLaunchKernelGGL(cid::k_fq_split_bin_len, dim3((n_bins + 255) / 256), dim3(256), 0, st, (const uint64_t *)off.p, (const uint32_t *)d_first.p, n_bins, bin_len.p);
+    HIP_TRY(hipGetLastError());
+    if ((rc = cid::bgzf_segments_layout(c, st, bin_len.p, n_bins, base.p, piece_first.p))) { (void)hipStreamSynchronize(st); return rc; }
+    uint64_t room = 0, np = 0;
+    HIP_TRY(hipMemcpyAsync(&room, base.p + n_bins, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&np, piece_first.p + n_bins, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    pc.lap(8);
+    const size_t bound = cid_bgzf_deflate_segments_bound((size_t)room, n_bins);
+    if ((rc = d_text.alloc(room + 16)) || (rc = d_out.alloc(bound + 16)) || (rc = d_len.alloc(np))) return rc;
+    unsigned grid = (unsigned)((kept + 3) / 4);
+    if (grid > 16384) grid = 16384;
+    hipLaunchKernelGGL(cid::k_fq_split_copy, dim3(grid), dim3(256), 0, st, F, (const uint32_t *)d_order.p, kept, (const uint64_t *)off.p, (const uint32_t *)d_first.p,
+                       n_bins, (const uint64_t *)base.p, d_text.p);
+    HIP_TRY(hipGetLastError());
+    if ((rc = cid::bgzf_deflate_segments_launch(c, st, d_text.p, bin_len.p, base.p, piece_first.p, n_bins, (size_t)np, d_out.p, d_len.p, d_total.p, d_bin_off.p,
+                                                fq->filter_matches))) { (void)hipStreamSynchronize(st); return rc; }
+    uint64_t total = 0;
+    std::vector<uint64_t> h_bin_off((size_t)n_bins + 1);
+    HIP_TRY(hipMemcpyAsync(&total, d_total.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_bin_off.data(), d_bin_off.p, ((size_t)n_bins + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    pc.lap(9);
+    *members_bytes = (size_t)total;
+    if (total > members_cap || !members)
+        return fail(CID_ERR_INVALID, "cid_fastq_split: the members take %llu bytes, the buffer holds %zu: call again with that much room",
+                    (unsigned long long)total, members_cap);
+    *n_members = (size_t)np;
+    memcpy(bin_off, h_bin_off.data(), ((size_t)n_bins + 1) * 8);
+    HIP_TRY(hipMemcpyAsync(members, d_out.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    pc.lap(10);
     return CID_OK;
 }
 

@@ -188,6 +188,15 @@ hipError_t warm_deflate();
 // *d_total = their bytes; queued on `stream`, which must be the stream the ctx's block cache is ordered on (c->stream)
 int bgzf_deflate_launch(cid_ctx *c, hipStream_t stream, const uint8_t *d_text, size_t text_bytes, uint8_t *d_members, uint32_t *d_member_len, uint64_t *d_total,
                         bool matches = false);   // matches: with LZ77 matches (cid_bgzf_deflate_lz)
+// The segmented form (cid_bgzf_deflate_segments, cid_fastq_split): n_segs texts in one buffer, each cut every 65 280 bytes from its own start.
+// _layout: d_seg_len [n_segs] -> d_base [n_segs + 1] (segment s's text at d_text + base[s], the lengths rounded up to 16; element n_segs =
+// the room the texts take) and d_piece_first [n_segs + 1] (the index of s's first piece; element n_segs = the pieces).  _launch: the
+// n_pieces members back to back at d_members (text room + 31 per piece), their lengths, *d_total, and (d_seg_off [n_segs + 1], may be null)
+// where each segment's members begin.  Same stream rule as bgzf_deflate_launch.
+int bgzf_segments_layout(cid_ctx *c, hipStream_t stream, const uint64_t *d_seg_len, size_t n_segs, uint64_t *d_base, uint64_t *d_piece_first);
+int bgzf_deflate_segments_launch(cid_ctx *c, hipStream_t stream, const uint8_t *d_text, const uint64_t *d_seg_len, const uint64_t *d_base,
+                                 const uint64_t *d_piece_first, size_t n_segs, size_t n_pieces, uint8_t *d_members, uint32_t *d_member_len, uint64_t *d_total,
+                                 uint64_t *d_seg_off, bool matches);
 hipError_t ctx_side_streams(cid_ctx *c, hipStream_t out[4]);   // created on first use; any thread
 
 }  // namespace cid

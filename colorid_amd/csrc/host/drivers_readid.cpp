@@ -3,6 +3,8 @@
 // plus the CPU-side tail (kmer_poll_plus, the counts file of src/reports.rs).  File formats follow the reference.
 #include <fcntl.h>
 #include <sys/mman.h>
+#include <dirent.h>
+#include <sys/resource.h>
 #include <sys/stat.h>
 #include "drivers_common.hpp"
 #include <unistd.h>
@@ -140,6 +142,7 @@ struct Counted {   // one batch after the GPU stage: each read's non-zero (colou
     std::vector<uint64_t> row_start;
     std::vector<uint32_t> colours, counts;
     std::vector<uint8_t> keep;   // --taxon: per read, whether its label passes the filter (filled by the poll)
+    std::vector<uint32_t> bin;   // --split: per read, the bin of its label (filled by the poll)
 };
 void count_batch(cid_ctx *ctx, const Bigsi &b, Counted &c, size_t d, size_t start_sample) {
     ReadBatch &rb = c.rb;
@@ -201,6 +204,9 @@ void poll_batch(const Bigsi &b, Counted &c, double fp_correct, const std::vector
     // --taxon: read_filter's tab_to_map keeps a row when its second column contains the query (read_filter.rs:21)
     const bool filter = g_taxon.on;
     if (filter) c.keep.assign(n, 0);
+    // --split: the label's bin by equality — the tally's indices, with the rejects told apart (C + 2 no_significant_hits, C + 3 several top hits)
+    const bool split = g_taxon.split;
+    if (split) c.bin.assign(n, 0);
     auto passes = [&](const std::string &o, size_t label_begin) {
         const bool hit = g_taxon.taxon.empty() || memmem(o.data() + label_begin, o.size() - label_begin, g_taxon.taxon.data(), g_taxon.taxon.size()) != nullptr;
         return (uint8_t)(hit != g_taxon.exclude);
@@ -220,6 +226,7 @@ void poll_batch(const Bigsi &b, Counted &c, double fp_correct, const std::vector
                 if (filter) { const size_t lb = o.size() + 1; o += "\ttoo_short"; c.keep[r] = passes(o, lb); o += "\t0\t0\taccept\t0\n"; }
                 else o += "\ttoo_short\t0\t0\taccept\t0\n";
                 ++a[C + 1];
+                if (split) c.bin[r] = (uint32_t)(C + 1);
                 continue;
             }
             const size_t e0 = (size_t)c.row_start[r], ne = (size_t)(c.row_start[r + 1] - c.row_start[r]);
@@ -227,13 +234,14 @@ void poll_batch(const Bigsi &b, Counted &c, double fp_correct, const std::vector
             const Poll p = poll_core(c.colours.data() + e0, c.counts.data() + e0, ne, c.nk[r], C, fp, fp_correct, sig.data());
             o += '\t';
             const size_t label_begin = o.size();
-            if (p.kind == 0) { o += "no_hits"; ++a[C]; }
-            else if (p.kind == 1) { o += "no_significant_hits"; ++a[C + 2]; }
+            if (p.kind == 0) { o += "no_hits"; ++a[C]; if (split) c.bin[r] = (uint32_t)C; }
+            else if (p.kind == 1) { o += "no_significant_hits"; ++a[C + 2]; if (split) c.bin[r] = (uint32_t)(C + 2); }
             else {
                 bool first = true;
                 for (size_t e = 0; e < ne; ++e)
                     if (sig[e]) { if (!first) o += ','; first = false; o += b.colors[c.colours[e0 + e]]; }
                 ++a[p.n_top == 1 ? p.first_top : C + 2];
+                if (split) c.bin[r] = p.n_top == 1 ? p.first_top : (uint32_t)(C + 3);
             }
             if (filter) c.keep[r] = passes(o, label_begin);
             o += '\t'; append_u64(o, p.best);
@@ -324,6 +332,14 @@ class BatchClassifier {
         keep_ready_.pop_front();
         return k;
     }
+    // --split: the same for the bins
+    std::vector<uint32_t> take_bins() {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_keep_.wait(lk, [&] { return !bins_ready_.empty(); });
+        std::vector<uint32_t> k = std::move(bins_ready_.front());
+        bins_ready_.pop_front();
+        return k;
+    }
     uint64_t finish() {
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -383,6 +399,7 @@ class BatchClassifier {
             fprintf(stderr, progress_fmt_, (unsigned long long)n_reads_);
             std::lock_guard<std::mutex> lk(mu_);
             if (g_taxon.on) { keep_ready_.push_back(std::move(c->keep)); c->keep.clear(); cv_keep_.notify_one(); }
+            if (g_taxon.split) { bins_ready_.push_back(std::move(c->bin)); c->bin.clear(); cv_keep_.notify_one(); }
             if (!ids_stay_) {   // (the device front end fills a Counted's ids itself: they stay with it, sized, for the next stretch)
                 c->rb.clear();
                 if (spare_.size() < 16) spare_.push_back(std::move(c->rb));
@@ -402,6 +419,7 @@ class BatchClassifier {
     std::mutex mu_;
     std::condition_variable cv_work_, cv_room_, cv_counted_, cv_polled_, cv_keep_;
     std::deque<std::vector<uint8_t>> keep_ready_;
+    std::deque<std::vector<uint32_t>> bins_ready_;
     std::deque<ReadBatch> queue_;
     std::deque<std::unique_ptr<Counted>> counted_;
     std::vector<std::unique_ptr<Counted>> free_counted_;
@@ -481,13 +499,45 @@ namespace {
 // finishes the classifier, empties the output and runs the whole input through the host front end (which takes such reads) — an input
 // that the host path completes is never a hard failure here.
 enum FrontEnd { kFrontEndDone, kFrontEndNotMine, kFrontEndRestart };
+// One block-gzip output file of either mode: created (and registered with remove_on_die) by open, fed whole members, closed behind the
+// 28-byte end-of-file block and released (keep_on_die) by finish.  `what` names the file in the reference's words when it cannot be made.
+struct BgzfOut {
+    std::string path;
+    FILE *f = nullptr;
+    void open(const std::string &p, const char *what) {
+        path = p;
+        f = fopen(path.c_str(), "wb");
+        if (f) remove_on_die(path);
+        if (!f) die("could not create %s!", what);
+    }
+    void write(const uint8_t *members, size_t bytes, const char *what) {
+        if (bytes && fwrite(members, 1, bytes, f) != bytes) die("could not write %s!", what);
+    }
+    void close() {
+        static const unsigned char eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        const bool ok = fwrite(eof_block, 1, sizeof(eof_block), f) == sizeof(eof_block);
+        const bool closed = fclose(f) == 0;
+        f = nullptr;
+        if (!ok || !closed) die("Could not close new read file");
+    }
+};
+static const char *mate_name(size_t n_files, size_t i) { return n_files == 2 ? (i ? "R2" : "R1") : "R1"; }
+// a step's members in page-locked memory: a share of the input's size to begin with, grown when a step takes more
+static void reserve_members(PinnedBuf &buf, size_t nf, const std::vector<std::string> &fq) {
+    size_t in_bytes = 0;
+    for (size_t i = 0; i < nf; ++i) {
+        struct stat sb;
+        if (stat(fq[i].c_str(), &sb) == 0) in_bytes = std::max(in_bytes, (size_t)sb.st_size);
+    }
+    buf.reserve(std::min<size_t>((size_t)96 << 20, 8 * in_bytes + (64u << 10)));
+}
+
 // --taxon: the output files of a sample, PREFIX_TAXON.fq.gz or PREFIX_TAXON_R1.fq.gz + _R2 (read_filter.rs:38, :54-57, :151-152: spaces in the
 // taxon become '_'), written a step at a time as the block-gzip members cid_fastq_filter hands back and closed with the BGZF end-of-file
 // block.  A run that cannot finish them removes them, whichever die() on whichever thread ends it (remove_on_die): a truncated file would
 // look whole to gzip -t up to its last member.
 struct FilteredOutput {
-    std::string path[2];
-    FILE *f[2] = {nullptr, nullptr};
+    BgzfOut out[2];
     size_t n_files = 0;
     uint64_t n_kept = 0;
     PinnedBuf buf;
@@ -496,16 +546,8 @@ struct FilteredOutput {
         std::string cleaned = g_taxon.taxon;
         std::replace(cleaned.begin(), cleaned.end(), ' ', '_');
         n_files = nf;
-        size_t in_bytes = 0;
-        for (size_t i = 0; i < nf; ++i) {
-            path[i] = prefix + "_" + cleaned + (nf == 2 ? (i ? "_R2" : "_R1") : "") + ".fq.gz";
-            f[i] = fopen(path[i].c_str(), "wb");
-            if (f[i]) remove_on_die(path[i]);
-            if (!f[i]) die("could not create %s!", nf == 2 ? (i ? "R2" : "R1") : "R1");
-            struct stat sb;
-            if (stat(fq[i].c_str(), &sb) == 0) in_bytes = std::max(in_bytes, (size_t)sb.st_size);
-        }
-        buf.reserve(std::min<size_t>((size_t)96 << 20, 8 * in_bytes + (64u << 10)));   // (a step's members; grown when one takes more)
+        for (size_t i = 0; i < nf; ++i) out[i].open(prefix + "_" + cleaned + (nf == 2 ? (i ? "_R2" : "_R1") : "") + ".fq.gz", mate_name(nf, i));
+        reserve_members(buf, nf, fq);
     }
     void write_step(cid_fastq *fr, const std::vector<uint8_t> &keep) {
         const auto t = Clock::now();
@@ -518,25 +560,101 @@ struct FilteredOutput {
                 rc = cid_fastq_filter(fr, keep.data(), (int)i, buf.p, buf.cap, &bytes, &n_members, &kept);
             }
             if (rc != CID_OK) die("%s", cid_last_error());
-            if (bytes && fwrite(buf.p, 1, bytes, f[i]) != bytes) die("could not write %s!", n_files == 2 ? (i ? "R2" : "R1") : "R1");
+            out[i].write(buf.p, bytes, mate_name(n_files, i));
             if (i == 0) n_kept += kept;
         }
         ms += ms_since(t);
     }
     void finish() {
-        static const unsigned char eof_block[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (size_t i = 0; i < n_files; ++i) {
-            const bool ok = fwrite(eof_block, 1, sizeof(eof_block), f[i]) == sizeof(eof_block);
-            const bool closed = fclose(f[i]) == 0;
-            f[i] = nullptr;
-            if (!ok || !closed) die("Could not close new read file");
-        }
-        for (size_t i = 0; i < n_files; ++i) keep_on_die(path[i]);
+        for (size_t i = 0; i < n_files; ++i) out[i].close();
+        for (size_t i = 0; i < n_files; ++i) keep_on_die(out[i].path);
         if (g_taxon.exclude)   // (read_filter.rs:119-129: either line counts the reads WRITTEN)
             fprintf(stderr, "Excluded %llu read pairs  with classification containing '%s' from output files\n", (unsigned long long)n_kept, g_taxon.taxon.c_str());
         else
             fprintf(stderr, "Wrote %llu read-pairs with classification containing '%s' to output files\n", (unsigned long long)n_kept, g_taxon.taxon.c_str());
         if (g_timing) fprintf(stderr, "timing: --taxon: %.0f ms in cid_fastq_filter (waiting for the classifier in flight included) and writing the members; coder: %s\n", ms,
+                              g_taxon.gz_matches ? "LZ77 matches (--gz-matches)" : "literals only");
+    }
+};
+
+// --split: the files of a sample, PREFIX_<name>.fq.gz (or _R1 + _R2) per bin that receives a read, opened when it first does, fed the
+// byte range cid_fastq_split hands back for the bin each step, and PREFIX_split.tsv — `label TAB reads TAB file[ TAB file2]` per
+// non-empty bin, in bin order — once every file is whole.  A run that cannot finish leaves neither (remove_on_die).
+static std::vector<std::string> g_split_names;   // split_prepare: the bins' labels; their file names are split_clean() of these
+static std::string split_clean(std::string name) {
+    for (char &ch : name) if (ch == ' ' || ch == '/') ch = '_';
+    return name;
+}
+struct SplitOutput {
+    std::string prefix, manifest;
+    std::vector<BgzfOut> out[2];
+    std::vector<uint64_t> reads, bin_off, bin_reads;
+    size_t n_files = 0, n_members = 0, n_short = 0;
+    uint64_t bytes_out = 0;
+    PinnedBuf buf;
+    double ms = 0, ms_write = 0, ms_open = 0;
+    void open(const std::string &pfx, size_t nf, const std::vector<std::string> &fq) {
+        prefix = pfx; n_files = nf;
+        manifest = prefix + "_split.tsv";
+        (void)remove(manifest.c_str());   // (one of an earlier run would describe files this run replaces)
+        const size_t nb = g_split_names.size();
+        for (size_t i = 0; i < nf; ++i) out[i].resize(nb);
+        reads.assign(nb, 0); bin_off.assign(nb + 1, 0); bin_reads.assign(nb, 0);
+        reserve_members(buf, nf, fq);
+    }
+    std::string file_of(size_t b, size_t i) const { return prefix + "_" + split_clean(g_split_names[b]) + (n_files == 2 ? (i ? "_R2" : "_R1") : "") + ".fq.gz"; }
+    void write_step(cid_fastq *fr, const std::vector<uint32_t> &bins) {
+        const auto t = Clock::now();
+        const uint32_t nb = (uint32_t)g_split_names.size();
+        for (size_t i = 0; i < n_files; ++i) {
+            size_t bytes = 0, nm = 0;
+            int rc = cid_fastq_split(fr, bins.data(), nb, (int)i, buf.p, buf.cap, &bytes, bin_off.data(), bin_reads.data(), &nm);
+            if (rc == CID_ERR_INVALID && bytes > buf.cap) {   // (the members take more room than the buffer has: once more with that much)
+                buf.reserve(bytes + bytes / 8);
+                rc = cid_fastq_split(fr, bins.data(), nb, (int)i, buf.p, buf.cap, &bytes, bin_off.data(), bin_reads.data(), &nm);
+            }
+            if (rc != CID_OK) die("%s", cid_last_error());
+            const auto tw = Clock::now();
+            for (uint32_t b = 0; b < nb; ++b) {
+                if (!bin_reads[b]) continue;
+                if (!out[i][b].f) {
+                    const auto to = Clock::now();
+                    out[i][b].open(file_of(b, i), mate_name(n_files, i));
+                    ms_open += ms_since(to);
+                }
+                out[i][b].write(buf.p + bin_off[b], (size_t)(bin_off[b + 1] - bin_off[b]), mate_name(n_files, i));
+                if (i == 0) reads[b] += bin_reads[b];
+                ++n_short;   // the last member of a bin in a step is short, unless the bin's text is a multiple of 65 280 bytes
+            }
+            n_members += nm; bytes_out += bytes;
+            ms_write += ms_since(tw);
+        }
+        ms += ms_since(t);
+    }
+    void finish() {
+        size_t n_out = 0;
+        uint64_t n_reads = 0;
+        for (size_t i = 0; i < n_files; ++i)
+            for (BgzfOut &o : out[i]) if (o.f) { o.close(); ++n_out; }
+        FILE *m = fopen(manifest.c_str(), "w");
+        if (m) remove_on_die(manifest);
+        if (!m) die("could not create %s!", manifest.c_str());
+        for (size_t b = 0; b < reads.size(); ++b) {
+            if (!reads[b]) continue;
+            n_reads += reads[b];
+            fprintf(m, "%s\t%llu\t%s", g_split_names[b].c_str(), (unsigned long long)reads[b], file_of(b, 0).c_str());
+            if (n_files == 2) fprintf(m, "\t%s", file_of(b, 1).c_str());
+            fputc('\n', m);
+        }
+        if (fclose(m) != 0) die("could not write %s!", manifest.c_str());
+        for (size_t i = 0; i < n_files; ++i)
+            for (BgzfOut &o : out[i]) if (!o.path.empty()) keep_on_die(o.path);
+        keep_on_die(manifest);
+        fprintf(stderr, "Wrote %llu %s to %zu files by classification (%s)\n", (unsigned long long)n_reads, n_files == 2 ? "read pairs" : "reads", n_out, manifest.c_str());
+        if (g_timing) fprintf(stderr, "timing: --split: %.0f ms in cid_fastq_split (waiting for the classifier in flight included) and writing the members "
+                              "(creating the files %.0f ms and writing to them %.0f ms of it); %zu members (%zu of them the last of a bin in its step: short), %llu bytes in %zu files; "
+                              "coder: %s\n", ms, ms_open, ms_write - ms_open, n_members, n_short,
+                              (unsigned long long)bytes_out, n_out,
                               g_taxon.gz_matches ? "LZ77 matches (--gz-matches)" : "literals only");
     }
 };
@@ -547,10 +665,12 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
     cid_fastq *fr = nullptr;
     CID_TRY(cid_fastq_create(ctx, (int)n_files, qual_offset, &fr));
     FilteredOutput filtered;
-    if (g_taxon.on) {
+    SplitOutput dealt;
+    if (g_taxon.on || g_taxon.split) {
         CID_TRY(cid_fastq_keep_steps(fr, 1));
         if (g_taxon.gz_matches) CID_TRY(cid_fastq_filter_matches(fr, 1));
-        filtered.open(prefix, n_files, fq);
+        if (g_taxon.on) filtered.open(prefix, n_files, fq);
+        else dealt.open(prefix, n_files, fq);
     }
     classifier.ids_stay_with_counted(true);
     const size_t target = read_id_mt_pe::device_fastq_stretch_bytes(b.colors.size());
@@ -614,6 +734,9 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
                 if (g_taxon.on)   // the host front end writes no filtered reads; die() leaves no partial .fq.gz behind
                     die("%s — --taxon writes the kept reads on the device front end only, which gave way; the partial .fq.gz files were removed "
                         "(run read_id without --taxon, or the reference's read_filter)", cid_last_error());
+                if (g_taxon.split)
+                    die("%s — --split writes the reads on the device front end only, which gave way; the partial .fq.gz files were removed "
+                        "(run read_id without --split, or the reference's read_filter once per label)", cid_last_error());
                 fprintf(stderr, "note: %s — %s\n", cid_last_error(), first ? "using the host front end" : "starting over with the host front end");
                 cid_fastq_destroy(fr);
                 classifier.ids_stay_with_counted(false);
@@ -623,7 +746,7 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
             first = false;
             ++n_steps;
         }
-        const bool filter_step = g_taxon.on && have && have_n;
+        const bool filter_step = (g_taxon.on || g_taxon.split) && have && have_n;
         if (have && have_n) {
             const auto tb = Clock::now();
             std::unique_ptr<Counted> c = classifier.take_counted();
@@ -646,7 +769,8 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
         for (size_t i = 0; i < n_files; ++i)   // the stretches after this one: inflated while this one is classified
             while (more[i] && pending[i] < ahead + 1) push_next(i);
         // --taxon: the step just handed to the poll stays on the device until the next _end; its labels come back from the poll
-        if (filter_step) filtered.write_step(fr, classifier.take_keep());
+        if (filter_step && g_taxon.on) filtered.write_step(fr, classifier.take_keep());
+        if (filter_step && g_taxon.split) dealt.write_step(fr, classifier.take_bins());
         if (!begin) break;
         const auto tc = Clock::now();
         const int rc = cid_fastq_classify_end(fr, &have_n, &have_ne, &have_idb);
@@ -659,6 +783,7 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
     }
     cid_fastq_destroy(fr);
     if (g_taxon.on) filtered.finish();
+    if (g_taxon.split) dealt.finish();
     if (g_timing)
         fprintf(stderr, "timing: device front end: waiting for the file reader %.0f ms, push (H2D of the members) %.0f ms, classify %.0f ms, fetch %.0f ms "
                 "(+ %.0f ms sizing its buffers), handing the rows to the poll %.0f ms; %.0f ms until the first stretch was pushed, %.0f ms in all\n",
@@ -679,6 +804,30 @@ void empty_output(FILE *out, const std::string &prefix) {
 }
 }  // namespace
 
+void read_id_mt_pe::split_prepare(const Bigsi &b, size_t n_files) {
+    const size_t C = b.colors.size();
+    g_split_names.assign(b.colors.begin(), b.colors.end());
+    for (const char *fixed : {"no_hits", "too_short", "no_significant_hits", "multiple_hits"}) g_split_names.push_back(fixed);
+    std::map<std::string, size_t> seen;
+    for (size_t i = 0; i < g_split_names.size(); ++i) {
+        const auto at = seen.emplace(split_clean(g_split_names[i]), i);
+        if (!at.second)
+            die("error: --split: '%s' and '%s' would both be written to PREFIX_%s.fq.gz (%s); rename one of them in the index", g_split_names[at.first->second].c_str(),
+                g_split_names[i].c_str(), at.first->first.c_str(), i >= C ? "the second is one of the four fixed bins" : "spaces and '/' become '_' in file names");
+    }
+    // every bin may come to hold a file per input file; what the process has open now stays open, and the run opens a few more
+    struct rlimit rl;
+    if (getrlimit(RLIMIT_NOFILE, &rl) == 0) {
+        if (rl.rlim_cur < rl.rlim_max) { rl.rlim_cur = rl.rlim_max; (void)setrlimit(RLIMIT_NOFILE, &rl); (void)getrlimit(RLIMIT_NOFILE, &rl); }
+        size_t open_now = 0;
+        if (DIR *d = opendir("/proc/self/fd")) { while (readdir(d)) ++open_now; closedir(d); }
+        const size_t others = (open_now ? open_now : 16) + 16, want = g_split_names.size() * n_files + others;
+        if (rl.rlim_cur != RLIM_INFINITY && want > (size_t)rl.rlim_cur)
+            die("error: --split: %zu accessions + 4 bins x %zu file%s + %zu other descriptors = %zu open files, this process may hold %llu: collapse the index to fewer "
+                "colours (colorid collapse) or raise the limit (ulimit -n)", C, n_files, n_files == 1 ? "" : "s", others, want, (unsigned long long)rl.rlim_cur);
+    }
+}
+
 void read_id_mt_pe::per_read_stream_se(cid_ctx *ctx, const std::vector<std::string> &fq, const Bigsi &b, size_t d, double fp_correct,
                                        size_t batch, const std::string &prefix, uint8_t qual_offset, size_t start_sample) {
     const auto t0 = Clock::now();
@@ -687,7 +836,8 @@ void read_id_mt_pe::per_read_stream_se(cid_ctx *ctx, const std::vector<std::stri
     if (!out) die("could not create outfile!");
     ReadBatch rb;
     const bool on_device = device_fastq_wanted(fq, 1);
-    if (g_taxon.on && !on_device) die("--taxon needs the device front end (block-gzip input on one GPU; recompress with bgzip)");
+    if ((g_taxon.on || g_taxon.split) && !on_device)
+        die("%s needs the device front end (block-gzip input on one GPU; recompress with bgzip)", g_taxon.split ? "--split" : "--taxon");
     if (on_device && !cli_env("COLORID_POLL_THREADS"))
         g_poll_threads = std::max(g_poll_threads, read_id_mt_pe::device_fastq_host_share() > 0.0 ? std::min(6, cpu_budget() * 3 / 8) : std::min(12, cpu_budget() * 5 / 8));   // no packing threads beside them: a stretch's poll on 4 threads takes 18 ms, the GPU side 13
     auto make_classifier = [&] { return std::unique_ptr<BatchClassifier>(new BatchClassifier(ctx, b, d, fp_correct, start_sample, fp, out, "%llu read pairs classified\r")); };
@@ -723,7 +873,8 @@ void read_id_mt_pe::per_read_stream_pe(cid_ctx *ctx, const std::vector<std::stri
     if (!out) die("could not create outfile!");
     ReadBatch rb;
     const bool on_device = device_fastq_wanted(fq, 2);
-    if (g_taxon.on && !on_device) die("--taxon needs the device front end (block-gzip input on one GPU; recompress with bgzip)");
+    if ((g_taxon.on || g_taxon.split) && !on_device)
+        die("%s needs the device front end (block-gzip input on one GPU; recompress with bgzip)", g_taxon.split ? "--split" : "--taxon");
     if (on_device && !cli_env("COLORID_POLL_THREADS"))
         g_poll_threads = std::max(g_poll_threads, read_id_mt_pe::device_fastq_host_share() > 0.0 ? std::min(6, cpu_budget() * 3 / 8) : std::min(12, cpu_budget() * 5 / 8));
     auto make_classifier = [&] { return std::unique_ptr<BatchClassifier>(new BatchClassifier(ctx, b, d, fp_correct, start_sample, fp, out, "%llu read pairs classified\r")); };

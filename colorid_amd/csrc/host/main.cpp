@@ -740,24 +740,30 @@ bool wants_device_front_end(const Args &a, const std::vector<std::string> &fq) {
 // --taxon TAXON [--exclude] [--gz-matches] (read_id, batch_id): the reference's read_filter fused into the classifying pass — the kept reads
 // are cut and compressed on the device (cid_fastq_filter; --gz-matches: with LZ77 matches, cid_fastq_filter_matches), so only block-gzip
 // input on one GPU is served; everything else is refused here, before the GPU context is made.
+// --split [--gz-matches]: every label's reads to a file of its own in the same pass (cid_fastq_split), the same route and the same refusals.
 read_id_mt_pe::TaxonFilter taxon_filter(const Args &a) {
     read_id_mt_pe::TaxonFilter f;
     const bool exclude = a.flags.count("exclude") != 0;
     const bool matches = a.flags.count("gz-matches") != 0;
+    const bool split = a.flags.count("split") != 0;
+    if (split && a.has("taxon")) die("error: --split writes every label's reads to a file of its own; --taxon TAXON writes one label's: give one of the two");
+    if (split && exclude) die("error: --split writes every label's reads to a file of its own; --exclude belongs to --taxon TAXON: leave it out");
     if (exclude && !a.has("taxon")) die("error: --exclude needs --taxon TAXON (the classification to leave out)");
-    if (matches && !a.has("taxon")) die("error: --gz-matches needs --taxon TAXON (it chooses how the kept reads are compressed)");
+    if (matches && !a.has("taxon") && !split) die("error: --gz-matches needs --taxon TAXON or --split (it chooses how the reads written are compressed)");
+    f.gz_matches = matches;
+    if (split) { f.split = true; return f; }
     if (!a.has("taxon")) return f;
-    f.on = true; f.taxon = a.one("taxon"); f.exclude = exclude; f.gz_matches = matches;
+    f.on = true; f.taxon = a.one("taxon"); f.exclude = exclude;
     return f;
 }
-void require_filter_route(const Args &a, const std::vector<std::string> &fq) {
+void require_filter_route(const Args &a, const std::vector<std::string> &fq, bool split) {
     if (wants_device_front_end(a, fq)) return;
     const char *why = !one_gpu_run(a) ? "it runs on one GPU only (no --gpus / --devices / --placement)"
                       : (cli_env("COLORID_DEVICE_FASTQ") && atoi(cli_env("COLORID_DEVICE_FASTQ")) == 0) ? "COLORID_DEVICE_FASTQ=0 turns the device front end off"
                       : !ends_with(fq[0], ".gz") ? "the input is not compressed"
                       : "the input is a single gzip stream, not block-gzip";
-    die("error: --taxon writes the kept reads in the classifying pass on the GPU, which takes block-gzip (BGZF) fastq input: %s; "
-        "compress the reads with bgzip (%s)", why, fq[0].c_str());
+    die("error: %s in the classifying pass on the GPU, which takes block-gzip (BGZF) fastq input: %s; "
+        "compress the reads with bgzip (%s)", split ? "--split writes every label's reads" : "--taxon writes the kept reads", why, fq[0].c_str());
 }
 
 // Start reading a sample's files before whoever classifies them asks: gzip decoding (or, for the device front end, reading the
@@ -794,14 +800,14 @@ int cmd_read_id(int argc, char **argv) {
                                                      {'H', "high_mem_load", false, false}, {'p', "fp_correct", true, false},
                                                      {'Q', "quality", true, false}, {'B', "bitvector_sample", true, false},
                                                      {0, "taxon", true, false}, {0, "exclude", false, false},
-                                                     {0, "gz-matches", false, false}}));
+                                                     {0, "gz-matches", false, false}, {0, "split", false, false}}));
     for (const char *req : {"bigsi", "query", "prefix"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const std::vector<std::string> fq = a.values.at("query");
     const ClassifyFlags flags = classify_flags(a);
     const std::string prefix = a.one("prefix");
     const read_id_mt_pe::TaxonFilter filter = taxon_filter(a);
-    if (filter.on) require_filter_route(a, fq);
+    if (filter.on || filter.split) require_filter_route(a, fq, filter.split);
     read_id_mt_pe::set_taxon_filter(filter);
     if (cli_env("COLORID_GPU_INFLATE") && atoi(cli_env("COLORID_GPU_INFLATE")) > 0) LineReader::inflate_on_gpu(num_or<int>(a, "device", 0));
     const bool device_front_end = wants_device_front_end(a, fq);
@@ -814,6 +820,7 @@ int cmd_read_id(int argc, char **argv) {
     replicate(gpus, b);
     warm.join();
     phase_done("index load");
+    if (filter.split) read_id_mt_pe::split_prepare(b, fq.size() > 1 ? 2 : 1);
     classify_sample(ctx, b, fq, prefix, flags);
     LineReader::drop_prefetched();
     BgzfMemberReader::drop_prefetched();
@@ -833,7 +840,7 @@ int cmd_batch_id(int argc, char **argv) {
                                                      {'H', "high_mem_load", false, false}, {'p', "fp_correct", true, false},
                                                      {'Q', "quality", true, false}, {'B', "bitvector_sample", true, false},
                                                      {0, "taxon", true, false}, {0, "exclude", false, false},
-                                                     {0, "gz-matches", false, false}}));
+                                                     {0, "gz-matches", false, false}, {0, "split", false, false}}));
     for (const char *req : {"bigsi", "query", "tag"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const ClassifyFlags flags = classify_flags(a);
@@ -841,7 +848,7 @@ int cmd_batch_id(int argc, char **argv) {
     const auto sheet = tab_to_map(a.one("query"));
     std::vector<std::pair<std::string, std::vector<std::string>>> samples(sheet.begin(), sheet.end());
     const read_id_mt_pe::TaxonFilter filter = taxon_filter(a);
-    if (filter.on) for (const auto &sm : samples) require_filter_route(a, sm.second);
+    if (filter.on || filter.split) for (const auto &sm : samples) require_filter_route(a, sm.second, filter.split);
     read_id_mt_pe::set_taxon_filter(filter);
     if (cli_env("COLORID_GPU_INFLATE") && atoi(cli_env("COLORID_GPU_INFLATE")) > 0) LineReader::inflate_on_gpu(num_or<int>(a, "device", 0));
     std::vector<char> on_device(samples.size(), 0);
@@ -856,6 +863,11 @@ int cmd_batch_id(int argc, char **argv) {
     replicate(gpus, b);
     warm.join();
     phase_done("index load");
+    if (filter.split) {
+        size_t most = 1;
+        for (const auto &sm : samples) most = std::max<size_t>(most, sm.second.size() > 1 ? 2 : 1);
+        read_id_mt_pe::split_prepare(b, most);
+    }
     for (size_t i = 0; i < samples.size(); ++i) {
         fprintf(stderr, "Classifying %s\n", samples[i].first.c_str());
         if (i + 1 < samples.size()) read_ahead(samples[i + 1].second, on_device[i + 1]);

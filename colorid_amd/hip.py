@@ -47,6 +47,25 @@ class Context:
         check(self.lib.cid_unique_freq_modes_dev(self.h, vp(d_uc) if d_uc else None, vp(d_freq) if d_freq else None, n, n_colors,
                                                  vp(d_modes) if d_modes else None))
 
+    def bgzf_deflate_segments(self, segments, matches=False, cap=None):
+        """cid_bgzf_deflate_segments: every text of `segments` (bytes each) as block-gzip members of its own, in one call ->
+        (members [bytes], member_len [uint32 per member], seg_member_first [uint64, len(segments) + 1]); cap: the room offered for the
+        members instead of cid_bgzf_deflate_segments_bound"""
+        lib = self.lib
+        text = b"".join(segments)
+        seg_off = np.zeros(len(segments) + 1, np.uint64)
+        seg_off[1:] = np.cumsum([len(s) for s in segments], dtype=np.uint64)
+        if cap is None:
+            cap = lib.cid_bgzf_deflate_segments_bound(len(text), len(segments))
+        buf = np.frombuffer(text, np.uint8) if len(text) else np.zeros(1, np.uint8)
+        out = np.zeros(max(cap, 1), np.uint8)
+        ln = np.zeros(sum((len(s) + 65279) // 65280 for s in segments) + 1, np.uint32)
+        first = np.zeros(len(segments) + 1, np.uint64)
+        nb, nm = C.c_size_t(0), C.c_size_t(0)
+        check(lib.cid_bgzf_deflate_segments(self.h, _p(buf), _p(seg_off), len(segments), 1 if matches else 0, _p(out), cap, C.byref(nb), _p(ln), _p(first),
+                                            C.byref(nm)))
+        return out[:nb.value].tobytes(), ln[:nm.value].copy(), first
+
     def timer_start(self):
         check(self.lib.cid_timer_start(self.h))
 
@@ -818,6 +837,22 @@ class FastqReader:
             rc = self.lib.cid_fastq_filter(self.h, _p(keep), file, _p(out), out.size, C.byref(nb), C.byref(nm), C.byref(nk))
         check(rc)
         return out[:nb.value].tobytes(), nm.value, nk.value
+
+    def split(self, bins, n_bins, file=0, cap=1 << 16):
+        """cid_fastq_split: the records of file `file` of the last ended step dealt into n_bins outputs (bins[r] < n_bins, or CID_SPLIT_DROP
+        = 0xFFFFFFFF: nowhere) -> (members [bytes], bin_off [uint64, n_bins + 1], bin_reads [uint64, n_bins], n_members): bin b's
+        block-gzip members are members[bin_off[b]:bin_off[b + 1]]; cap: the room offered first (grown to what the call reports)"""
+        bins = np.ascontiguousarray(bins, np.uint32)
+        nb, nm = C.c_size_t(0), C.c_size_t(0)
+        off = np.zeros(n_bins + 1, np.uint64)
+        reads = np.zeros(max(n_bins, 1), np.uint64)
+        out = np.zeros(max(cap, 1), np.uint8)
+        rc = self.lib.cid_fastq_split(self.h, _p(bins), n_bins, file, _p(out), cap, C.byref(nb), _p(off), _p(reads), C.byref(nm))
+        if rc == CID_ERR_INVALID and nb.value > cap:   # with the size the members take: the same call with that much room
+            out = np.zeros(nb.value, np.uint8)
+            rc = self.lib.cid_fastq_split(self.h, _p(bins), n_bins, file, _p(out), out.size, C.byref(nb), _p(off), _p(reads), C.byref(nm))
+        check(rc)
+        return out[:nb.value].tobytes(), off, reads[:n_bins], nm.value
 
     def count_kmers(self, kmerset, max_pushes=0):
         """every complete record held adds its reads' k-mers to `kmerset` (search's fastq producers); -> reads taken"""

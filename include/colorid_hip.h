@@ -586,6 +586,19 @@ int cid_bgzf_deflate_lz(cid_ctx *, const uint8_t *text, size_t text_bytes, uint8
                         uint32_t *member_len, size_t *n_members);
 int cid_bgzf_deflate_lz_dev(cid_ctx *, const uint8_t *text, size_t text_bytes, uint8_t *members, size_t members_cap, uint64_t *members_bytes,
                             uint32_t *member_len, size_t *n_members);
+/* cid_bgzf_deflate (matches = 0) or cid_bgzf_deflate_lz (matches != 0) over n_segs independent texts in one call: segment s is
+ * text[seg_off[s] .. seg_off[s + 1]) (seg_off [n_segs + 1], ascending) and is cut every 65 280 bytes counted from ITS start, so no member
+ * spans two segments; segment s's members are the members seg_member_first[s] .. seg_member_first[s + 1] - 1 ([n_segs + 1], the last
+ * element = *n_members), back to back in `members` in segment order, and they are byte for byte what the contiguous call returns for
+ * that segment's text alone.  A zero-length segment contributes no member.  On the device every segment's text starts on a multiple of
+ * 16 bytes (the lengths are rounded up in the staged copy), so every piece is aligned as the pieces of the contiguous call are.
+ * cid_bgzf_deflate_segments_bound(text_bytes, n_segs) = text_bytes + 31 x (text_bytes / 65 280 + n_segs) bytes of room are never
+ * refused; CID_ERR_INVALID when the members take more than members_cap (*members_bytes then says how much), a null argument or a
+ * descending seg_off.  Scratch from the ctx's block cache while the call runs: what the contiguous call takes for the same text (the
+ * text rounded up by 16 bytes per segment), 12 bytes per member for the piece table and 24 bytes per segment. */
+size_t cid_bgzf_deflate_segments_bound(size_t text_bytes, size_t n_segs);
+int cid_bgzf_deflate_segments(cid_ctx *, const uint8_t *text, const uint64_t *seg_off, size_t n_segs, int matches, uint8_t *members, size_t members_cap,
+                              size_t *members_bytes, uint32_t *member_len, uint64_t *seg_member_first, size_t *n_members);
 /* ---- the FASTQ front end of read_id on the device: what the reference does per read before its search — inflate
  *      (src/read_id_mt_pe.rs:848-856), take the lines four at a time (:862-879 / pairs :927-975: header, sequence, '+', quality; lines()
  *      strips "\n" and "\r\n"; an unterminated last line counts), seq::qual_mask (src/seq.rs:36-56) and the (id, [seq(, mate)]) batch
@@ -663,6 +676,27 @@ int cid_fastq_keep_steps(cid_fastq *, int on);
 int cid_fastq_filter_matches(cid_fastq *, int on);
 int cid_fastq_filter(cid_fastq *, const uint8_t *keep, int file, uint8_t *members, size_t members_cap, size_t *members_bytes, size_t *n_members,
                      uint64_t *n_kept);
+/* read_id --split: the records of file `file` of the step that the last _end ended, dealt into n_bins outputs in one call — filter's
+ * record form, state rules and stream, for every label at once.
+ *   bin[n_reads]   per read of the step its output, bin[r] < n_bins, or CID_SPLIT_DROP: the read goes nowhere.
+ *   members        bin b's block-gzip members are members[bin_off[b] .. bin_off[b + 1]) (bin_off [n_bins + 1]): whole members, the bin's
+ *                  records in input order, its text cut every 65 280 bytes counted from the start of THAT bin — no member spans two
+ *                  bins, an empty bin is an empty range.  bin_reads[b] = the reads of bin b; *n_members = the members of all bins.
+ *                  The coder is the one cid_fastq_filter_matches selected.  With every bin[r] in {0, CID_SPLIT_DROP}, bin 0's bytes
+ *                  are cid_fastq_filter(keep = (bin == 0))'s, byte for byte.
+ *   How: a stable counting sort of the read indices by bin on the host (O(n_reads + n_bins), beside the walk filter makes over keep[]),
+ *   then on the device one scan over the records' sizes in output order, per bin its bytes, its base in the gathered text (rounded up to
+ *   16 bytes, so that every piece is aligned as the pieces of cid_bgzf_deflate are) and its first piece, one wave per record for the copy,
+ *   a table of (offset, length) per piece for the coder, and the gather.  Two synchronisations before the members' copy, as in filter.
+ *   CID_ERR_STATE: keep_steps is off or no step has ended yet.  CID_ERR_INVALID: n_bins == 0; a bin[r] that is neither < n_bins nor
+ *   CID_SPLIT_DROP (checked before anything is launched); members_cap too small — *members_bytes then says how much room the same call
+ *   needs, and no member has been written.
+ *   From the ctx's block cache while it runs, given back before it returns, for K bytes of text in all bins: K + 16 per bin for the
+ *   gathered text, K + 31 per member + 31 per bin for the members, 65 312 + 12 per member for the slots and the piece table (members
+ *   <= K / 65 280 + the non-empty bins), 12 bytes per read dealt and 36 per bin; with filter_matches the LZ77 coder's tokens as in filter. */
+#define CID_SPLIT_DROP 0xFFFFFFFFu
+int cid_fastq_split(cid_fastq *, const uint32_t *bin, uint32_t n_bins, int file, uint8_t *members, size_t members_cap, size_t *members_bytes,
+                    uint64_t *bin_off, uint64_t *bin_reads, size_t *n_members);
 CID_CORE void cid_fastq_destroy(cid_fastq *);
 #define CID_WARM_READID 1u
 #define CID_WARM_SEARCH 2u
