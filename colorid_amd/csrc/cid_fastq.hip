@@ -187,8 +187,8 @@ __global__ __launch_bounds__(256) void k_fq_ids(FqFile f0, uint64_t n_reads, con
         if (lane == 0) ids[o + n] = 0;
     }
 }
-// cid_fastq_filter: the bytes record r of a file takes in the output, `header\nsequence\n+\nquality\n` (the reference's format!,
-// src/read_filter.rs:89-105: the lines as lines() gives them, whatever followed the '+' dropped), or none when the read is not kept
+// cid_fastq_filter / _split: the bytes record r of a file takes in the output, `header\nsequence\n+\nquality\n` (the reference's format!,
+// src/read_filter.rs:89-105: the lines as lines() gives them, whatever followed the '+' dropped)
 __device__ __forceinline__ uint64_t fq_record_bytes(const FqFile &f, uint64_t r) {
     uint32_t b, e;
     uint64_t bytes = 5;
@@ -197,13 +197,7 @@ __device__ __forceinline__ uint64_t fq_record_bytes(const FqFile &f, uint64_t r)
     fq_line(f, 4 * r + 3, b, e); bytes += e - b;
     return bytes;
 }
-struct FqKeepIn {
-    FqFile f;
-    const uint8_t *keep;
-    uint64_t n;
-    __device__ uint64_t operator()(uint64_t r) const { return r >= n || !keep[r] ? 0ull : fq_record_bytes(f, r); }
-};
-// cid_fastq_split: the same over the reads in output order — element j is record order[j]
+// the scan's input: the reads in output order — element j is record order[j]
 struct FqOrderIn {
     FqFile f;
     const uint32_t *order;
@@ -225,14 +219,9 @@ __device__ __forceinline__ void fq_copy_record(const FqFile &f, uint64_t r, uint
     for (uint32_t j = lane; j < e - b; j += 64) o[3 + j] = f.text[b + j];
     if (lane == 0) o[3 + (e - b)] = '\n';
 }
-// one wave per kept record, to out[off[r] ..)
-__global__ __launch_bounds__(256) void k_fq_filter_copy(FqFile f, const uint8_t *keep, uint64_t n, const uint64_t *off, uint8_t *out) {
-    const uint32_t lane = threadIdx.x & 63;
-    for (uint64_t r = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < n; r += (uint64_t)gridDim.x * 4)
-        if (keep[r]) fq_copy_record(f, r, out + off[r], lane);
-}
-// cid_fastq_split: bin b holds the reads order[bin_first[b] .. bin_first[b + 1]), off[j] = the bytes of the records before order[j];
+// fastq_deal: bin b holds the reads order[bin_first[b] .. bin_first[b + 1]), off[j] = the bytes of the records before order[j];
 // bin_len[b] = the bytes of its records (k_fq_split_bin_len), and one wave per record copies it to base[b] + its offset inside the bin
+// (one bin, cid_fastq_filter: the search below has nothing to halve)
 __global__ __launch_bounds__(256) void k_fq_split_bin_len(const uint64_t *off, const uint32_t *bin_first, uint32_t n_bins, uint64_t *bin_len) {
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < n_bins) bin_len[b] = off[bin_first[b + 1]] - off[bin_first[b]];
@@ -316,13 +305,13 @@ struct cid_fastq {
         std::vector<void *> scratch;   // what the kernels in flight read: back to the cache in _end
     } infl;
     // cid_fastq_keep_steps: the step that _end has just ended stays on the device as it was cut — either file's text and line ends —
-    // until the next _end, for cid_fastq_filter.  The text the next step appends to is then a buffer of its own (the unfinished tail
-    // is copied there instead of moved to the front): one more generation of text + 4 bytes per line in HBM, ~2 x 256 MiB per file at
-    // the command line's stretch size.  Transient, inside one cid_fastq_filter call and back in the block cache when it returns: the kept
-    // text (K bytes), the bound for its members (K + 31 a member) and bgzf_deflate_launch's slots (65 312 a member): ~3 K, so up to
+    // until the next _end, for cid_fastq_filter / _split.  The text the next step appends to is then a buffer of its own (the unfinished
+    // tail is copied there instead of moved to the front): one more generation of text + 4 bytes per line in HBM, ~2 x 256 MiB per file at
+    // the command line's stretch size.  Transient, inside one fastq_deal call and back in the block cache when it returns: the kept
+    // text (K bytes), the bound for its members (K + 31 a member) and the coder's slots (65 312 a member): ~3 K, so up to
     // ~0.75 GiB more when a whole 256 MiB stretch of one file is kept.
     bool keep_steps = false;
-    // cid_fastq_filter_matches: the kept text goes through the LZ77 coder (bgzf_deflate_launch's `matches`), which takes its tokens from
+    // cid_fastq_filter_matches: the kept text goes through the LZ77 coder (bgzf_deflate_segments_launch's `matches`), which takes its tokens from
     // the block cache too: 261 120 bytes per workgroup launched, min(members, 6 x CUs) of them (383 MiB at most on 256 CUs).
     bool filter_matches = false;
     struct Gen {
@@ -335,7 +324,7 @@ struct cid_fastq {
     hipStream_t fetch_stream = nullptr;   // results leave beside the classifier of the NEXT step, not behind it
     // CID_FASTQ_TIMING=1: host time per part of a step, printed when the reader is destroyed
     bool timing = false;
-    double ms_part[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // [7 ..]: the parts of cid_fastq_split
+    double ms_part[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // [7 ..]: the parts of fastq_deal (cid_fastq_split and cid_fastq_filter)
     uint64_t n_steps = 0;
 };
 
@@ -446,7 +435,7 @@ void cid_fastq_destroy(cid_fastq *fq) {
                 "records + scans %.1f, pack + launch of the classifier %.1f, report compaction + drain %.1f, carry %.1f\n", (unsigned long long)fq->n_steps,
                 fq->ms_part[0], fq->ms_part[1], fq->ms_part[2], fq->ms_part[3], fq->ms_part[4], fq->ms_part[5], fq->ms_part[6]);
     if (fq->timing && fq->ms_part[7] > 0)
-        fprintf(stderr, "cid_fastq: cid_fastq_split: host ms ordering the reads by bin (counting sort) %.1f, order up + sizes and layout + first wait %.1f, "
+        fprintf(stderr, "cid_fastq: cid_fastq_split / _filter: host ms ordering the reads by bin (counting sort) %.1f, order up + sizes and layout + first wait %.1f, "
                 "scratch + copy + coder + second wait %.1f, members to the host %.1f\n", fq->ms_part[7], fq->ms_part[8], fq->ms_part[9], fq->ms_part[10]);
     cid_ctx *c = fq->ctx;
     (void)hipSetDevice(c->device);
@@ -834,6 +823,96 @@ static int fastq_step(cid_fastq *fq, const cid_index *ix, cid_kmerset *ks, uint3
     return rc ? rc : fastq_end(fq, n_reads, n_entries, id_bytes);
 }
 
+// cid_fastq_filter and cid_fastq_split (`what`: "filter" / "split", for the error texts): is there a kept step to read
+static int fastq_deal_state(const cid_fastq *fq, const char *what) {
+    if (!fq->keep_steps) return fail(CID_ERR_STATE, "cid_fastq_%s: the reader keeps no steps (cid_fastq_keep_steps)", what);
+    if (!fq->gen.valid) return fail(CID_ERR_STATE, "cid_fastq_%s: no finished step to %s", what, what);
+    return CID_OK;
+}
+// ... and the one path behind both: the records of file `file` of the kept step dealt into n_bins outputs (cid_fastq_split's contract,
+// include/colorid_hip.h; cid_fastq_filter is the call with one bin).  The caller has checked its arguments and the state and zeroed
+// *members_bytes and *n_members; both are set before the refusal for lack of room.
+static int fastq_deal(cid_fastq *fq, const char *what, const uint32_t *bin, uint32_t n_bins, int file, uint8_t *members, size_t members_cap,
+                      size_t *members_bytes, uint64_t *bin_off, uint64_t *bin_reads, size_t *n_members) {
+    const uint64_t n = fq->gen.n;
+    // ---- the order (host): a stable counting sort of the step's reads by bin — one pass to count, one to place
+    PartClock pc(fq);
+    std::vector<uint32_t> first((size_t)n_bins + 1, 0);
+    uint64_t kept = 0;
+    for (uint64_t r = 0; r < n; ++r) {
+        const uint32_t b = bin[r];
+        if (b == CID_SPLIT_DROP) continue;
+        if (b >= n_bins) return fail(CID_ERR_INVALID, "cid_fastq_%s: read %llu goes to bin %u of %u", what, (unsigned long long)r, b, n_bins);
+        if (n_bins > 1) ++first[(size_t)b + 1];   // (one bin: `kept` is its count; bumping ONE counter in memory waits for its own store every read)
+        ++kept;
+    }
+    if (n_bins == 1) first[1] = (uint32_t)kept;
+    for (uint32_t b = 0; b < n_bins; ++b) { bin_reads[b] = first[(size_t)b + 1]; bin_off[b] = 0; first[(size_t)b + 1] += first[b]; }
+    bin_off[n_bins] = 0;
+    if (kept == 0) return CID_OK;
+    if (!fq->gen.text[file] || !fq->gen.nl[file]) return fail(CID_ERR_STATE, "cid_fastq_%s: the step's text was not kept (its _end failed)", what);
+    std::vector<uint32_t> order((size_t)kept);
+    if (n_bins == 1) {   // the kept reads in input order, the cursor in a register
+        uint64_t j = 0;
+        for (uint64_t r = 0; r < n && j < kept; ++r) { order[j] = (uint32_t)r; j += bin[r] == 0; }
+    } else {
+        std::vector<uint32_t> at(first.begin(), first.end() - 1);
+        for (uint64_t r = 0; r < n; ++r)
+            if (bin[r] != CID_SPLIT_DROP) order[at[bin[r]]++] = (uint32_t)r;
+    }
+    pc.lap(7);
+    cid_ctx *c = fq->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st = c->stream;   // (behind a classifier launched since: the step's buffers and the block cache are this stream's)
+    int rc;
+    Buf<uint8_t> d_text(c), d_out(c);
+    Buf<uint64_t> off(c), state(c), bin_len(c), base(c), piece_first(c), d_bin_off(c), d_total(c);
+    Buf<uint32_t> d_order(c), d_first(c), d_len(c);
+    if ((rc = d_order.alloc(kept)) || (rc = d_first.alloc((size_t)n_bins + 1)) || (rc = off.alloc(kept + 1)) || (rc = state.alloc(cid::scan_state_words(kept + 1))) ||
+        (rc = bin_len.alloc(n_bins)) || (rc = base.alloc((size_t)n_bins + 1)) || (rc = piece_first.alloc((size_t)n_bins + 1)) ||
+        (rc = d_bin_off.alloc((size_t)n_bins + 1)) || (rc = d_total.alloc(2)))
+        return rc;
+    // (pageable sources: either copy has left the host's vectors when its call returns)
+    HIP_TRY(hipMemcpyAsync(d_order.p, order.data(), kept * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_first.p, first.data(), ((size_t)n_bins + 1) * 4, hipMemcpyHostToDevice, st));
+    const cid::FqFile F{fq->gen.text[file], fq->gen.nl[file], nullptr, fq->gen.len[file]};
+    // ---- sizes and layout (device): the records' offsets in output order, every bin's bytes, its 16-byte-aligned base and first piece
+    HIP_TRY(cid::scan_launch(cid::FqOrderIn{F, d_order.p, kept}, cid::ScanOutU64{off.p, 0ull}, kept + 1, state.p, st));
+    hipLaunchKernelGGL(cid::k_fq_split_bin_len, dim3((n_bins + 255) / 256), dim3(256), 0, st, (const uint64_t *)off.p, (const uint32_t *)d_first.p, n_bins, bin_len.p);
+    HIP_TRY(hipGetLastError());
+    if ((rc = cid::bgzf_segments_layout(c, st, bin_len.p, n_bins, base.p, piece_first.p))) { (void)hipStreamSynchronize(st); return rc; }
+    uint64_t room = 0, np = 0;
+    HIP_TRY(hipMemcpyAsync(&room, base.p + n_bins, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&np, piece_first.p + n_bins, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    pc.lap(8);
+    const size_t bound = cid_bgzf_deflate_segments_bound((size_t)room, n_bins);
+    if ((rc = d_text.alloc(room + 16)) || (rc = d_out.alloc(bound + 16)) || (rc = d_len.alloc(np))) return rc;
+    unsigned grid = (unsigned)((kept + 3) / 4);
+    if (grid > 16384) grid = 16384;
+    hipLaunchKernelGGL(cid::k_fq_split_copy, dim3(grid), dim3(256), 0, st, F, (const uint32_t *)d_order.p, kept, (const uint64_t *)off.p, (const uint32_t *)d_first.p,
+                       n_bins, (const uint64_t *)base.p, d_text.p);
+    HIP_TRY(hipGetLastError());
+    if ((rc = cid::bgzf_deflate_segments_launch(c, st, d_text.p, bin_len.p, base.p, piece_first.p, n_bins, (size_t)np, d_out.p, d_len.p, d_total.p, d_bin_off.p,
+                                                fq->filter_matches))) { (void)hipStreamSynchronize(st); return rc; }
+    uint64_t total = 0;
+    std::vector<uint64_t> h_bin_off((size_t)n_bins + 1);
+    HIP_TRY(hipMemcpyAsync(&total, d_total.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_bin_off.data(), d_bin_off.p, ((size_t)n_bins + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    pc.lap(9);
+    *members_bytes = (size_t)total;
+    *n_members = (size_t)np;
+    if (total > members_cap || !members)
+        return fail(CID_ERR_INVALID, "cid_fastq_%s: the members take %llu bytes, the buffer holds %zu: call again with that much room", what,
+                    (unsigned long long)total, members_cap);
+    memcpy(bin_off, h_bin_off.data(), ((size_t)n_bins + 1) * 8);
+    HIP_TRY(hipMemcpyAsync(members, d_out.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    pc.lap(10);
+    return CID_OK;
+}
+
 extern "C" {
 
 int cid_fastq_classify(cid_fastq *fq, const cid_index *ix, uint32_t stride_d, uint32_t start_sample, int max_pushes, uint64_t *n_reads,
@@ -882,52 +961,20 @@ int cid_fastq_filter_matches(cid_fastq *fq, int on) {
     return CID_OK;
 }
 
+// splitting into one bin: bin 0's range is the whole of `members`, its read count is *n_kept
 int cid_fastq_filter(cid_fastq *fq, const uint8_t *keep, int file, uint8_t *members, size_t members_cap, size_t *members_bytes, size_t *n_members,
                      uint64_t *n_kept) {
     if (!fq || !members_bytes || !n_members || !n_kept || file < 0 || file >= fq->n_files) return fail(CID_ERR_INVALID, "bad argument");
     *members_bytes = 0; *n_members = 0; *n_kept = 0;
-    if (!fq->keep_steps) return fail(CID_ERR_STATE, "cid_fastq_filter: the reader keeps no steps (cid_fastq_keep_steps)");
-    if (!fq->gen.valid) return fail(CID_ERR_STATE, "cid_fastq_filter: no finished step to filter");
+    if (const int rc = fastq_deal_state(fq, "filter")) return rc;
     const uint64_t n = fq->gen.n;
     if (n == 0) return CID_OK;
     if (!keep) return fail(CID_ERR_INVALID, "null argument");
     if (!fq->gen.text[file] || !fq->gen.nl[file]) return fail(CID_ERR_STATE, "cid_fastq_filter: the step's text was not kept (its _end failed)");
-    uint64_t kept = 0;
-    for (uint64_t r = 0; r < n; ++r) kept += keep[r] != 0;
-    *n_kept = kept;
-    if (kept == 0) return CID_OK;
-    cid_ctx *c = fq->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = c->stream;   // (behind a classifier launched since: the step's buffers and the block cache are this stream's)
-    int rc;
-    Buf<uint8_t> d_keep(c), d_text(c), d_out(c);
-    Buf<uint64_t> off(c), state(c), d_total(c);
-    Buf<uint32_t> d_len(c);
-    if ((rc = d_keep.alloc(n)) || (rc = off.alloc(n + 1)) || (rc = state.alloc(cid::scan_state_words(n + 1))) || (rc = d_total.alloc(2))) return rc;
-    HIP_TRY(hipMemcpyAsync(d_keep.p, keep, n, hipMemcpyHostToDevice, st));
-    const cid::FqFile F{fq->gen.text[file], fq->gen.nl[file], nullptr, fq->gen.len[file]};
-    HIP_TRY(cid::scan_launch(cid::FqKeepIn{F, d_keep.p, n}, cid::ScanOutU64{off.p, 0ull}, n + 1, state.p, st));
-    uint64_t text_bytes = 0;
-    HIP_TRY(hipMemcpyAsync(&text_bytes, off.p + n, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const size_t nm = (size_t)((text_bytes + 65279) / 65280), bound = cid_bgzf_deflate_bound((size_t)text_bytes);
-    if ((rc = d_text.alloc(text_bytes + 16)) || (rc = d_out.alloc(bound + 16)) || (rc = d_len.alloc(nm))) return rc;
-    unsigned grid = (unsigned)((n + 3) / 4);
-    if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL(cid::k_fq_filter_copy, dim3(grid), dim3(256), 0, st, F, (const uint8_t *)d_keep.p, n, (const uint64_t *)off.p, d_text.p);
-    HIP_TRY(hipGetLastError());
-    if ((rc = cid::bgzf_deflate_launch(c, st, d_text.p, (size_t)text_bytes, d_out.p, d_len.p, d_total.p, fq->filter_matches))) { (void)hipStreamSynchronize(st); return rc; }
-    uint64_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d_total.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    *members_bytes = (size_t)total;
-    *n_members = nm;
-    if (total > members_cap || !members)
-        return fail(CID_ERR_INVALID, "cid_fastq_filter: the members take %llu bytes, the buffer holds %zu: call again with that much room",
-                    (unsigned long long)total, members_cap);
-    HIP_TRY(hipMemcpyAsync(members, d_out.p, (size_t)total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return CID_OK;
+    std::vector<uint32_t> bin((size_t)n);
+    for (uint64_t r = 0; r < n; ++r) bin[r] = keep[r] ? 0u : CID_SPLIT_DROP;
+    uint64_t bin_off[2];
+    return fastq_deal(fq, "filter", bin.data(), 1, file, members, members_cap, members_bytes, bin_off, n_kept, n_members);
 }
 
 int cid_fastq_split(cid_fastq *fq, const uint32_t *bin, uint32_t n_bins, int file, uint8_t *members, size_t members_cap, size_t *members_bytes,
@@ -937,79 +984,9 @@ int cid_fastq_split(cid_fastq *fq, const uint32_t *bin, uint32_t n_bins, int fil
     if (n_bins == 0) return fail(CID_ERR_INVALID, "cid_fastq_split: no bins");
     if (n_bins == CID_SPLIT_DROP) return fail(CID_ERR_INVALID, "cid_fastq_split: %u bins: that value marks a dropped read", n_bins);
     if (!bin_off || !bin_reads) return fail(CID_ERR_INVALID, "null argument");
-    if (!fq->keep_steps) return fail(CID_ERR_STATE, "cid_fastq_split: the reader keeps no steps (cid_fastq_keep_steps)");
-    if (!fq->gen.valid) return fail(CID_ERR_STATE, "cid_fastq_split: no finished step to split");
-    const uint64_t n = fq->gen.n;
-    if (n && !bin) return fail(CID_ERR_INVALID, "null argument");
-    // ---- the order (host): a stable counting sort of the step's reads by bin — one pass to count, one to place
-    PartClock pc(fq);
-    std::vector<uint32_t> first((size_t)n_bins + 1, 0);
-    uint64_t kept = 0;
-    for (uint64_t r = 0; r < n; ++r) {
-        const uint32_t b = bin[r];
-        if (b == CID_SPLIT_DROP) continue;
-        if (b >= n_bins) return fail(CID_ERR_INVALID, "cid_fastq_split: read %llu goes to bin %u of %u", (unsigned long long)r, b, n_bins);
-        ++first[(size_t)b + 1];
-        ++kept;
-    }
-    for (uint32_t b = 0; b < n_bins; ++b) { bin_reads[b] = first[(size_t)b + 1]; bin_off[b] = 0; first[(size_t)b + 1] += first[b]; }
-    bin_off[n_bins] = 0;
-    if (kept == 0) return CID_OK;
-    if (!fq->gen.text[file] || !fq->gen.nl[file]) return fail(CID_ERR_STATE, "cid_fastq_split: the step's text was not kept (its _end failed)");
-    std::vector<uint32_t> order((size_t)kept), at(first.begin(), first.end() - 1);
-    for (uint64_t r = 0; r < n; ++r)
-        if (bin[r] != CID_SPLIT_DROP) order[at[bin[r]]++] = (uint32_t)r;
-    pc.lap(7);
-    cid_ctx *c = fq->ctx;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = c->stream;   // (behind a classifier launched since: the step's buffers and the block cache are this stream's)
-    int rc;
-    Buf<uint8_t> d_text(c), d_out(c);
-    Buf<uint64_t> off(c), state(c), bin_len(c), base(c), piece_first(c), d_bin_off(c), d_total(c);
-    Buf<uint32_t> d_order(c), d_first(c), d_len(c);
-    if ((rc = d_order.alloc(kept)) || (rc = d_first.alloc((size_t)n_bins + 1)) || (rc = off.alloc(kept + 1)) || (rc = state.alloc(cid::scan_state_words(kept + 1))) ||
-        (rc = bin_len.alloc(n_bins)) || (rc = base.alloc((size_t)n_bins + 1)) || (rc = piece_first.alloc((size_t)n_bins + 1)) ||
-        (rc = d_bin_off.alloc((size_t)n_bins + 1)) || (rc = d_total.alloc(2)))
-        return rc;
-    // (pageable sources: either copy has left the host's vectors when its call returns)
-    HIP_TRY(hipMemcpyAsync(d_order.p, order.data(), kept * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_first.p, first.data(), ((size_t)n_bins + 1) * 4, hipMemcpyHostToDevice, st));
-    const cid::FqFile F{fq->gen.text[file], fq->gen.nl[file], nullptr, fq->gen.len[file]};
-    // ---- sizes and layout (device): the records' offsets in output order, every bin's bytes, its 16-byte-aligned base and first piece
-    HIP_TRY(cid::scan_launch(cid::FqOrderIn{F, d_order.p, kept}, cid::ScanOutU64{off.p, 0ull}, kept + 1, state.p, st));
-    hipLaunchKernelGGL(cid::k_fq_split_bin_len, dim3((n_bins + 255) / 256), dim3(256), 0, st, (const uint64_t *)off.p, (const uint32_t *)d_first.p, n_bins, bin_len.p);
-    HIP_TRY(hipGetLastError());
-    if ((rc = cid::bgzf_segments_layout(c, st, bin_len.p, n_bins, base.p, piece_first.p))) { (void)hipStreamSynchronize(st); return rc; }
-    uint64_t room = 0, np = 0;
-    HIP_TRY(hipMemcpyAsync(&room, base.p + n_bins, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&np, piece_first.p + n_bins, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    pc.lap(8);
-    const size_t bound = cid_bgzf_deflate_segments_bound((size_t)room, n_bins);
-    if ((rc = d_text.alloc(room + 16)) || (rc = d_out.alloc(bound + 16)) || (rc = d_len.alloc(np))) return rc;
-    unsigned grid = (unsigned)((kept + 3) / 4);
-    if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL(cid::k_fq_split_copy, dim3(grid), dim3(256), 0, st, F, (const uint32_t *)d_order.p, kept, (const uint64_t *)off.p, (const uint32_t *)d_first.p,
-                       n_bins, (const uint64_t *)base.p, d_text.p);
-    HIP_TRY(hipGetLastError());
-    if ((rc = cid::bgzf_deflate_segments_launch(c, st, d_text.p, bin_len.p, base.p, piece_first.p, n_bins, (size_t)np, d_out.p, d_len.p, d_total.p, d_bin_off.p,
-                                                fq->filter_matches))) { (void)hipStreamSynchronize(st); return rc; }
-    uint64_t total = 0;
-    std::vector<uint64_t> h_bin_off((size_t)n_bins + 1);
-    HIP_TRY(hipMemcpyAsync(&total, d_total.p, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_bin_off.data(), d_bin_off.p, ((size_t)n_bins + 1) * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    pc.lap(9);
-    *members_bytes = (size_t)total;
-    if (total > members_cap || !members)
-        return fail(CID_ERR_INVALID, "cid_fastq_split: the members take %llu bytes, the buffer holds %zu: call again with that much room",
-                    (unsigned long long)total, members_cap);
-    *n_members = (size_t)np;
-    memcpy(bin_off, h_bin_off.data(), ((size_t)n_bins + 1) * 8);
-    HIP_TRY(hipMemcpyAsync(members, d_out.p, (size_t)total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    pc.lap(10);
-    return CID_OK;
+    if (const int rc = fastq_deal_state(fq, "split")) return rc;
+    if (fq->gen.n && !bin) return fail(CID_ERR_INVALID, "null argument");
+    return fastq_deal(fq, "split", bin, n_bins, file, members, members_cap, members_bytes, bin_off, bin_reads, n_members);
 }
 
 int cid_fastq_fetch(cid_fastq *fq, uint32_t *n_kmers, uint8_t *status, uint64_t *row_start, uint32_t *colours, uint32_t *counts, uint64_t *id_off,

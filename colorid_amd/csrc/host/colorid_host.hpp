@@ -420,13 +420,18 @@ double device_fastq_host_share();                     // share of a stretch's te
 int device_fastq_host_threads(size_t n_files);
 // read_id / batch_id --taxon TAXON [--exclude] (the reference's read_filter, src/read_filter.rs, fused into the classifying pass): the
 // reads whose label — column 2 of their _reads.txt row — contains TAXON (--exclude: does not contain it) are written by the device
-// front end as PREFIX_TAXON.fq.gz / PREFIX_TAXON_R1.fq.gz + _R2 (cid_fastq_filter).  Set before the streamers run; on == false: none.
+// front end as PREFIX_TAXON.fq.gz / PREFIX_TAXON_R1.fq.gz + _R2: the one-bin case of --split.
 // --split (no reference counterpart; one read_filter pass per label there): EVERY read to the file of its label, decided by equality —
 // bin c: accession c (one significant top hit), C: no_hits, C + 1: too_short, C + 2: no_significant_hits, C + 3: multiple_hits (a joined
 // list of several top hits) — as PREFIX_<name>.fq.gz / _R1 + _R2 per non-empty bin (cid_fastq_split, once per file per step) and the
-// manifest PREFIX_split.tsv.  split excludes on.
-struct TaxonFilter { bool on = false; std::string taxon; bool exclude = false; bool gz_matches = false; bool split = false; };   // gz_matches: --gz-matches, members with LZ77 matches
-void set_taxon_filter(const TaxonFilter &f);
+// manifest PREFIX_split.tsv.  Set before the streamers run.
+struct ReadOutput {   // which reads the classifying pass writes as .fq.gz
+    enum Mode { kNone, kTaxon, kSplit } mode = kNone;
+    std::string taxon;         // kTaxon: --taxon TAXON
+    bool exclude = false;      // kTaxon: --exclude
+    bool gz_matches = false;   // --gz-matches: members with LZ77 matches
+};
+void set_read_output(const ReadOutput &o);
 // --split, after the index is loaded and before a read is classified: the bins' file names (spaces and '/' become '_'); ends the run when
 // two bins would share a file or when (C + 4) x n_files descriptors are more than the process may hold open
 void split_prepare(const Bigsi &b, size_t n_files);

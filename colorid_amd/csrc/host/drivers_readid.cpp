@@ -13,8 +13,9 @@ namespace colorid {
 
 static double g_ms_gpu = 0, g_ms_poll = 0, g_ms_gpu_count = 0, g_ms_write = 0;
 static uint64_t g_entries = 0;
-static read_id_mt_pe::TaxonFilter g_taxon;   // --taxon / --exclude
-void read_id_mt_pe::set_taxon_filter(const TaxonFilter &f) { g_taxon = f; }
+using read_id_mt_pe::ReadOutput;
+static ReadOutput g_out;   // --taxon [--exclude] / --split
+void read_id_mt_pe::set_read_output(const ReadOutput &o) { g_out = o; }
 static double g_ms_wait[4] = {0, 0, 0, 0};   // parser blocked by a full queue | GPU stage idle | GPU stage blocked by the poll | poll idle
 
 // probability::Binomial::mass in log space.  The poll evaluates it ~10 times per read (once per candidate colour), so the pieces that
@@ -141,8 +142,7 @@ struct Counted {   // one batch after the GPU stage: each read's non-zero (colou
     std::vector<uint8_t> status;
     std::vector<uint64_t> row_start;
     std::vector<uint32_t> colours, counts;
-    std::vector<uint8_t> keep;   // --taxon: per read, whether its label passes the filter (filled by the poll)
-    std::vector<uint32_t> bin;   // --split: per read, the bin of its label (filled by the poll)
+    std::vector<uint32_t> bin;   // --taxon / --split: per read, the output bin of its label or CID_SPLIT_DROP (filled by the poll)
 };
 void count_batch(cid_ctx *ctx, const Bigsi &b, Counted &c, size_t d, size_t start_sample) {
     ReadBatch &rb = c.rb;
@@ -201,15 +201,14 @@ void poll_batch(const Bigsi &b, Counted &c, double fp_correct, const std::vector
     // the tally of <prefix>_counts.txt: an accepted read counts under its label — one accession, "no_hits" or "too_short" — every other under "reject"
     for (size_t t = 0; t < nt; ++t) { text[t].clear(); acc[t].assign(C + 3, 0); }   // [C] no_hits, [C+1] too_short, [C+2] reject
     if (memchr(c.rb.id_chars.data(), '\t', c.rb.id_chars.size())) tally_ok = false;
-    // --taxon: read_filter's tab_to_map keeps a row when its second column contains the query (read_filter.rs:21)
-    const bool filter = g_taxon.on;
-    if (filter) c.keep.assign(n, 0);
+    // --taxon: one bin; read_filter's tab_to_map keeps a row when its second column contains the query (read_filter.rs:21)
+    const bool filter = g_out.mode == ReadOutput::kTaxon;
     // --split: the label's bin by equality — the tally's indices, with the rejects told apart (C + 2 no_significant_hits, C + 3 several top hits)
-    const bool split = g_taxon.split;
-    if (split) c.bin.assign(n, 0);
-    auto passes = [&](const std::string &o, size_t label_begin) {
-        const bool hit = g_taxon.taxon.empty() || memmem(o.data() + label_begin, o.size() - label_begin, g_taxon.taxon.data(), g_taxon.taxon.size()) != nullptr;
-        return (uint8_t)(hit != g_taxon.exclude);
+    const bool split = g_out.mode == ReadOutput::kSplit;
+    if (g_out.mode != ReadOutput::kNone) c.bin.assign(n, 0);
+    auto taxon_bin = [&](const std::string &o, size_t label_begin) {
+        const bool hit = g_out.taxon.empty() || memmem(o.data() + label_begin, o.size() - label_begin, g_out.taxon.data(), g_out.taxon.size()) != nullptr;
+        return hit != g_out.exclude ? 0u : CID_SPLIT_DROP;
     };
     auto work = [&](size_t t) {
         // (the slice's string is moved onto this thread's stack while it grows: the headers of text[0], text[1], ... share cache lines,
@@ -223,7 +222,7 @@ void poll_batch(const Bigsi &b, Counted &c, double fp_correct, const std::vector
         for (size_t r = r0; r < r1; ++r) {
             o += c.rb.id(r);
             if (c.status[r] == 1) {
-                if (filter) { const size_t lb = o.size() + 1; o += "\ttoo_short"; c.keep[r] = passes(o, lb); o += "\t0\t0\taccept\t0\n"; }
+                if (filter) { const size_t lb = o.size() + 1; o += "\ttoo_short"; c.bin[r] = taxon_bin(o, lb); o += "\t0\t0\taccept\t0\n"; }
                 else o += "\ttoo_short\t0\t0\taccept\t0\n";
                 ++a[C + 1];
                 if (split) c.bin[r] = (uint32_t)(C + 1);
@@ -243,7 +242,7 @@ void poll_batch(const Bigsi &b, Counted &c, double fp_correct, const std::vector
                 ++a[p.n_top == 1 ? p.first_top : C + 2];
                 if (split) c.bin[r] = p.n_top == 1 ? p.first_top : (uint32_t)(C + 3);
             }
-            if (filter) c.keep[r] = passes(o, label_begin);
+            if (filter) c.bin[r] = taxon_bin(o, label_begin);
             o += '\t'; append_u64(o, p.best);
             o += '\t'; append_u64(o, c.nk[r]);
             o += (p.kind == 0 || (p.kind == 2 && p.n_top == 1)) ? "\taccept\t" : "\treject\t";
@@ -324,18 +323,10 @@ class BatchClassifier {
         counted_.push_back(std::move(c));
         cv_counted_.notify_one();
     }
-    // --taxon: the keep flags of the oldest polled batch not yet taken (batches are polled in the order they were handed over)
-    std::vector<uint8_t> take_keep() {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_keep_.wait(lk, [&] { return !keep_ready_.empty(); });
-        std::vector<uint8_t> k = std::move(keep_ready_.front());
-        keep_ready_.pop_front();
-        return k;
-    }
-    // --split: the same for the bins
+    // --taxon / --split: the bins of the oldest polled batch not yet taken (batches are polled in the order they were handed over)
     std::vector<uint32_t> take_bins() {
         std::unique_lock<std::mutex> lk(mu_);
-        cv_keep_.wait(lk, [&] { return !bins_ready_.empty(); });
+        cv_bins_.wait(lk, [&] { return !bins_ready_.empty(); });
         std::vector<uint32_t> k = std::move(bins_ready_.front());
         bins_ready_.pop_front();
         return k;
@@ -398,8 +389,7 @@ class BatchClassifier {
             n_reads_ += c->rb.size();
             fprintf(stderr, progress_fmt_, (unsigned long long)n_reads_);
             std::lock_guard<std::mutex> lk(mu_);
-            if (g_taxon.on) { keep_ready_.push_back(std::move(c->keep)); c->keep.clear(); cv_keep_.notify_one(); }
-            if (g_taxon.split) { bins_ready_.push_back(std::move(c->bin)); c->bin.clear(); cv_keep_.notify_one(); }
+            if (g_out.mode != ReadOutput::kNone) { bins_ready_.push_back(std::move(c->bin)); c->bin.clear(); cv_bins_.notify_one(); }
             if (!ids_stay_) {   // (the device front end fills a Counted's ids itself: they stay with it, sized, for the next stretch)
                 c->rb.clear();
                 if (spare_.size() < 16) spare_.push_back(std::move(c->rb));
@@ -417,8 +407,7 @@ class BatchClassifier {
     FILE *out_;
     const char *progress_fmt_;
     std::mutex mu_;
-    std::condition_variable cv_work_, cv_room_, cv_counted_, cv_polled_, cv_keep_;
-    std::deque<std::vector<uint8_t>> keep_ready_;
+    std::condition_variable cv_work_, cv_room_, cv_counted_, cv_polled_, cv_bins_;
     std::deque<std::vector<uint32_t>> bins_ready_;
     std::deque<ReadBatch> queue_;
     std::deque<std::unique_ptr<Counted>> counted_;
@@ -532,61 +521,23 @@ static void reserve_members(PinnedBuf &buf, size_t nf, const std::vector<std::st
     buf.reserve(std::min<size_t>((size_t)96 << 20, 8 * in_bytes + (64u << 10)));
 }
 
-// --taxon: the output files of a sample, PREFIX_TAXON.fq.gz or PREFIX_TAXON_R1.fq.gz + _R2 (read_filter.rs:38, :54-57, :151-152: spaces in the
-// taxon become '_'), written a step at a time as the block-gzip members cid_fastq_filter hands back and closed with the BGZF end-of-file
-// block.  A run that cannot finish them removes them, whichever die() on whichever thread ends it (remove_on_die): a truncated file would
+// --taxon / --split: the files of a sample, PREFIX_<stem>.fq.gz (or _R1 + _R2) per bin, fed the byte range cid_fastq_split hands back
+// for the bin each step and closed with the BGZF end-of-file block.  The two modes differ in data only:
+//   --taxon   one bin, named by the taxon with spaces as '_' (read_filter.rs:38, :54-57, :151-152); its files are made at open, so a
+//             run that keeps nothing leaves valid empty files;
+//   --split   the C + 4 bins of split_prepare; a bin's files are made when it first receives a read, and PREFIX_split.tsv — `label TAB
+//             reads TAB file[ TAB file2]` per non-empty bin, in bin order — once every file is whole.
+// A run that cannot finish removes what it made, whichever die() on whichever thread ends it (remove_on_die): a truncated file would
 // look whole to gzip -t up to its last member.
-struct FilteredOutput {
-    BgzfOut out[2];
-    size_t n_files = 0;
-    uint64_t n_kept = 0;
-    PinnedBuf buf;
-    double ms = 0;
-    void open(const std::string &prefix, size_t nf, const std::vector<std::string> &fq) {
-        std::string cleaned = g_taxon.taxon;
-        std::replace(cleaned.begin(), cleaned.end(), ' ', '_');
-        n_files = nf;
-        for (size_t i = 0; i < nf; ++i) out[i].open(prefix + "_" + cleaned + (nf == 2 ? (i ? "_R2" : "_R1") : "") + ".fq.gz", mate_name(nf, i));
-        reserve_members(buf, nf, fq);
-    }
-    void write_step(cid_fastq *fr, const std::vector<uint8_t> &keep) {
-        const auto t = Clock::now();
-        for (size_t i = 0; i < n_files; ++i) {
-            size_t bytes = 0, n_members = 0;
-            uint64_t kept = 0;
-            int rc = cid_fastq_filter(fr, keep.data(), (int)i, buf.p, buf.cap, &bytes, &n_members, &kept);
-            if (rc == CID_ERR_INVALID && bytes > buf.cap) {   // (the members take more room than the buffer has: once more with that much)
-                buf.reserve(bytes + bytes / 8);
-                rc = cid_fastq_filter(fr, keep.data(), (int)i, buf.p, buf.cap, &bytes, &n_members, &kept);
-            }
-            if (rc != CID_OK) die("%s", cid_last_error());
-            out[i].write(buf.p, bytes, mate_name(n_files, i));
-            if (i == 0) n_kept += kept;
-        }
-        ms += ms_since(t);
-    }
-    void finish() {
-        for (size_t i = 0; i < n_files; ++i) out[i].close();
-        for (size_t i = 0; i < n_files; ++i) keep_on_die(out[i].path);
-        if (g_taxon.exclude)   // (read_filter.rs:119-129: either line counts the reads WRITTEN)
-            fprintf(stderr, "Excluded %llu read pairs  with classification containing '%s' from output files\n", (unsigned long long)n_kept, g_taxon.taxon.c_str());
-        else
-            fprintf(stderr, "Wrote %llu read-pairs with classification containing '%s' to output files\n", (unsigned long long)n_kept, g_taxon.taxon.c_str());
-        if (g_timing) fprintf(stderr, "timing: --taxon: %.0f ms in cid_fastq_filter (waiting for the classifier in flight included) and writing the members; coder: %s\n", ms,
-                              g_taxon.gz_matches ? "LZ77 matches (--gz-matches)" : "literals only");
-    }
-};
-
-// --split: the files of a sample, PREFIX_<name>.fq.gz (or _R1 + _R2) per bin that receives a read, opened when it first does, fed the
-// byte range cid_fastq_split hands back for the bin each step, and PREFIX_split.tsv — `label TAB reads TAB file[ TAB file2]` per
-// non-empty bin, in bin order — once every file is whole.  A run that cannot finish leaves neither (remove_on_die).
 static std::vector<std::string> g_split_names;   // split_prepare: the bins' labels; their file names are split_clean() of these
 static std::string split_clean(std::string name) {
     for (char &ch : name) if (ch == ' ' || ch == '/') ch = '_';
     return name;
 }
-struct SplitOutput {
+struct BinnedOutput {
+    const bool split = g_out.mode == ReadOutput::kSplit;
     std::string prefix, manifest;
+    std::vector<std::string> names, stems;   // per bin: its label, and what its file names carry of it
     std::vector<BgzfOut> out[2];
     std::vector<uint64_t> reads, bin_off, bin_reads;
     size_t n_files = 0, n_members = 0, n_short = 0;
@@ -595,17 +546,26 @@ struct SplitOutput {
     double ms = 0, ms_write = 0, ms_open = 0;
     void open(const std::string &pfx, size_t nf, const std::vector<std::string> &fq) {
         prefix = pfx; n_files = nf;
-        manifest = prefix + "_split.tsv";
-        (void)remove(manifest.c_str());   // (one of an earlier run would describe files this run replaces)
-        const size_t nb = g_split_names.size();
+        if (split) {
+            names = g_split_names;
+            for (const std::string &name : names) stems.push_back(split_clean(name));
+            manifest = prefix + "_split.tsv";
+            (void)remove(manifest.c_str());   // (one of an earlier run would describe files this run replaces)
+        } else {
+            names.assign(1, g_out.taxon);
+            stems = names;
+            std::replace(stems[0].begin(), stems[0].end(), ' ', '_');
+        }
+        const size_t nb = names.size();
         for (size_t i = 0; i < nf; ++i) out[i].resize(nb);
         reads.assign(nb, 0); bin_off.assign(nb + 1, 0); bin_reads.assign(nb, 0);
+        if (!split) for (size_t i = 0; i < nf; ++i) out[i][0].open(file_of(0, i), mate_name(nf, i));
         reserve_members(buf, nf, fq);
     }
-    std::string file_of(size_t b, size_t i) const { return prefix + "_" + split_clean(g_split_names[b]) + (n_files == 2 ? (i ? "_R2" : "_R1") : "") + ".fq.gz"; }
+    std::string file_of(size_t b, size_t i) const { return prefix + "_" + stems[b] + (n_files == 2 ? (i ? "_R2" : "_R1") : "") + ".fq.gz"; }
     void write_step(cid_fastq *fr, const std::vector<uint32_t> &bins) {
         const auto t = Clock::now();
-        const uint32_t nb = (uint32_t)g_split_names.size();
+        const uint32_t nb = (uint32_t)names.size();
         for (size_t i = 0; i < n_files; ++i) {
             size_t bytes = 0, nm = 0;
             int rc = cid_fastq_split(fr, bins.data(), nb, (int)i, buf.p, buf.cap, &bytes, bin_off.data(), bin_reads.data(), &nm);
@@ -636,26 +596,36 @@ struct SplitOutput {
         uint64_t n_reads = 0;
         for (size_t i = 0; i < n_files; ++i)
             for (BgzfOut &o : out[i]) if (o.f) { o.close(); ++n_out; }
+        for (uint64_t r : reads) n_reads += r;
+        if (split) write_manifest();
+        for (size_t i = 0; i < n_files; ++i)
+            for (BgzfOut &o : out[i]) if (!o.path.empty()) keep_on_die(o.path);
+        const char *coder = g_out.gz_matches ? "LZ77 matches (--gz-matches)" : "literals only";
+        if (split) {
+            keep_on_die(manifest);
+            fprintf(stderr, "Wrote %llu %s to %zu files by classification (%s)\n", (unsigned long long)n_reads, n_files == 2 ? "read pairs" : "reads", n_out, manifest.c_str());
+            if (g_timing) fprintf(stderr, "timing: --split: %.0f ms in cid_fastq_split (waiting for the classifier in flight included) and writing the members "
+                                  "(creating the files %.0f ms and writing to them %.0f ms of it); %zu members (%zu of them the last of a bin in its step: short), %llu bytes in %zu files; "
+                                  "coder: %s\n", ms, ms_open, ms_write - ms_open, n_members, n_short, (unsigned long long)bytes_out, n_out, coder);
+        } else {
+            if (g_out.exclude)   // (read_filter.rs:119-129: either line counts the reads WRITTEN)
+                fprintf(stderr, "Excluded %llu read pairs  with classification containing '%s' from output files\n", (unsigned long long)n_reads, g_out.taxon.c_str());
+            else
+                fprintf(stderr, "Wrote %llu read-pairs with classification containing '%s' to output files\n", (unsigned long long)n_reads, g_out.taxon.c_str());
+            if (g_timing) fprintf(stderr, "timing: --taxon: %.0f ms in cid_fastq_filter (waiting for the classifier in flight included) and writing the members; coder: %s\n", ms, coder);
+        }
+    }
+    void write_manifest() {
         FILE *m = fopen(manifest.c_str(), "w");
         if (m) remove_on_die(manifest);
         if (!m) die("could not create %s!", manifest.c_str());
         for (size_t b = 0; b < reads.size(); ++b) {
             if (!reads[b]) continue;
-            n_reads += reads[b];
-            fprintf(m, "%s\t%llu\t%s", g_split_names[b].c_str(), (unsigned long long)reads[b], file_of(b, 0).c_str());
+            fprintf(m, "%s\t%llu\t%s", names[b].c_str(), (unsigned long long)reads[b], file_of(b, 0).c_str());
             if (n_files == 2) fprintf(m, "\t%s", file_of(b, 1).c_str());
             fputc('\n', m);
         }
         if (fclose(m) != 0) die("could not write %s!", manifest.c_str());
-        for (size_t i = 0; i < n_files; ++i)
-            for (BgzfOut &o : out[i]) if (!o.path.empty()) keep_on_die(o.path);
-        keep_on_die(manifest);
-        fprintf(stderr, "Wrote %llu %s to %zu files by classification (%s)\n", (unsigned long long)n_reads, n_files == 2 ? "read pairs" : "reads", n_out, manifest.c_str());
-        if (g_timing) fprintf(stderr, "timing: --split: %.0f ms in cid_fastq_split (waiting for the classifier in flight included) and writing the members "
-                              "(creating the files %.0f ms and writing to them %.0f ms of it); %zu members (%zu of them the last of a bin in its step: short), %llu bytes in %zu files; "
-                              "coder: %s\n", ms, ms_open, ms_write - ms_open, n_members, n_short,
-                              (unsigned long long)bytes_out, n_out,
-                              g_taxon.gz_matches ? "LZ77 matches (--gz-matches)" : "literals only");
     }
 };
 
@@ -664,13 +634,12 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
     const auto t_enter = Clock::now();
     cid_fastq *fr = nullptr;
     CID_TRY(cid_fastq_create(ctx, (int)n_files, qual_offset, &fr));
-    FilteredOutput filtered;
-    SplitOutput dealt;
-    if (g_taxon.on || g_taxon.split) {
+    const bool writes_reads = g_out.mode != ReadOutput::kNone;
+    BinnedOutput dealt;
+    if (writes_reads) {
         CID_TRY(cid_fastq_keep_steps(fr, 1));
-        if (g_taxon.gz_matches) CID_TRY(cid_fastq_filter_matches(fr, 1));
-        if (g_taxon.on) filtered.open(prefix, n_files, fq);
-        else dealt.open(prefix, n_files, fq);
+        if (g_out.gz_matches) CID_TRY(cid_fastq_filter_matches(fr, 1));
+        dealt.open(prefix, n_files, fq);
     }
     classifier.ids_stay_with_counted(true);
     const size_t target = read_id_mt_pe::device_fastq_stretch_bytes(b.colors.size());
@@ -731,12 +700,11 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
             ms_classify += ms_since(tc);
             for (size_t i = 0; i < n_files; ++i) if (pending[i]) --pending[i];
             if (rc == CID_ERR_UNSUPPORTED) {   // (tests inject one through the library: cid_ctx_tune fastq_refuse_at_step / CID_FASTQ_REFUSE_AT_STEP)
-                if (g_taxon.on)   // the host front end writes no filtered reads; die() leaves no partial .fq.gz behind
-                    die("%s — --taxon writes the kept reads on the device front end only, which gave way; the partial .fq.gz files were removed "
-                        "(run read_id without --taxon, or the reference's read_filter)", cid_last_error());
-                if (g_taxon.split)
-                    die("%s — --split writes the reads on the device front end only, which gave way; the partial .fq.gz files were removed "
-                        "(run read_id without --split, or the reference's read_filter once per label)", cid_last_error());
+                if (writes_reads)   // the host front end writes no reads; die() leaves no partial .fq.gz behind
+                    die(dealt.split ? "%s — --split writes the reads on the device front end only, which gave way; the partial .fq.gz files were removed "
+                                      "(run read_id without --split, or the reference's read_filter once per label)"
+                                    : "%s — --taxon writes the kept reads on the device front end only, which gave way; the partial .fq.gz files were removed "
+                                      "(run read_id without --taxon, or the reference's read_filter)", cid_last_error());
                 fprintf(stderr, "note: %s — %s\n", cid_last_error(), first ? "using the host front end" : "starting over with the host front end");
                 cid_fastq_destroy(fr);
                 classifier.ids_stay_with_counted(false);
@@ -746,7 +714,7 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
             first = false;
             ++n_steps;
         }
-        const bool filter_step = (g_taxon.on || g_taxon.split) && have && have_n;
+        const bool write_step = writes_reads && have && have_n;
         if (have && have_n) {
             const auto tb = Clock::now();
             std::unique_ptr<Counted> c = classifier.take_counted();
@@ -768,9 +736,8 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
         have = false;
         for (size_t i = 0; i < n_files; ++i)   // the stretches after this one: inflated while this one is classified
             while (more[i] && pending[i] < ahead + 1) push_next(i);
-        // --taxon: the step just handed to the poll stays on the device until the next _end; its labels come back from the poll
-        if (filter_step && g_taxon.on) filtered.write_step(fr, classifier.take_keep());
-        if (filter_step && g_taxon.split) dealt.write_step(fr, classifier.take_bins());
+        // --taxon / --split: the step just handed to the poll stays on the device until the next _end; its reads' bins come back from the poll
+        if (write_step) dealt.write_step(fr, classifier.take_bins());
         if (!begin) break;
         const auto tc = Clock::now();
         const int rc = cid_fastq_classify_end(fr, &have_n, &have_ne, &have_idb);
@@ -782,8 +749,7 @@ FrontEnd classify_bgzf_on_device(cid_ctx *ctx, const std::vector<std::string> &f
         t_gpu = Clock::now();
     }
     cid_fastq_destroy(fr);
-    if (g_taxon.on) filtered.finish();
-    if (g_taxon.split) dealt.finish();
+    if (writes_reads) dealt.finish();
     if (g_timing)
         fprintf(stderr, "timing: device front end: waiting for the file reader %.0f ms, push (H2D of the members) %.0f ms, classify %.0f ms, fetch %.0f ms "
                 "(+ %.0f ms sizing its buffers), handing the rows to the poll %.0f ms; %.0f ms until the first stretch was pushed, %.0f ms in all\n",
@@ -836,8 +802,8 @@ void read_id_mt_pe::per_read_stream_se(cid_ctx *ctx, const std::vector<std::stri
     if (!out) die("could not create outfile!");
     ReadBatch rb;
     const bool on_device = device_fastq_wanted(fq, 1);
-    if ((g_taxon.on || g_taxon.split) && !on_device)
-        die("%s needs the device front end (block-gzip input on one GPU; recompress with bgzip)", g_taxon.split ? "--split" : "--taxon");
+    if (g_out.mode != ReadOutput::kNone && !on_device)
+        die("%s needs the device front end (block-gzip input on one GPU; recompress with bgzip)", g_out.mode == ReadOutput::kSplit ? "--split" : "--taxon");
     if (on_device && !cli_env("COLORID_POLL_THREADS"))
         g_poll_threads = std::max(g_poll_threads, read_id_mt_pe::device_fastq_host_share() > 0.0 ? std::min(6, cpu_budget() * 3 / 8) : std::min(12, cpu_budget() * 5 / 8));   // no packing threads beside them: a stretch's poll on 4 threads takes 18 ms, the GPU side 13
     auto make_classifier = [&] { return std::unique_ptr<BatchClassifier>(new BatchClassifier(ctx, b, d, fp_correct, start_sample, fp, out, "%llu read pairs classified\r")); };
@@ -873,8 +839,8 @@ void read_id_mt_pe::per_read_stream_pe(cid_ctx *ctx, const std::vector<std::stri
     if (!out) die("could not create outfile!");
     ReadBatch rb;
     const bool on_device = device_fastq_wanted(fq, 2);
-    if ((g_taxon.on || g_taxon.split) && !on_device)
-        die("%s needs the device front end (block-gzip input on one GPU; recompress with bgzip)", g_taxon.split ? "--split" : "--taxon");
+    if (g_out.mode != ReadOutput::kNone && !on_device)
+        die("%s needs the device front end (block-gzip input on one GPU; recompress with bgzip)", g_out.mode == ReadOutput::kSplit ? "--split" : "--taxon");
     if (on_device && !cli_env("COLORID_POLL_THREADS"))
         g_poll_threads = std::max(g_poll_threads, read_id_mt_pe::device_fastq_host_share() > 0.0 ? std::min(6, cpu_budget() * 3 / 8) : std::min(12, cpu_budget() * 5 / 8));
     auto make_classifier = [&] { return std::unique_ptr<BatchClassifier>(new BatchClassifier(ctx, b, d, fp_correct, start_sample, fp, out, "%llu read pairs classified\r")); };

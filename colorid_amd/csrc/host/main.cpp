@@ -738,11 +738,11 @@ bool wants_device_front_end(const Args &a, const std::vector<std::string> &fq) {
 }
 
 // --taxon TAXON [--exclude] [--gz-matches] (read_id, batch_id): the reference's read_filter fused into the classifying pass — the kept reads
-// are cut and compressed on the device (cid_fastq_filter; --gz-matches: with LZ77 matches, cid_fastq_filter_matches), so only block-gzip
-// input on one GPU is served; everything else is refused here, before the GPU context is made.
+// are cut and compressed on the device (cid_fastq_split with one bin; --gz-matches: with LZ77 matches, cid_fastq_filter_matches), so only
+// block-gzip input on one GPU is served; everything else is refused here, before the GPU context is made.
 // --split [--gz-matches]: every label's reads to a file of its own in the same pass (cid_fastq_split), the same route and the same refusals.
-read_id_mt_pe::TaxonFilter taxon_filter(const Args &a) {
-    read_id_mt_pe::TaxonFilter f;
+read_id_mt_pe::ReadOutput read_output(const Args &a) {
+    read_id_mt_pe::ReadOutput f;
     const bool exclude = a.flags.count("exclude") != 0;
     const bool matches = a.flags.count("gz-matches") != 0;
     const bool split = a.flags.count("split") != 0;
@@ -751,12 +751,12 @@ read_id_mt_pe::TaxonFilter taxon_filter(const Args &a) {
     if (exclude && !a.has("taxon")) die("error: --exclude needs --taxon TAXON (the classification to leave out)");
     if (matches && !a.has("taxon") && !split) die("error: --gz-matches needs --taxon TAXON or --split (it chooses how the reads written are compressed)");
     f.gz_matches = matches;
-    if (split) { f.split = true; return f; }
+    if (split) { f.mode = f.kSplit; return f; }
     if (!a.has("taxon")) return f;
-    f.on = true; f.taxon = a.one("taxon"); f.exclude = exclude;
+    f.mode = f.kTaxon; f.taxon = a.one("taxon"); f.exclude = exclude;
     return f;
 }
-void require_filter_route(const Args &a, const std::vector<std::string> &fq, bool split) {
+void require_output_route(const Args &a, const std::vector<std::string> &fq, bool split) {
     if (wants_device_front_end(a, fq)) return;
     const char *why = !one_gpu_run(a) ? "it runs on one GPU only (no --gpus / --devices / --placement)"
                       : (cli_env("COLORID_DEVICE_FASTQ") && atoi(cli_env("COLORID_DEVICE_FASTQ")) == 0) ? "COLORID_DEVICE_FASTQ=0 turns the device front end off"
@@ -806,9 +806,10 @@ int cmd_read_id(int argc, char **argv) {
     const std::vector<std::string> fq = a.values.at("query");
     const ClassifyFlags flags = classify_flags(a);
     const std::string prefix = a.one("prefix");
-    const read_id_mt_pe::TaxonFilter filter = taxon_filter(a);
-    if (filter.on || filter.split) require_filter_route(a, fq, filter.split);
-    read_id_mt_pe::set_taxon_filter(filter);
+    const read_id_mt_pe::ReadOutput output = read_output(a);
+    const bool split = output.mode == output.kSplit;
+    if (output.mode != output.kNone) require_output_route(a, fq, split);
+    read_id_mt_pe::set_read_output(output);
     if (cli_env("COLORID_GPU_INFLATE") && atoi(cli_env("COLORID_GPU_INFLATE")) > 0) LineReader::inflate_on_gpu(num_or<int>(a, "device", 0));
     const bool device_front_end = wants_device_front_end(a, fq);
     read_ahead(fq, device_front_end);
@@ -820,7 +821,7 @@ int cmd_read_id(int argc, char **argv) {
     replicate(gpus, b);
     warm.join();
     phase_done("index load");
-    if (filter.split) read_id_mt_pe::split_prepare(b, fq.size() > 1 ? 2 : 1);
+    if (split) read_id_mt_pe::split_prepare(b, fq.size() > 1 ? 2 : 1);
     classify_sample(ctx, b, fq, prefix, flags);
     LineReader::drop_prefetched();
     BgzfMemberReader::drop_prefetched();
@@ -847,9 +848,10 @@ int cmd_batch_id(int argc, char **argv) {
     const std::string tag = a.one("tag");
     const auto sheet = tab_to_map(a.one("query"));
     std::vector<std::pair<std::string, std::vector<std::string>>> samples(sheet.begin(), sheet.end());
-    const read_id_mt_pe::TaxonFilter filter = taxon_filter(a);
-    if (filter.on || filter.split) for (const auto &sm : samples) require_filter_route(a, sm.second, filter.split);
-    read_id_mt_pe::set_taxon_filter(filter);
+    const read_id_mt_pe::ReadOutput output = read_output(a);
+    const bool split = output.mode == output.kSplit;
+    if (output.mode != output.kNone) for (const auto &sm : samples) require_output_route(a, sm.second, split);
+    read_id_mt_pe::set_read_output(output);
     if (cli_env("COLORID_GPU_INFLATE") && atoi(cli_env("COLORID_GPU_INFLATE")) > 0) LineReader::inflate_on_gpu(num_or<int>(a, "device", 0));
     std::vector<char> on_device(samples.size(), 0);
     bool any_on_device = false;
@@ -863,7 +865,7 @@ int cmd_batch_id(int argc, char **argv) {
     replicate(gpus, b);
     warm.join();
     phase_done("index load");
-    if (filter.split) {
+    if (split) {
         size_t most = 1;
         for (const auto &sm : samples) most = std::max<size_t>(most, sm.second.size() > 1 ? 2 : 1);
         read_id_mt_pe::split_prepare(b, most);

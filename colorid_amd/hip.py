@@ -829,30 +829,32 @@ class FastqReader:
         """the kept records (keep[r] != 0) of file `file` of the last ended step, `header\\nsequence\\n+\\nquality\\n` each, as
         block-gzip members -> (members [bytes], n_members, n_kept)"""
         keep = np.ascontiguousarray(keep, np.uint8)
-        nb, nm, nk = C.c_size_t(0), C.c_size_t(0), C.c_uint64(0)
-        out = np.zeros(1 << 16, np.uint8)
-        rc = self.lib.cid_fastq_filter(self.h, _p(keep), file, _p(out), out.size, C.byref(nb), C.byref(nm), C.byref(nk))
-        if rc == CID_ERR_INVALID and nb.value > out.size:   # with the size the members take: the same call with that much room
+        nm, nk = C.c_size_t(0), C.c_uint64(0)
+        members = self._members(1 << 16, lambda out, nb: self.lib.cid_fastq_filter(self.h, _p(keep), file, _p(out), out.size, nb, C.byref(nm), C.byref(nk)))
+        return members, nm.value, nk.value
+
+    @staticmethod
+    def _members(cap, call):
+        """call(out, byref(n_bytes)) with `cap` bytes of room, and once more with the size it reports when that was too little"""
+        nb = C.c_size_t(0)
+        out = np.zeros(max(cap, 1), np.uint8)
+        rc = call(out[:cap], C.byref(nb))
+        if rc == CID_ERR_INVALID and nb.value > cap:   # with the size the members take: the same call with that much room
             out = np.zeros(nb.value, np.uint8)
-            rc = self.lib.cid_fastq_filter(self.h, _p(keep), file, _p(out), out.size, C.byref(nb), C.byref(nm), C.byref(nk))
+            rc = call(out, C.byref(nb))
         check(rc)
-        return out[:nb.value].tobytes(), nm.value, nk.value
+        return out[:nb.value].tobytes()
 
     def split(self, bins, n_bins, file=0, cap=1 << 16):
         """cid_fastq_split: the records of file `file` of the last ended step dealt into n_bins outputs (bins[r] < n_bins, or CID_SPLIT_DROP
         = 0xFFFFFFFF: nowhere) -> (members [bytes], bin_off [uint64, n_bins + 1], bin_reads [uint64, n_bins], n_members): bin b's
         block-gzip members are members[bin_off[b]:bin_off[b + 1]]; cap: the room offered first (grown to what the call reports)"""
         bins = np.ascontiguousarray(bins, np.uint32)
-        nb, nm = C.c_size_t(0), C.c_size_t(0)
+        nm = C.c_size_t(0)
         off = np.zeros(n_bins + 1, np.uint64)
         reads = np.zeros(max(n_bins, 1), np.uint64)
-        out = np.zeros(max(cap, 1), np.uint8)
-        rc = self.lib.cid_fastq_split(self.h, _p(bins), n_bins, file, _p(out), cap, C.byref(nb), _p(off), _p(reads), C.byref(nm))
-        if rc == CID_ERR_INVALID and nb.value > cap:   # with the size the members take: the same call with that much room
-            out = np.zeros(nb.value, np.uint8)
-            rc = self.lib.cid_fastq_split(self.h, _p(bins), n_bins, file, _p(out), out.size, C.byref(nb), _p(off), _p(reads), C.byref(nm))
-        check(rc)
-        return out[:nb.value].tobytes(), off, reads[:n_bins], nm.value
+        members = self._members(cap, lambda out, nb: self.lib.cid_fastq_split(self.h, _p(bins), n_bins, file, _p(out), out.size, nb, _p(off), _p(reads), C.byref(nm)))
+        return members, off, reads[:n_bins], nm.value
 
     def count_kmers(self, kmerset, max_pushes=0):
         """every complete record held adds its reads' k-mers to `kmerset` (search's fastq producers); -> reads taken"""

@@ -657,9 +657,10 @@ CID_CORE int cid_fastq_fetch(cid_fastq *, uint32_t *n_kmers, uint8_t *status, ui
  *   keep_steps   on: from the next _end on, a step's text and line ends stay on the device until the NEXT _end (like its results for
  *                fetch), also across the _begin of the step after it.  Costs one more generation of text + 4 bytes per line in device
  *                memory per file (the next step appends to a buffer of its own).  Off (the default): nothing is kept, today's path.
- *                On top of that, while it runs, a filter call takes from the ctx's block cache, for K bytes of kept text: K for the
- *                kept text, K + 31 per member for the gathered members and 65 312 per member (K / 65 280 members) for the slots
- *                the members are coded into, ~3 K in all plus ~10 bytes per read of the step; given back before it returns.
+ *                On top of that, while it runs, a filter call takes from the ctx's block cache what a split call with one bin takes
+ *                (below): for K bytes of kept text, K for the kept text, K + 31 per member for the gathered members and 65 312 + 12
+ *                per member (K / 65 280 members) for the slots the members are coded into, ~3 K in all plus 12 bytes per kept
+ *                read; given back before it returns.
  *                With filter_matches on, also the LZ77 coder's tokens: 261 120 bytes per workgroup launched, min(members, 6 x CUs)
  *                of them (383 MiB at most on 256 CUs).
  *   filter_matches   on: filter sends the kept text through cid_bgzf_deflate_lz_dev (members with LZ77 matches: smaller files, a
@@ -668,10 +669,12 @@ CID_CORE int cid_fastq_fetch(cid_fastq *, uint32_t *n_kmers, uint8_t *status, ui
  *   filter       keep[n_reads] (0 / 1, the step's reads in order); for every kept read the record of file `file` is written as
  *                `header\nsequence\n+\nquality\n` (read_filter.rs:89-105: the lines as lines() gives them — "\r\n" stripped, an
  *                unterminated last line counts —, the sequence as the input has it, not quality-masked, whatever followed the '+'
- *                dropped), in input order; the text goes through cid_bgzf_deflate_dev and the members come back in `members`.
+ *                dropped), in input order; the members — the bytes cid_bgzf_deflate_dev makes of that text — come back in `members`.
+ *                It is split (below) into ONE bin, keep[r] ? 0 : CID_SPLIT_DROP, through the same kernels: the library has no
+ *                filter path of its own.  *n_kept = the bin's reads, *n_members = its members.
  *                For pairs: once per file with the same flags.  Runs on the ctx stream (behind a classifier launched since).
  *                CID_ERR_STATE: keep_steps is off or no step has ended yet; CID_ERR_INVALID: members_cap too small — *members_bytes
- *                then says how much room the same call needs. */
+ *                then says how much room the same call needs (*n_members and *n_kept are set as well). */
 int cid_fastq_keep_steps(cid_fastq *, int on);
 int cid_fastq_filter_matches(cid_fastq *, int on);
 int cid_fastq_filter(cid_fastq *, const uint8_t *keep, int file, uint8_t *members, size_t members_cap, size_t *members_bytes, size_t *n_members,
@@ -683,14 +686,13 @@ int cid_fastq_filter(cid_fastq *, const uint8_t *keep, int file, uint8_t *member
  *                  records in input order, its text cut every 65 280 bytes counted from the start of THAT bin — no member spans two
  *                  bins, an empty bin is an empty range.  bin_reads[b] = the reads of bin b; *n_members = the members of all bins.
  *                  The coder is the one cid_fastq_filter_matches selected.  With every bin[r] in {0, CID_SPLIT_DROP}, bin 0's bytes
- *                  are cid_fastq_filter(keep = (bin == 0))'s, byte for byte.
- *   How: a stable counting sort of the read indices by bin on the host (O(n_reads + n_bins), beside the walk filter makes over keep[]),
- *   then on the device one scan over the records' sizes in output order, per bin its bytes, its base in the gathered text (rounded up to
+ *                  are cid_fastq_filter(keep = (bin == 0))'s, byte for byte: that call IS this one with n_bins = 1.
+ *   How: a stable counting sort of the read indices by bin on the host (O(n_reads + n_bins)), then on the device one scan over the records' sizes in output order, per bin its bytes, its base in the gathered text (rounded up to
  *   16 bytes, so that every piece is aligned as the pieces of cid_bgzf_deflate are) and its first piece, one wave per record for the copy,
- *   a table of (offset, length) per piece for the coder, and the gather.  Two synchronisations before the members' copy, as in filter.
+ *   a table of (offset, length) per piece for the coder, and the gather.  Two synchronisations before the members' copy.
  *   CID_ERR_STATE: keep_steps is off or no step has ended yet.  CID_ERR_INVALID: n_bins == 0; a bin[r] that is neither < n_bins nor
  *   CID_SPLIT_DROP (checked before anything is launched); members_cap too small — *members_bytes then says how much room the same call
- *   needs, and no member has been written.
+ *   needs (*n_members and bin_reads are set as well), and no member has been written.
  *   From the ctx's block cache while it runs, given back before it returns, for K bytes of text in all bins: K + 16 per bin for the
  *   gathered text, K + 31 per member + 31 per bin for the members, 65 312 + 12 per member for the slots and the piece table (members
  *   <= K / 65 280 + the non-empty bins), 12 bytes per read dealt and 36 per bin; with filter_matches the LZ77 coder's tokens as in filter. */

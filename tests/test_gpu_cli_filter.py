@@ -94,6 +94,29 @@ def test_read_id_taxon_writes_the_kept_reads(sample, tmp_path, paired, exclude):
         assert f"Wrote {sum(keep)} read-pairs with classification containing '{TAXON}' to output files" in err
 
 
+@pytest.mark.parametrize("paired", [False, True])
+@pytest.mark.parametrize("taxon,exclude", [("no such label", False), ("t", True)])
+def test_a_run_that_keeps_nothing_leaves_whole_empty_files(sample, tmp_path, paired, taxon, exclude):
+    """a taxon that no label contains, and --exclude of one that every label contains ("t": Listeria, no_hits, too_short,
+    no_significant_hits): the files are made when the run opens them, not at a bin's first read, and hold the end-of-file block alone"""
+    d, bxi, texts = sample
+    files = []
+    for mate, (_, records) in enumerate(texts[:2 if paired else 1]):
+        files.append(str(tmp_path / f"few_{mate + 1}.fastq.gz"))
+        _write_bgzf(files[-1], restated(records[:300], [1] * 300), np.random.default_rng(23))
+    pre = str(tmp_path / "nothing")
+    err = colorid("read_id", "-b", bxi, "-q", *files, "-n", pre, "--taxon", taxon, *(["--exclude"] if exclude else []))
+    keep = kept_by_the_reference_rule(open(pre + "_reads.txt").read(), taxon, exclude)
+    assert len(keep) == 300 and not any(keep)
+    stem = pre + "_" + taxon.replace(" ", "_")
+    for name in ([stem + "_R1.fq.gz", stem + "_R2.fq.gz"] if paired else [stem + ".fq.gz"]):
+        assert open(name, "rb").read() == EOF_BLOCK, name
+    if exclude:
+        assert f"Excluded 0 read pairs  with classification containing '{taxon}' from output files" in err
+    else:
+        assert f"Wrote 0 read-pairs with classification containing '{taxon}' to output files" in err
+
+
 def test_batch_id_taxon_writes_each_samples_files(sample, tmp_path):
     d, bxi, texts = sample
     sheet = tmp_path / "samples.tsv"

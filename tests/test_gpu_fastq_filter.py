@@ -1,13 +1,14 @@
 """cid_fastq_filter: the kept records of a classified step, written by the device as block-gzip members, against a restatement of the
 reference's read_filter (src/read_filter.rs:60-116 / :154-178): the lines as lines() gives them, four per record, a kept record written
 as `header\\nsequence\\n+\\nquality\\n` — the sequence as the input has it, whatever followed the '+' dropped."""
+import ctypes as C
 import zlib
 
 import numpy as np
 import pytest
 
 import colorid_amd
-from colorid_amd._lib import CID_ERR_STATE
+from colorid_amd._lib import CID_ERR_INVALID, CID_ERR_STATE
 from test_gpu_fastq import line_loop_records, world  # noqa: F401  (the toy index of the front end's tests)
 
 pytestmark = pytest.mark.gpu
@@ -110,6 +111,50 @@ def test_filter_of_a_step_while_the_next_one_runs(hip_ctx, world):
     assert n1 + n2 == 300
     blob, _, n_kept = fr.filter(np.ones(n2, np.uint8), 0)
     assert n_kept == n2 and gunzip(blob) == restated(records[n1:], [1] * n2)
+    fr.close()
+
+
+def test_the_c_entry_point_without_a_record_and_without_room(hip_ctx, world):
+    """what a caller of cid_fastq_filter itself relies on, for either file of a pair: a step without a complete record answers CID_OK with
+    zeros whatever `keep` is; too little room answers CID_ERR_INVALID with the buffer untouched, *n_kept set and *members_bytes the very
+    size with which the same call then succeeds"""
+    oix, hx, genomes = world
+    lib = hip_ctx.lib
+    rng = np.random.default_rng(10)
+    texts = []
+    for mate in (1, 2):
+        out = bytearray()
+        for i in range(12):
+            L = int(rng.integers(40, 61))
+            a = int(rng.integers(0, len(genomes[i % 5]) - L))
+            out += b"@s%d/%d\n" % (i, mate) + genomes[i % 5][a:a + L] + b"\n+\n" + bytes(rng.integers(35, 74, L).astype(np.uint8)) + b"\n"
+        texts.append(bytes(out))
+    records = [line_loop_records(t) for t in texts]
+    fr = colorid_amd.FastqReader(hip_ctx, 2, 0)
+    fr.keep_steps()
+    nb, nm, nk = C.c_size_t(7), C.c_size_t(7), C.c_uint64(7)
+
+    def call(keep, f, buf):
+        return lib.cid_fastq_filter(fr.h, keep.ctypes.data_as(C.c_void_p) if keep is not None else None, f, buf.ctypes.data_as(C.c_void_p), buf.size,
+                                    C.byref(nb), C.byref(nm), C.byref(nk))
+    for f in range(2):
+        fr.push_text(f, texts[f][:20])                                           # half a record
+    assert len(fr.classify(hx, 1, 3)[0]) == 0
+    out = np.full(64, 0xAB, np.uint8)
+    for f in range(2):
+        nb.value = nm.value = nk.value = 7
+        assert call(None, f, out) == 0 and (nb.value, nm.value, nk.value) == (0, 0, 0) and np.all(out == 0xAB)
+    for f in range(2):
+        fr.push_text(f, texts[f][20:], last=True)
+    assert len(fr.classify(hx, 1, 3)[0]) == 12
+    keep = np.array([1, 0, 1, 1, 0, 1, 1, 1, 0, 1, 1, 0], np.uint8)
+    for f in range(2):
+        assert call(keep, f, out) == CID_ERR_INVALID and nb.value > out.size and np.all(out == 0xAB)
+        assert (nk.value, nm.value) == (8, 1)
+        room = np.full(nb.value, 0xAB, np.uint8)
+        nk.value = 0
+        assert call(keep, f, room) == 0 and nb.value == room.size and (nk.value, nm.value) == (8, 1)
+        assert gunzip(room.tobytes()) == restated(records[f], keep)              # (gunzip takes every byte: the members end at the buffer's last)
     fr.close()
 
 

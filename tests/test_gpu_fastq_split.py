@@ -115,9 +115,13 @@ def test_members_are_cut_from_the_start_of_each_bin(hip_ctx, world):
 
 @pytest.mark.parametrize("matches", [False, True])
 def test_one_bin_is_cid_fastq_filter_byte_for_byte(hip_ctx, world, matches):
+    """cid_fastq_filter is cid_fastq_split with one bin, so the first comparison holds a path against itself; the second holds it against
+    the contiguous coder (cid_bgzf_deflate / cid_bgzf_deflate_lz of the restated text), which shares no layout code with the segment table"""
+    from colorid_amd.hip import bgzf_deflate
     oix, hx, genomes = world
     rng = np.random.default_rng(44)
     text = make_text(rng, genomes, 300, 1, True)
+    records = line_loop_records(text)
     fr, n = one_step(hip_ctx, hx, [text])
     assert n == 300
     fr.filter_matches(matches)
@@ -126,6 +130,11 @@ def test_one_bin_is_cid_fastq_filter_byte_for_byte(hip_ctx, world, matches):
         bins = np.where(keep != 0, 0, DROP).astype(np.uint32)
         blob, off, bin_reads, n_members = fr.split(bins, 1, 0)
         assert blob == want and (n_members, int(bin_reads[0])) == (want_members, want_kept) and off.tolist() == [0, len(want)]
+        kept_text = restated(records, bins.tolist(), 0)
+        if keep.all():                                                            # with the empty sequence and the 70 000-base record: several members
+            assert n_members > 1 and records[7][1] == b"" and len(records[150][1]) == 70_000
+        contiguous, member_len = bgzf_deflate(hip_ctx, kept_text, matches)
+        assert blob == contiguous and n_members == len(member_len)
         bins3 = np.where(keep != 0, 1, DROP).astype(np.uint32)                    # the same records as bin 1 of 3
         blob3, off3, reads3, _ = fr.split(bins3, 3, 0)
         assert blob3 == want and off3.tolist() == [0, 0, len(want), len(want)] and reads3.tolist() == [0, want_kept, 0]

@@ -7,11 +7,13 @@
   (b) the command line: an index of 16 random 1 Mb genomes (m = 5 M, n = 4, k = 31), the reads drawn from them with 1 % errors and
       written as block gzip; `read_id` without the flags, `read_id --taxon genomeA` (8 of the 16 genomes: about half the reads kept), the
       same with `--gz-matches` and
-      `read_id` without the flags from PARENT_BIN (the parent commit's binary), alternating, REPS times each after one warm-up: the
-      whole-process wall clock and the classification phase (COLORID_TIMING), then one traced --taxon run for the filter's kernels.
+      the same three commands from PARENT_BIN (the parent commit's binary), alternating, REPS (EXP_REPS, default 3) times each after one
+      warm-up: the whole-process wall clock, the classification phase and the `timing: --taxon:` line (COLORID_TIMING), whether either
+      binary's .fq.gz files are the same bytes, then one traced --taxon run of either binary for the filter step's kernels.
 
-Run on the GPU box:   python3 tools/profile_filter.py OUT_DIR [PARENT_BIN]
-writes OUT_DIR/filter_summary.md, filter_deflate.json, filter_deflate_kernel_stats.csv, filter_cli_kernel_stats.csv"""
+Run on the GPU box:   python3 tools/profile_filter.py OUT_DIR [PARENT_BIN [cli]]      (cli: section (b) alone)
+writes OUT_DIR/filter_summary.md, filter_deflate.json, filter_deflate_kernel_stats.csv, filter_cli_kernel_stats.csv,
+filter_cli_parent_kernel_stats.csv"""
 import json
 import os
 import pathlib
@@ -27,7 +29,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 BIN = os.path.join(ROOT, "colorid_amd", "bin", "colorid")
-REPS = 3
+REPS = int(os.environ.get("EXP_REPS", 3))
 G, LG, R = 16, 1_000_000, int(os.environ.get("EXP_READS", 1_000_000))
 
 from profile_merge import kernel_stats, run   # noqa: E402
@@ -80,12 +82,17 @@ def rng_of(xs, unit, fmt="{:.2f}"):
     return (fmt.format(min(xs)) + "–" + fmt.format(max(xs)) + " " + unit + " (" + ", ".join(fmt.format(x) for x in xs) + ")") if xs else "n/a"
 
 
-def main():
-    out_dir = os.path.abspath(sys.argv[1])
-    parent_bin = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 else None
-    os.makedirs(out_dir, exist_ok=True)
-    lines = [f"# `read_id --taxon`: the device compressor and the fused filter, {R:,} x 150 bp reads", ""]
-    # ---- (a) the compressor alone
+def taxon_line_ms(stderr):
+    m = re.search(r"timing: --taxon: (\d+) ms", stderr)
+    return int(m.group(1)) if m else None
+
+
+# every kernel the filter step launches, either binary's: the copy, the coder, the gather and the scans that size and lay them out
+FILTER_STEP_KERNELS = ("k_bgzf_deflate", "k_bgzf_gather", "k_bgzf_piece", "k_bgzf_seg", "k_fq_filter", "k_fq_split",
+                       "FqKeepIn", "FqOrderIn", "DefLenIn", "DefSegRoomIn", "DefSegPiecesIn")
+
+
+def compressor_alone(out_dir, lines):
     exp = [sys.executable, os.path.join(ROOT, "tools", "exp_deflate.py")]
     p, _ = run(exp, env=dict(os.environ, EXP_READS=str(R)), limit=900)
     djs = [json.loads(ln) for ln in p.stdout.strip().splitlines() if ln.startswith("{")]
@@ -114,6 +121,15 @@ def main():
         if any(k in name for k in ("k_bgzf_deflate", "k_bgzf_gather", "scan")):
             n, t = int(r["Calls"]), float(r["TotalDurationNs"]) / 1e6
             lines.append(f"| `{name.split('(')[0][-60:]}` | {n} | {t:.2f} | {t / n:.3f} |")
+
+
+def main():
+    out_dir = os.path.abspath(sys.argv[1])
+    parent_bin = os.path.abspath(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[2] else None
+    os.makedirs(out_dir, exist_ok=True)
+    lines = [f"# `read_id --taxon`: the device compressor and the fused filter, {R:,} x 150 bp reads", ""]
+    if sys.argv[3:] != ["cli"]:
+        compressor_alone(out_dir, lines)
     # ---- (b) the command line
     work = pathlib.Path(tempfile.mkdtemp(prefix="filter_prof_"))
     try:
@@ -124,34 +140,48 @@ def main():
         cmds = {"plain": [BIN, "read_id", *q, "-n", str(work / "plain")],
                 "taxon": [BIN, "read_id", *q, "-n", str(work / "taxon"), "--taxon", "genomeA"],
                 "taxon_lz": [BIN, "read_id", *q, "-n", str(work / "taxon_lz"), "--taxon", "genomeA", "--gz-matches"]}
-        if parent_bin:
+        if parent_bin:                                           # (the parent's --taxon runs follow this commit's directly: alternating)
             cmds["parent"] = [parent_bin, "read_id", *q, "-n", str(work / "parent")]
+            cmds["parent_taxon"] = [parent_bin, *cmds["taxon"][1:-3], str(work / "ptaxon"), "--taxon", "genomeA"]
+            cmds["parent_taxon_lz"] = [*cmds["parent_taxon"][:-3], str(work / "ptaxon_lz"), "--taxon", "genomeA", "--gz-matches"]
         run(cmds["plain"], env=env)                              # a warm-up nobody counts: index and reads come into the page cache
-        walls, cls, first = {k: [] for k in cmds}, {k: [] for k in cmds}, {}
+        walls, cls, flt, first = {k: [] for k in cmds}, {k: [] for k in cmds}, {k: [] for k in cmds}, {}
         for rep in range(REPS):                                  # alternating, so a drift of the box hits them alike
             for tag, cmd in cmds.items():
                 p, wall = run(cmd, env=env)
                 walls[tag].append(wall)
                 print(f"{tag}: {wall:.2f} s", file=sys.stderr, flush=True)
                 cls[tag].append(classification_ms(p.stderr))
+                flt[tag].append(taxon_line_ms(p.stderr))
                 first.setdefault(tag, phases(p.stderr))
         same = all(open(work / f"taxon_{s}.txt", "rb").read() == open(work / f"plain_{s}.txt", "rb").read() for s in ("reads", "counts"))
         out_gz = os.path.getsize(work / "taxon_genomeA.fq.gz")
         out_gz_lz = os.path.getsize(work / "taxon_lz_genomeA.fq.gz")
-        cli_stats = kernel_stats(out_dir, "filter_cli", cmds["taxon"])
+        if parent_bin:
+            same_files = all(open(work / f"taxon{s}_genomeA.fq.gz", "rb").read() == open(work / f"ptaxon{s}_genomeA.fq.gz", "rb").read() for s in ("", "_lz"))
+        traced = {"taxon": kernel_stats(out_dir, "filter_cli", cmds["taxon"])}
+        if parent_bin:
+            traced["parent_taxon"] = kernel_stats(out_dir, "filter_cli_parent", cmds["parent_taxon"])
         label = {"plain": "`read_id`", "taxon": "`read_id --taxon genomeA`", "taxon_lz": "`read_id --taxon genomeA --gz-matches`",
-                 "parent": "`read_id`, the parent commit's binary"}
+                 "parent": "`read_id`, the parent commit's binary", "parent_taxon": "`read_id --taxon genomeA`, the parent commit's binary",
+                 "parent_taxon_lz": "`read_id --taxon genomeA --gz-matches`, the parent commit's binary"}
         lines += ["", "## (b) the command line", "",
                   f"index: {G} genomes of {LG:,} bases, m = 5 M, n = 4, k = 31; reads: {text_bytes / 1e6:.1f} MB of FASTQ text as block gzip "
                   f"({os.path.getsize(work / 'reads.fastq.gz') / 1e6:.1f} MB); `--taxon genomeA` names {G // 2} of the {G} accessions; its output: "
                   f"{out_gz / 1e6:.1f} MB, with `--gz-matches` {out_gz_lz / 1e6:.1f} MB; `_reads.txt` and `_counts.txt` equal to the run without the flags: {same}", "",
-                  f"| command | process wall, {REPS} alternating runs | classification phase (COLORID_TIMING) |", "|---|---|---|"]
+                  f"| command | process wall, {REPS} alternating runs | classification phase (COLORID_TIMING) | its `timing: --taxon:` line, median |",
+                  "|---|---|---|---|"]
         for tag in cmds:
-            lines.append(f"| {label[tag]} | {rng_of(walls[tag], 's')} | {rng_of(cls[tag], 'ms', '{:.0f}')} |")
-        lines += ["", "Kernels of one traced `--taxon` run that the flags add:", "", "| kernel | calls | total ms |", "|---|---|---|"]
-        for name, r in cli_stats.items():
-            if any(k in name for k in ("k_bgzf_deflate", "k_bgzf_gather", "k_fq_filter")):
-                lines.append(f"| `{name.split('(')[0][-60:]}` | {int(r['Calls'])} | {float(r['TotalDurationNs']) / 1e6:.2f} |")
+            ms = sorted(x for x in flt[tag] if x is not None)
+            lines.append(f"| {label[tag]} | {rng_of(walls[tag], 's')} | {rng_of(cls[tag], 'ms', '{:.0f}')} | "
+                         f"{rng_of(flt[tag], 'ms', '{:.0f}')}, {ms[len(ms) // 2] if ms else '—'} |")
+        if parent_bin:
+            lines += ["", f"`.fq.gz` outputs of this commit equal to the parent's byte for byte, both coders: {same_files}"]
+        for tag, stats in traced.items():
+            lines += ["", f"Kernels of the filter step, one traced run of {label[tag]}:", "", "| kernel | calls | total ms |", "|---|---|---|"]
+            rows = [(name, int(r["Calls"]), float(r["TotalDurationNs"]) / 1e6) for name, r in stats.items() if any(k in name for k in FILTER_STEP_KERNELS)]
+            lines += [f"| `{name.split('(')[0][-70:]}` | {calls} | {ms:.2f} |" for name, calls, ms in rows]
+            lines.append(f"| all of them | {sum(r[1] for r in rows)} | {sum(r[2] for r in rows):.2f} |")
         for tag in cmds:
             lines += ["", f"{label[tag]}, first counted run:", "", "```", *first[tag], "```"]
     finally:

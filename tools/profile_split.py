@@ -22,7 +22,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
 BIN = os.path.join(ROOT, "colorid_amd", "bin", "colorid")
-REPS = 3
+REPS = int(os.environ.get("EXP_REPS", 3))
 
 import profile_filter as pf   # noqa: E402
 from profile_merge import kernel_stats, run   # noqa: E402
