@@ -124,6 +124,25 @@ int search_segments_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kme
 }
 
 
+// The segmented perfect search on device-resident inputs and outputs, asynchronous on the ctx stream.  `preset`: set the words to all
+// ones and the flags to 0 first (else they are ANDed into / OR-ed: the second launch over a row that a chunk boundary cut)
+int perfect_segments_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs, uint64_t n_kmers,
+                            uint64_t *d_words, uint8_t *d_missing, bool preset) {
+    cid::PerfectSegmentParams q;
+    int rc = fill_search_params(c, ix, caller_keys(ix, d_kmers, nullptr, nullptr, n_kmers), q.s);
+    if (rc) return rc;
+    q.s.c_pad = 0;   // no histogram: the k-mer image, the hash rows and the tile's segment numbers are all the LDS the kernel needs
+    q.s.wave_bytes = (uint32_t)cid::perfect_segments_wave_bytes(ix->k, ix->n_hash);
+    q.seg_off = d_seg_off; q.n_segs = n_segs; q.and_words = d_words; q.missing = d_missing;
+    if (preset) {
+        HIP_TRY(hipMemsetAsync(d_words, 0xFF, n_segs * (size_t)ix->rs * 8, c->stream));
+        HIP_TRY(hipMemsetAsync(d_missing, 0, n_segs, c->stream));
+    }
+    HIP_TRY(cid::launch_perfect_segments(q, c->stream));
+    return CID_OK;
+}
+
+
 // The coverage search's two launches, device-resident inputs and outputs, asynchronous on the ctx stream.  d_rows: one row of rs u64 per
 // window; the host form gathers a slice chunk by chunk (d_kmers, d_flags and d_rows then start at the chunk's first window) and
 // computes the statistics once over the whole slice.
@@ -454,6 +473,96 @@ int cid_search_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, c
         HIP_TRY(hipMemcpyAsync(hits + s0 * C, d_hits, (s1 - s0) * C * 4, hipMemcpyDeviceToHost, c->stream));
         if (any_row_missing) HIP_TRY(hipMemcpyAsync(any_row_missing + s0, d_miss, s1 - s0, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return CID_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ segmented perfect search (cid_perfect_segments.hip)
+
+int cid_search_perfect_segments_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs,
+                                    uint64_t n_kmers, uint64_t *d_and_words, uint8_t *d_any_row_missing) {
+    int rc = check_segments_index(c, ix);
+    if (rc) return rc;
+    if (n_segs == 0) return CID_OK;
+    if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
+    if (!d_seg_off || !d_and_words || (n_kmers && !d_kmers)) return fail(CID_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    if (!d_any_row_missing) {   // the words of a flagged segment are zero whether or not the caller wants the flags
+        void *d_miss;
+        rc = slot_reserve(c, S_NK, n_segs, &d_miss); if (rc) return rc;
+        d_any_row_missing = (uint8_t *)d_miss;
+    }
+    rc = perfect_segments_launch(c, ix, d_kmers, d_seg_off, n_segs, n_kmers, d_and_words, d_any_row_missing, true);
+    if (rc) return rc;
+    HIP_TRY(cid::launch_perfect_segments_finish(d_and_words, d_any_row_missing, d_seg_off, n_segs, ix->rs, ix->n_colors, c->stream));
+    return CID_OK;
+}
+
+// Host-pointer form, chunked as cid_search_segments is.  The device copy of the words holds a slice of segments (dense_report_bytes); a
+// slice's k-mers go up in chunks of upload_chunk_bytes, each with its own offsets: the slice's segments clipped to the chunk, so a segment
+// cut by a chunk boundary is ANDed by two launches into the same row (preset once per slice) and its flag OR-ed the same way.  The finish
+// kernel runs once per slice, over the slice's true offsets.
+int cid_search_perfect_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint64_t *seg_off, size_t n_segs,
+                                uint32_t *and_words_le, uint8_t *any_row_missing) {
+    int rc = check_segments_index(c, ix);
+    if (rc) return rc;
+    if (n_segs == 0) return CID_OK;
+    if (!seg_off || !and_words_le) return fail(CID_ERR_INVALID, "null argument");
+    if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
+    if (seg_off[0] != 0) return fail(CID_ERR_INVALID, "seg_off[0] must be 0");
+    for (size_t s = 0; s < n_segs; ++s) {
+        if (seg_off[s + 1] < seg_off[s]) return fail(CID_ERR_INVALID, "seg_off decreases at segment %zu", s);
+        if (seg_off[s + 1] - seg_off[s] >= (1ull << 32)) return fail(CID_ERR_INVALID, "segment %zu has 2^32 k-mers or more", s);
+    }
+    const uint64_t n_kmers = seg_off[n_segs];
+    if (n_kmers && !kmers) return fail(CID_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t k = ix->k, rs = ix->rs, w32 = ix->w32;
+    size_t chunk = upload_chunk_kmers(c, k);
+    if (chunk > n_kmers) chunk = n_kmers ? (size_t)n_kmers : 1;
+    size_t per_slice = (size_t)(c->tune.dense_report_bytes / (rs * 8));
+    if (per_slice == 0) per_slice = 1;
+    if (per_slice > n_segs) per_slice = n_segs;
+    void *d_k, *d_words, *d_miss, *d_off;
+    rc = slot_reserve(c, S_KMERS, chunk * k, &d_k); if (rc) return rc;
+    rc = slot_reserve(c, S_REPORT, per_slice * rs * 8, &d_words); if (rc) return rc;
+    rc = slot_reserve(c, S_NK, per_slice, &d_miss); if (rc) return rc;
+    std::vector<uint64_t> loc;   // the slice's true offsets (per_slice + 1 of them, for the finish), then its chunks' clipped offset arrays
+    struct Piece { size_t k0, nk, sa, n_loc, loc0; };
+    std::vector<Piece> pieces;
+    std::vector<uint64_t> h_words;
+    for (size_t s0 = 0; s0 < n_segs; s0 += per_slice) {
+        const size_t s1 = std::min(n_segs, s0 + per_slice), ns = s1 - s0;
+        loc.assign(seg_off + s0, seg_off + s1 + 1);
+        pieces.clear();
+        size_t sa = s0;
+        for (uint64_t k0 = seg_off[s0]; k0 < seg_off[s1]; k0 += chunk) {
+            const uint64_t k1 = std::min<uint64_t>(seg_off[s1], k0 + chunk);
+            while (seg_off[sa + 1] <= k0) ++sa;          // the segment that holds k-mer k0
+            size_t sb = sa;
+            while (seg_off[sb + 1] < k1) ++sb;           // the one that holds k-mer k1 - 1
+            pieces.push_back(Piece{(size_t)k0, (size_t)(k1 - k0), sa, sb - sa + 1, loc.size()});
+            for (size_t s = sa; s <= sb + 1; ++s) loc.push_back(std::min(std::max(seg_off[s], k0), k1) - k0);
+        }
+        HIP_TRY(hipMemsetAsync(d_words, 0xFF, ns * rs * 8, c->stream));
+        HIP_TRY(hipMemsetAsync(d_miss, 0, ns, c->stream));
+        rc = slot_reserve(c, S_SEQOFF, loc.size() * 8, &d_off); if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(d_off, loc.data(), loc.size() * 8, hipMemcpyHostToDevice, c->stream));
+        for (const Piece &pc : pieces) {
+            HIP_TRY(hipMemcpyAsync(d_k, kmers + pc.k0 * k, pc.nk * k, hipMemcpyHostToDevice, c->stream));
+            rc = perfect_segments_launch(c, ix, (const uint8_t *)d_k, (const uint64_t *)d_off + pc.loc0, pc.n_loc, pc.nk,
+                                         (uint64_t *)d_words + (pc.sa - s0) * rs, (uint8_t *)d_miss + (pc.sa - s0), false);
+            if (rc) return rc;
+        }
+        HIP_TRY(cid::launch_perfect_segments_finish((uint64_t *)d_words, (const uint8_t *)d_miss, (const uint64_t *)d_off, ns, (uint32_t)rs,
+                                                    ix->n_colors, c->stream));
+        h_words.resize(ns * rs);
+        HIP_TRY(hipMemcpyAsync(h_words.data(), d_words, ns * rs * 8, hipMemcpyDeviceToHost, c->stream));
+        if (any_row_missing) HIP_TRY(hipMemcpyAsync(any_row_missing + s0, d_miss, ns, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (size_t s = 0; s < ns; ++s)          // u64 words of the padded row -> the BitVec's u32 words
+            for (size_t w = 0; w < w32; ++w)
+                and_words_le[(s0 + s) * w32 + w] = (uint32_t)(h_words[s * rs + w / 2] >> (32 * (w & 1)));
     }
     return CID_OK;
 }

@@ -180,6 +180,21 @@ struct SegmentParams {
     uint8_t *missing;          // [n_segs], or nullptr
 };
 hipError_t launch_search_segments(const SegmentParams &p, hipStream_t stream);
+// Segmented perfect search (cid_perfect_segments.hip): and_words[s * s.rs + w] is ANDed with the rows of segment s's k-mers and missing[s]
+// set (caller presets all ones / 0); k_perfect_segments_finish then zeroes the words of empty and flagged segments and the bits past the
+// last colour.  Of `s` only the index, the k-mers, wave_bytes (perfect_segments_wave_bytes; c_pad = 0) and tiles_per_block are used.
+struct PerfectSegmentParams {
+    SearchParams s;
+    const uint64_t *seg_off;   // [n_segs + 1], non-decreasing, seg_off[0] = 0, seg_off[n_segs] = s.n_kmers
+    uint64_t n_segs;           // < 2^32
+    uint64_t *and_words;       // [n_segs][s.rs]
+    uint8_t *missing;          // [n_segs], never null
+};
+size_t perfect_segments_wave_bytes(uint32_t k, uint32_t n_hash);
+hipError_t launch_perfect_segments(const PerfectSegmentParams &p, hipStream_t stream);
+// seg_off: the segments' TRUE offsets (a host-form launch sees clipped ones); only the differences are read
+hipError_t launch_perfect_segments_finish(uint64_t *and_words, const uint8_t *missing, const uint64_t *seg_off, uint64_t n_segs, uint32_t rs,
+                                          uint32_t n_colors, hipStream_t stream);
 // Coverage search (cid_cover.hip): the segmented search with the windows kept in order.  k_cover_rows writes every window's AND words to
 // rows[window * s.rs + word] (zeros for a window whose flag byte lacks bit 0); k_cover_stats turns the bits of segment s = windows
 // [seg_off[s], seg_off[s+1]) into out[s * n_colors + c], eight u32 per cell (include/colorid_hip.h: cid_cover).  Of `s` only the index,

@@ -9,11 +9,13 @@
 #include <map>
 #include <utility>
 #include <thread>
+#include <unordered_map>
 #include <mutex>
 #include <functional>
 #include <deque>
 #include <condition_variable>
 #include <memory>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -396,6 +398,27 @@ Classification kmer_poll_plus(const uint32_t *colours, const uint32_t *counts, s
                               const std::vector<double> &fp, double fp_correct);
 void read_counts_five_fields(const std::string &reads_file, const std::string &prefix);            // reports.rs:98-120
 
+// ---------------------------------------------------------------- allele table (alleles.cpp)
+// `search -s -m` rows -> the accessions x loci table of a cgMLST scheme (PREFIX.raw.tsv, .detailed.tsv, .report.out; with max_missing >= 0
+// also .clean.tsv and .dropped.txt).  add(): one row, label and accession; add_rows_file(): the rows of a saved stdout, lines of fewer
+// than four TAB-separated fields (banner, warnings) skipped.  A label without '_' makes write() end the run, naming it, before any file
+// is made.  write() says on stderr how many accessions x loci it wrote.
+class AlleleTable {
+  public:
+    void add(const char *label, size_t label_len, const std::string &accession);
+    void add(const std::string &label, const std::string &accession) { add(label.data(), label.size(), accession); }
+    void add_rows_file(const std::string &path);
+    void write(const std::string &prefix, long long max_missing) const;
+  private:
+    struct Cell { std::string allele; size_t n = 0; };   // the first row's allele, the number of rows
+    std::vector<std::string> accessions_;                // in order of their first row
+    std::unordered_map<std::string, size_t> acc_index_;
+    std::vector<std::map<std::string, Cell>> cells_;     // per accession: locus -> cell
+    std::set<std::string> loci_;
+    std::string bad_label_;
+    bool bad_ = false;
+};
+
 // ---------------------------------------------------------------- several GPUs (--gpus N / --devices a,b,..)
 // When set, the drivers below shard every query over the group's ranks (cid_group_*); results are identical.
 void set_group(cid_group *group, const std::vector<cid_index *> &replicas);
@@ -404,7 +427,8 @@ void set_stripes(cid_group *group, const std::vector<cid_index *> &stripes);   /
 // ---------------------------------------------------------------- drivers (same names as the reference modules)
 namespace perfect_search {
 void batch_search(cid_ctx *, const std::vector<std::string> &files, const Bigsi &b);      // perfect_search.rs:6-60
-void batch_search_mf(cid_ctx *, const std::vector<std::string> &files, const Bigsi &b);   // perfect_search.rs:62-120
+// perfect_search.rs:62-120; alleles != nullptr (`--alleles`): every row printed is also added to the table
+void batch_search_mf(cid_ctx *, const std::vector<std::string> &files, const Bigsi &b, AlleleTable *alleles = nullptr);
 }
 namespace batch_search_pe {
 void batch_search(cid_ctx *, const std::vector<std::string> &files1, const std::vector<std::string> &files2, const Bigsi &b,

@@ -8,7 +8,8 @@
 // file `build` writes over the kept lines of the reference list); compare (all-pairs similarity of an index's accessions: which of
 // them are duplicates — the question before `subset -x`); fold (an index at a smaller Bloom size that divides its own, the file
 // `build -s` writes at that size: an over-sized index shrunk, or two indices brought to one size before `merge`); collapse (several
-// accessions of an index as one colour, the rows `build` writes over the members' sequences joined: strain-level index -> taxon-level).
+// accessions of an index as one colour, the rows `build` writes over the members' sequences joined: strain-level index -> taxon-level);
+// alleles (the accessions x loci table of a cgMLST scheme from saved `search -s -m` rows; `search -s -m --alleles` makes it in the run).
 // Minimizer indices (.mxi): build -m [-v M], info, read_id, batch_id.  Not provided (outside the query path): read_filter.
 #include <algorithm>
 #include <cctype>
@@ -621,14 +622,35 @@ int cmd_collapse(int argc, char **argv) {
     return 0;
 }
 
+// --max-missing N (search --alleles, alleles): -1 when absent
+long long max_missing_arg(const Args &a) {
+    if (!a.has("max-missing")) return -1;
+    const std::string &v = a.one("max-missing");
+    char *end = nullptr;
+    const long long n = strtoll(v.c_str(), &end, 10);
+    if (v.empty() || *end || n < 0) die("error: --max-missing expects a number of cells (0 or more), got '%s'", v.c_str());
+    return n;
+}
+
 int cmd_search(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, with_common({{'b', "bigsi", true, false}, {'q', "query", true, true}, {'r', "reverse", true, true},
                                                      {'f', "filter", true, false}, {'p', "p_shared", true, false}, {'g', "gene_search", false, false},
                                                      {'s', "perfect_search", false, false}, {'m', "multi_fasta", false, false},
-                                                     {'Q', "quality", true, false}, {0, "coverage", false, false}}));
+                                                     {'Q', "quality", true, false}, {0, "coverage", false, false},
+                                                     {0, "alleles", true, false}, {0, "max-missing", true, false}}));
     for (const char *req : {"bigsi", "query"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const std::vector<std::string> files1 = a.values.at("query");
+    // -s -m --alleles PREFIX [--max-missing N]: the rows of -s -m, and the accessions x loci table made from them (AlleleTable) once
+    // the last file is done.  What does not go together is refused here, before the GPU context is made
+    if (a.has("alleles")) {
+        if (a.flags.count("gene_search")) die("error: --alleles makes the allele table of a perfect search (-s -m) and does not go with -g");
+        if (!a.flags.count("perfect_search") || !a.flags.count("multi_fasta"))
+            die("error: --alleles needs -s -m (every FASTA record an allele, perfect search)");
+    } else if (a.has("max-missing")) {
+        die("error: --max-missing needs --alleles PREFIX (it chooses which accessions go to PREFIX.clean.tsv)");
+    }
+    const long long max_missing = max_missing_arg(a);
     // -g -m --coverage: where on each record an accession hits (cid_search_cover).  FASTA records on one GPU; everything else is refused
     // here, before the GPU context is made
     const bool coverage = a.flags.count("coverage") != 0;
@@ -679,8 +701,11 @@ int cmd_search(int argc, char **argv) {
             die("error: --coverage serves indices of at most 8192 accessions; %s has %zu", a.one("bigsi").c_str(), b.colors.size());
         batch_search_pe::batch_search_cover(ctx, files1, b, cov);
     } else if (a.flags.count("perfect_search")) {
-        if (a.flags.count("multi_fasta")) perfect_search::batch_search_mf(ctx, files1, b);
-        else perfect_search::batch_search(ctx, files1, b);
+        if (a.flags.count("multi_fasta")) {
+            AlleleTable table;
+            perfect_search::batch_search_mf(ctx, files1, b, a.has("alleles") ? &table : nullptr);
+            if (a.has("alleles")) { fflush(stdout); table.write(a.one("alleles"), max_missing); }
+        } else perfect_search::batch_search(ctx, files1, b);
     } else if (a.flags.count("gene_search") && a.flags.count("multi_fasta") &&
                std::none_of(files1.begin(), files1.end(), [](const std::string &f) { return ends_with(f, "gz"); })) {
         batch_search_pe::batch_search_mf(ctx, files1, b, cov);   // -g -m: every FASTA record is its own query
@@ -692,6 +717,19 @@ int cmd_search(int argc, char **argv) {
     BgzfMemberReader::drop_prefetched();
     release(gpus, b);
     phase_done("release");
+    return 0;
+}
+
+// alleles: -r ROWS -o PREFIX [--max-missing N] — the table writer of `search -s -m --alleles` over rows saved earlier (the stdout of a
+// `search -s -m` run: lines of fewer than four TAB-separated fields, the banner and the warnings, are skipped).  No GPU is opened.
+int cmd_alleles(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {{'r', "rows", true, false}, {'o', "output", true, false}, {0, "max-missing", true, false}});
+    for (const char *req : {"rows", "output"})
+        if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
+    const long long max_missing = max_missing_arg(a);
+    AlleleTable table;
+    table.add_rows_file(a.one("rows"));
+    table.write(a.one("output"), max_missing);
     return 0;
 }
 
@@ -971,17 +1009,22 @@ int main(int argc, char **argv) {
     // src/main.rs:16-20: init_log() prints this banner on stdout before anything else
     printf("\n ************** initializing logger *****************\n\n");
     if (argc < 2) {
-        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare|collapse> [FLAGS]\n");
+        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare|collapse|alleles> [FLAGS]\n");
         return 1;
     }
     const std::string cmd = argv[1];
     if (cmd == "--help" || cmd == "-h" || cmd == "help") {
-        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare|collapse> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
+        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare|collapse|alleles> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
                "SEARCH:\n"
                "    search -b idx.bxi -q panel.fasta -g -m [-p 0.35]               every FASTA record its own gene query\n"
                "    search -b idx.bxi -q panel.fasta -g -m --coverage [-p 0.35]    the same rows, and where on the record the accession hits:\n"
                "                             bases covered / record length, longest covered stretch (bases), stretches, first and last\n"
-               "                             covered base (1-based); one GPU, FASTA queries, at most 8192 accessions\n\n"
+               "                             covered base (1-based); one GPU, FASTA queries, at most 8192 accessions\n"
+               "    search -b idx.bxi -q scheme.fasta -s -m --alleles PREFIX [--max-missing N]   the rows of -s -m (every record an allele\n"
+               "                             named LOCUS_ALLELE), and from them the accessions x loci table: PREFIX.raw.tsv (allele, or NA for\n"
+               "                             several or none), PREFIX.detailed.tsv (MULTI / NOT_CALLED), PREFIX.report.out; --max-missing N:\n"
+               "                             PREFIX.clean.tsv without, PREFIX.dropped.txt with the accessions of more than N NA cells\n"
+               "    alleles -r ROWS -o PREFIX [--max-missing N]   the same tables from the saved stdout of a `search -s -m` run; no GPU\n\n"
                "INDEX MAINTENANCE:\n"
                "    collapse -b OUT -i idx.bxi -g groups.tsv      several accessions as one colour (groups.tsv: accession TAB group per line;\n"
                "                             unlisted accessions stay as they are, a group of one is a rename): rows are the OR of the\n"
@@ -1008,6 +1051,7 @@ int main(int argc, char **argv) {
     if (cmd == "fold") return leave(cmd_fold(argc, argv));
     if (cmd == "compare") return leave(cmd_compare(argc, argv));
     if (cmd == "collapse") return leave(cmd_collapse(argc, argv));
+    if (cmd == "alleles") return leave(cmd_alleles(argc, argv));
     if (cmd == "debug-kmers") return cmd_debug_kmers(argc, argv);
     if (cmd == "debug-records") return cmd_debug_records(argc, argv);
     if (cmd == "batch_id") return leave(cmd_batch_id(argc, argv));

@@ -243,6 +243,24 @@ class Index:
         check(self.lib.cid_search_segments_dev(self.ctx.h, self.h, vp(d_kmers), vp(d_seg_off), n_segs, n_kmers, vp(d_hits),
                                                vp(d_missing) if d_missing else None))
 
+    # ---- segmented perfect search: one AND word row per query
+    def search_perfect_segments(self, kmers, seg_off, want_missing=True):
+        """segment s = k-mers [seg_off[s], seg_off[s+1]) -> (words[n_segs, w32] uint32, missing[n_segs] bool or None): search_perfect per
+        segment; the words of a flagged or empty segment are zero"""
+        kmers = np.ascontiguousarray(kmers, np.uint8).reshape(-1, self.k)
+        seg_off = np.ascontiguousarray(seg_off, np.uint64)
+        n_segs = len(seg_off) - 1
+        words = np.zeros((n_segs, self.w32), np.uint32)
+        missing = np.zeros(n_segs, np.uint8) if want_missing else None
+        check(self.lib.cid_search_perfect_segments(self.ctx.h, self.h, _p(kmers), _p(seg_off), n_segs, _p(words), _p(missing)))
+        return words, (missing.astype(bool) if want_missing else None)
+
+    def search_perfect_segments_dev(self, d_kmers, d_seg_off, n_segs, n_kmers, d_and_words, d_missing=None):
+        """d_and_words: n_segs x row_stride_words u64 in device memory"""
+        check(self.lib.cid_search_perfect_segments_dev(self.ctx.h, self.h, vp(d_kmers) if d_kmers else None, vp(d_seg_off) if d_seg_off else None,
+                                                       n_segs, n_kmers, vp(d_and_words) if d_and_words else None,
+                                                       vp(d_missing) if d_missing else None))
+
     # ---- coverage search: where on each query a colour hits
     def search_cover(self, kmers, seg_off, flags=None):
         """kmers: one canonical k-mer per window, in sequence order; segment s = windows [seg_off[s], seg_off[s+1]); flags: one byte per

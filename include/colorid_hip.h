@@ -222,6 +222,24 @@ int cid_search_segments(cid_ctx *, const cid_index *, const uint8_t *kmers, cons
 int cid_search_segments_dev(cid_ctx *, const cid_index *, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs,
                             uint64_t n_kmers, uint32_t *d_hits, uint8_t *d_any_row_missing);
 
+/* ---- Segmented perfect search (EXTENDED): cid_search_perfect for many queries in one call — every record of a scheme's multi-FASTA an
+ *      allele (`search -s -m`).  Segments as for cid_search_segments.  Per segment s: and_words[s] = the AND, over all of the segment's
+ *      k-mers and their num_hash rows, of the rows' colour bits — bit c set iff colour c holds every k-mer of s (src/perfect_search.rs:
+ *      83-110 per segment) — and any_row_missing[s] = 1 iff some k-mer of s has an all-zero row.  As cid_search_perfect does, the words of
+ *      a flagged segment are zero; so are the words of an empty segment and the bits at and above n_colors.  n_segs == 0 is CID_OK and
+ *      touches nothing.  The answer per segment is n_colors bits where cid_search_segments returns n_colors counters.
+ *      Host form: and_words_le holds n_segs rows of ceil(n_colors / 32) u32 words (bit c = word c / 32, bit c % 32: a BitVec<u32>'s
+ *      storage, as cid_search_perfect returns it); any_row_missing may be NULL.  It uploads in chunks of "upload_chunk_bytes" and keeps at
+ *      most "dense_report_bytes" of the words on the device at a time.
+ *      _dev: everything in device memory, d_kmers 16-byte aligned, n_kmers = d_seg_off[n_segs]; d_and_words holds n_segs rows of
+ *      row_stride_words u64 words (cid_index_row_stride_words; the words past the colours are zero); d_any_row_missing may be NULL.
+ *      Asynchronous on the ctx stream; presets its outputs: nothing is assumed about their contents.
+ *      Errors as cid_search_segments. ---- */
+int cid_search_perfect_segments(cid_ctx *, const cid_index *, const uint8_t *kmers, const uint64_t *seg_off, size_t n_segs,
+                                uint32_t *and_words_le, uint8_t *any_row_missing);
+int cid_search_perfect_segments_dev(cid_ctx *, const cid_index *, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs,
+                                    uint64_t n_kmers, uint64_t *d_and_words, uint8_t *d_any_row_missing);
+
 /* ---- Coverage search (EXTENDED): WHERE on each query an accession hits (`search -g -m --coverage`).  The segmented search with the
  *      windows kept in sequence order.  A segment is one record: L windows numbered 0 .. L-1, window w covers bases [w, w + k_size).
  *      `kmers` holds one canonical upper-case k-mer per window, in order (k_size ASCII bytes each), segment s = windows
