@@ -65,6 +65,8 @@ SIGNATURES = {
     "cid_search_segments_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t, C.c_uint64, vp, vp]),
     "cid_search_perfect_segments": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
     "cid_search_perfect_segments_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t, C.c_uint64, vp, vp]),
+    "cid_search_nearest_segments": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp]),
+    "cid_search_nearest_segments_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t, C.c_uint64, vp, C.c_size_t, vp]),
     "cid_search_cover": (C.c_int, [vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "cid_search_cover_dev": (C.c_int, [vp, vp, vp, vp, vp, C.c_size_t, C.c_uint64, vp]),
     "cid_search_count_codes_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp]),

@@ -567,6 +567,102 @@ int cid_search_perfect_segments(cid_ctx *c, const cid_index *ix, const uint8_t *
     return CID_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ nearest segment per group (cid_nearest.hip)
+
+int cid_search_nearest_segments_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs,
+                                    uint64_t n_kmers, const uint64_t *d_group_off, size_t n_groups, cid_nearest *d_out) {
+    int rc = check_segments_index(c, ix);
+    if (rc) return rc;
+    if (n_groups == 0 || n_segs == 0) return CID_OK;
+    if (n_segs >= (1ull << 32) || n_groups >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or groups, or more");
+    if (!d_seg_off || !d_group_off || !d_out || (n_kmers && !d_kmers)) return fail(CID_ERR_INVALID, "null argument");
+    if (!aligned16(d_out)) return fail(CID_ERR_INVALID, "d_out must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(c->device));
+    void *d_hits;
+    rc = slot_reserve(c, S_REPORT, n_segs * (size_t)ix->n_colors * 4, &d_hits); if (rc) return rc;
+    rc = search_segments_launch(c, ix, d_kmers, d_seg_off, n_segs, n_kmers, (uint32_t *)d_hits, nullptr, true); if (rc) return rc;
+    HIP_TRY(cid::launch_nearest_preset(d_out, (uint64_t)n_groups * ix->n_colors, c->stream));
+    cid::NearestParams q{(const uint32_t *)d_hits, d_seg_off, d_group_off, n_groups, 0, 0, n_segs, ix->n_colors, reinterpret_cast<uint4 *>(d_out)};
+    HIP_TRY(cid::launch_nearest_groups(q, c->stream));
+    return CID_OK;
+}
+
+// Host-pointer form.  The cells of all groups stay on the device for the whole call, preset once.  The segments go through in slices whose
+// counters fit dense_report_bytes, a slice's k-mers in chunks of upload_chunk_bytes with clipped offsets, exactly as cid_search_segments
+// does; one k_nearest_groups launch ends the slice and merges the slice's part of every group it touches into the group's cells.  A cut
+// may fall inside a group: the earlier slice holds the lower segment numbers, and the order is total, so the result is that of one pass.
+int cid_search_nearest_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint64_t *seg_off, size_t n_segs,
+                                const uint64_t *group_off, size_t n_groups, cid_nearest *out) {
+    int rc = check_segments_index(c, ix);
+    if (rc) return rc;
+    if (n_groups == 0 || n_segs == 0) return CID_OK;
+    if (!seg_off || !group_off || !out) return fail(CID_ERR_INVALID, "null argument");
+    if (n_segs >= (1ull << 32) || n_groups >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or groups, or more");
+    if (seg_off[0] != 0) return fail(CID_ERR_INVALID, "seg_off[0] must be 0");
+    for (size_t s = 0; s < n_segs; ++s) {
+        if (seg_off[s + 1] < seg_off[s]) return fail(CID_ERR_INVALID, "seg_off decreases at segment %zu", s);
+        if (seg_off[s + 1] - seg_off[s] >= (1ull << 32)) return fail(CID_ERR_INVALID, "segment %zu has 2^32 k-mers or more", s);
+    }
+    if (group_off[0] != 0) return fail(CID_ERR_INVALID, "group_off[0] must be 0");
+    for (size_t g = 0; g < n_groups; ++g)
+        if (group_off[g + 1] < group_off[g]) return fail(CID_ERR_INVALID, "group_off decreases at group %zu", g);
+    if (group_off[n_groups] != n_segs)
+        return fail(CID_ERR_INVALID, "group_off ends at %llu, not at the %zu segments", (unsigned long long)group_off[n_groups], n_segs);
+    const uint64_t n_kmers = seg_off[n_segs];
+    if (n_kmers && !kmers) return fail(CID_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t C = ix->n_colors, k = ix->k;
+    size_t chunk = upload_chunk_kmers(c, k);
+    if (chunk > n_kmers) chunk = n_kmers ? (size_t)n_kmers : 1;
+    size_t per_slice = (size_t)(c->tune.dense_report_bytes / (C * 4));
+    if (per_slice == 0) per_slice = 1;
+    if (per_slice > n_segs) per_slice = n_segs;
+    void *d_k, *d_hits, *d_off, *d_groups, *d_cells;
+    rc = slot_reserve(c, S_KMERS, chunk * k, &d_k); if (rc) return rc;
+    rc = slot_reserve(c, S_REPORT, per_slice * C * 4, &d_hits); if (rc) return rc;
+    rc = slot_reserve(c, S_ROWIDS, (n_groups + 1) * 8, &d_groups); if (rc) return rc;
+    rc = slot_reserve(c, S_WORDS, n_groups * C * sizeof(cid_nearest), &d_cells); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(d_groups, group_off, (n_groups + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(cid::launch_nearest_preset(d_cells, (uint64_t)n_groups * C, c->stream));
+    std::vector<uint64_t> loc;   // the slice's true offsets (its segments + 1 of them, for the lengths), then its chunks' clipped offset arrays
+    struct Piece { size_t k0, nk, sa, n_loc, loc0; };
+    std::vector<Piece> pieces;
+    size_t ga = 0;               // the first group that reaches into the slice
+    for (size_t s0 = 0; s0 < n_segs; s0 += per_slice) {
+        const size_t s1 = std::min(n_segs, s0 + per_slice), ns = s1 - s0;
+        loc.assign(seg_off + s0, seg_off + s1 + 1);
+        pieces.clear();
+        size_t sa = s0;
+        for (uint64_t k0 = seg_off[s0]; k0 < seg_off[s1]; k0 += chunk) {
+            const uint64_t k1 = std::min<uint64_t>(seg_off[s1], k0 + chunk);
+            while (seg_off[sa + 1] <= k0) ++sa;          // the segment that holds k-mer k0
+            size_t sb = sa;
+            while (seg_off[sb + 1] < k1) ++sb;           // the one that holds k-mer k1 - 1
+            pieces.push_back(Piece{(size_t)k0, (size_t)(k1 - k0), sa, sb - sa + 1, loc.size()});
+            for (size_t s = sa; s <= sb + 1; ++s) loc.push_back(std::min(std::max(seg_off[s], k0), k1) - k0);
+        }
+        HIP_TRY(hipMemsetAsync(d_hits, 0, ns * C * 4, c->stream));
+        rc = slot_reserve(c, S_SEQOFF, loc.size() * 8, &d_off); if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(d_off, loc.data(), loc.size() * 8, hipMemcpyHostToDevice, c->stream));
+        for (const Piece &pc : pieces) {
+            HIP_TRY(hipMemcpyAsync(d_k, kmers + pc.k0 * k, pc.nk * k, hipMemcpyHostToDevice, c->stream));
+            rc = search_segments_launch(c, ix, (const uint8_t *)d_k, (const uint64_t *)d_off + pc.loc0, pc.n_loc, pc.nk,
+                                        (uint32_t *)d_hits + (pc.sa - s0) * C, nullptr, false);
+            if (rc) return rc;
+        }
+        while (group_off[ga + 1] <= s0) ++ga;            // (group_off ends at n_segs > s0)
+        size_t gb = ga;                                  // the last group that starts before the slice's end
+        while (gb + 1 < n_groups && group_off[gb + 1] < s1) ++gb;
+        cid::NearestParams q{(const uint32_t *)d_hits, (const uint64_t *)d_off, (const uint64_t *)d_groups + ga, gb - ga + 1, ga, s0, s1, (uint32_t)C,
+                             reinterpret_cast<uint4 *>(d_cells)};
+        HIP_TRY(cid::launch_nearest_groups(q, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));        // loc is rewritten for the next slice
+    }
+    HIP_TRY(hipMemcpyAsync(out, d_cells, n_groups * C * sizeof(cid_nearest), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return CID_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ coverage search (cid_cover.hip)
 
 int cid_search_cover_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_seg_off, const uint8_t *d_flags, size_t n_segs,

@@ -195,6 +195,22 @@ hipError_t launch_perfect_segments(const PerfectSegmentParams &p, hipStream_t st
 // seg_off: the segments' TRUE offsets (a host-form launch sees clipped ones); only the differences are read
 hipError_t launch_perfect_segments_finish(uint64_t *and_words, const uint8_t *missing, const uint64_t *seg_off, uint64_t n_segs, uint32_t rs,
                                           uint32_t n_colors, hipStream_t stream);
+// Nearest-allele reduction (cid_nearest.hip): k_search_segments' counters of the segments [s_lo, s_hi) -> per (group, colour) the segment
+// with the largest share, MERGED into out (caller presets: launch_nearest_preset).  Group g of the launch = segments
+// [group_off[g], group_off[g + 1]) clipped to [s_lo, s_hi); segment numbers are those group_off speaks of.
+constexpr int kNearestGroups = 4;   // consecutive groups per workgroup: one per wave in the final merge
+struct NearestParams {
+    const uint32_t *hits;        // row of segment s at hits + (s - s_lo) * n_colors
+    const uint64_t *seg_off;     // [s_hi - s_lo + 1]: entry s - s_lo; only the differences are read
+    const uint64_t *group_off;   // [n_groups + 1], the launch's first group first
+    uint64_t n_groups;           // of this launch; < 2^33
+    uint64_t g_base;             // the launch's first group's row of `out`
+    uint64_t s_lo, s_hi;
+    uint32_t n_colors;
+    uint4 *out;                  // [.][n_colors] cells {seg, kmers_hit, n_kmers, n_perfect}
+};
+hipError_t launch_nearest_groups(const NearestParams &p, hipStream_t stream);
+hipError_t launch_nearest_preset(void *out, uint64_t n_cells, hipStream_t stream);
 // Coverage search (cid_cover.hip): the segmented search with the windows kept in order.  k_cover_rows writes every window's AND words to
 // rows[window * s.rs + word] (zeros for a window whose flag byte lacks bit 0); k_cover_stats turns the bits of segment s = windows
 // [seg_off[s], seg_off[s+1]) into out[s * n_colors + c], eight u32 per cell (include/colorid_hip.h: cid_cover).  Of `s` only the index,

@@ -113,4 +113,53 @@ void AlleleTable::write(const std::string &prefix, long long max_missing) const 
             det_path.c_str(), rep_path.c_str());
 }
 
+// ---------------------------------------------------------------- PREFIX.nearest.tsv (`search -s -m --alleles PREFIX --nearest`)
+
+void NearestTable::add_record(const std::string &label) {
+    if (!bad_ && label.find('_') == std::string::npos) { bad_label_ = label; bad_ = true; }
+    labels_.push_back(label);
+}
+
+// `later` holds records after the cell's: it wins only with a strictly greater share, hits_a * len_b against hits_b * len_a in 64 bits
+void NearestTable::merge(cid_nearest &cell, const cid_nearest &later) {
+    const uint32_t n_perfect = cell.n_perfect + later.n_perfect;
+    if (later.seg != CID_NEAREST_NONE &&
+        (cell.seg == CID_NEAREST_NONE || (uint64_t)later.kmers_hit * cell.n_kmers > (uint64_t)cell.kmers_hit * later.n_kmers))
+        cell = later;
+    cell.n_perfect = n_perfect;
+}
+
+void NearestTable::merge_group(const std::string &locus, const cid_nearest *cells, size_t record_base) {
+    auto it = loci_.find(locus);
+    if (it == loci_.end()) it = loci_.emplace(locus, std::vector<cid_nearest>(n_colors_, cid_nearest{CID_NEAREST_NONE, 0, 0, 0})).first;
+    for (size_t c = 0; c < n_colors_; ++c) {
+        cid_nearest in = cells[c];
+        if (in.seg != CID_NEAREST_NONE) in.seg += (uint32_t)record_base;
+        merge(it->second[c], in);
+    }
+}
+
+void NearestTable::write(const std::string &prefix, const std::vector<std::string> &accessions, double min_share) const {
+    if (bad_)
+        die("alleles: the label '%s' has no '_': a scheme's records are named LOCUS_ALLELE; no nearest-allele file is written", bad_label_.c_str());
+    const std::string path = prefix + ".nearest.tsv";
+    FILE *f = table_out(path);
+    fputs("accession\tlocus\tallele\tkmers_hit\tkmers\tshare\n", f);
+    size_t n = 0;
+    for (size_t c = 0; c < n_colors_; ++c)
+        for (const auto &lc : loci_) {   // std::string orders by unsigned bytes
+            const cid_nearest &cell = lc.second[c];
+            if (cell.n_perfect || cell.seg == CID_NEAREST_NONE) continue;
+            const double share = (double)cell.kmers_hit / (double)cell.n_kmers;
+            if (!(share >= min_share)) continue;
+            const std::string &label = labels_[cell.seg];
+            const size_t u1 = label.find('_'), u2 = label.find('_', u1 + 1);
+            fprintf(f, "%s\t%s\t%s\t%u\t%u\t%.3f\n", accessions[c].c_str(), lc.first.c_str(),
+                    label.substr(u1 + 1, u2 == std::string::npos ? std::string::npos : u2 - u1 - 1).c_str(), cell.kmers_hit, cell.n_kmers, share);
+            ++n;
+        }
+    table_close(f, path);
+    fprintf(stderr, "alleles: %zu nearest-allele calls (share >= %g) written to %s\n", n, min_share, path.c_str());
+}
+
 }  // namespace colorid

@@ -419,6 +419,31 @@ class AlleleTable {
     bool bad_ = false;
 };
 
+// `search -s -m --alleles PREFIX --nearest`: per (locus, accession) the record of the locus with the largest share of its k-mers in the
+// accession, and how many records the accession holds completely (cid_search_nearest_segments' cells, one group per run of records of a
+// locus).  add_record(): every record of the scheme, in input order — its number is what a cell's `seg` is turned into.  merge_group():
+// the cells of one group (n_colors of them, seg = the record's number in the batch + record_base) into the locus; a locus that recurs —
+// a run cut by a batch boundary, a later run, another query file — is merged by merge(), the library's total order: the greater share
+// wins, compared exactly, ties to the earlier record; n_perfect adds up.  write(): PREFIX.nearest.tsv, one line per accession (colour
+// order) and locus (byte order) without a perfect record whose best share is at least min_share; a label without '_' ends the run as
+// AlleleTable::write does.
+class NearestTable {
+  public:
+    explicit NearestTable(size_t n_colors) : n_colors_(n_colors) {}
+    static std::string locus_of(const std::string &label) { return label.substr(0, label.find('_')); }
+    size_t n_records() const { return labels_.size(); }
+    void add_record(const std::string &label);
+    void merge_group(const std::string &locus, const cid_nearest *cells, size_t record_base);
+    static void merge(cid_nearest &cell, const cid_nearest &later);
+    void write(const std::string &prefix, const std::vector<std::string> &accessions, double min_share) const;
+  private:
+    size_t n_colors_;
+    std::vector<std::string> labels_;                          // every record's label; a cell's seg is an index into it
+    std::map<std::string, std::vector<cid_nearest>> loci_;     // locus -> one cell per accession
+    std::string bad_label_;
+    bool bad_ = false;
+};
+
 // ---------------------------------------------------------------- several GPUs (--gpus N / --devices a,b,..)
 // When set, the drivers below shard every query over the group's ranks (cid_group_*); results are identical.
 void set_group(cid_group *group, const std::vector<cid_index *> &replicas);
@@ -427,8 +452,9 @@ void set_stripes(cid_group *group, const std::vector<cid_index *> &stripes);   /
 // ---------------------------------------------------------------- drivers (same names as the reference modules)
 namespace perfect_search {
 void batch_search(cid_ctx *, const std::vector<std::string> &files, const Bigsi &b);      // perfect_search.rs:6-60
-// perfect_search.rs:62-120; alleles != nullptr (`--alleles`): every row printed is also added to the table
-void batch_search_mf(cid_ctx *, const std::vector<std::string> &files, const Bigsi &b, AlleleTable *alleles = nullptr);
+// perfect_search.rs:62-120; alleles != nullptr (`--alleles`): every row printed is also added to the table; nearest != nullptr
+// (`--nearest`, the batched route only): every batch goes through cid_search_nearest_segments as well
+void batch_search_mf(cid_ctx *, const std::vector<std::string> &files, const Bigsi &b, AlleleTable *alleles = nullptr, NearestTable *nearest = nullptr);
 }
 namespace batch_search_pe {
 void batch_search(cid_ctx *, const std::vector<std::string> &files1, const std::vector<std::string> &files2, const Bigsi &b,

@@ -360,6 +360,28 @@ struct PerfectBatch {
     std::vector<Record> records;
     double ms_calls = 0;   // COLORID_TIMING: time inside the library
     size_t n_calls = 0;
+    // --nearest: the batch goes through cid_search_nearest_segments as well, on the same keys and offsets (its k-mers go up a second time).
+    // A group is a maximal run of consecutive records of one locus; a record without k-mers is an empty segment in its place.  A locus
+    // enters the table with its first group that has a k-mer; what the table holds of it already is merged with (NearestTable::merge).
+    NearestTable *nearest = nullptr;
+    double ms_nearest = 0;
+    void nearest_call(cid_ctx *ctx, const Bigsi &b) {
+        const size_t n = records.size(), C = b.colors.size(), base = nearest->n_records();
+        std::vector<uint64_t> group_off;
+        std::vector<std::string> loci;
+        for (size_t i = 0; i < n; ++i) {
+            nearest->add_record(records[i].label);
+            std::string locus = NearestTable::locus_of(records[i].label);
+            if (loci.empty() || locus != loci.back()) { group_off.push_back(i); loci.push_back(std::move(locus)); }
+        }
+        group_off.push_back(n);
+        std::vector<cid_nearest> cells(loci.size() * C);
+        const auto t0 = Clock::now();
+        CID_TRY(cid_search_nearest_segments(ctx, b.index, keys.data(), off.data(), n, group_off.data(), loci.size(), cells.data()));
+        ms_nearest += ms_since(t0);
+        for (size_t g = 0; g < loci.size(); ++g)
+            if (off[group_off[g + 1]] > off[group_off[g]]) nearest->merge_group(loci[g], cells.data() + g * C, base);
+    }
     void push(const std::string &label, const KmerMap *km) {
         records.push_back(Record{label, km == nullptr});
         if (km) keys.insert(keys.end(), km->keys(), km->keys() + km->size() * km->k());
@@ -378,16 +400,20 @@ struct PerfectBatch {
         ms_calls += ms_since(t0);
         ++n_calls;
         for (size_t i = 0; i < n; ++i) emit(records[i], (size_t)(off[i + 1] - off[i]), words.data() + i * w32, (int)missing[i]);
+        if (nearest) nearest_call(ctx, b);
         keys.clear();
         off.assign(1, 0);
         records.clear();
     }
 };
 
-void perfect_search::batch_search_mf(cid_ctx *ctx, const std::vector<std::string> &files, const Bigsi &b, AlleleTable *alleles) {
+void perfect_search::batch_search_mf(cid_ctx *ctx, const std::vector<std::string> &files, const Bigsi &b, AlleleTable *alleles, NearestTable *nearest) {
     const bool batched = segments_route(b);
     const size_t w32 = (b.colors.size() + 31) / 32;
     PerfectBatch batch;
+    batch.nearest = nearest;
+    // COLORID_MF_BATCH_RECORDS=N: a batch of at most N records (tests: a batch boundary inside a locus); unset: PerfectBatch::full alone
+    const size_t batch_records = cli_env("COLORID_MF_BATCH_RECORDS") ? (size_t)strtoull(cli_env("COLORID_MF_BATCH_RECORDS"), nullptr, 10) : 0;
     auto warn = [](const std::string &label) {
         printf("Warning! no kmers in query '%s'; maybe your kmer length is larger than your query length?\n", label.c_str());
     };
@@ -408,7 +434,7 @@ void perfect_search::batch_search_mf(cid_ctx *ctx, const std::vector<std::string
             const bool some = kmerize_string(seqs[i], km);
             if (batched && (!some || km.size())) {
                 batch.push(labels[i], some ? &km : nullptr);
-                if (batch.full(w32)) batch.flush(ctx, b, emit);
+                if (batch.full(w32) || (batch_records && batch.records.size() >= batch_records)) batch.flush(ctx, b, emit);
                 continue;
             }
             batch.flush(ctx, b, emit);   // (a record of k bases or more without a k-mer: the one-record call refuses it, as it always has)
@@ -420,6 +446,8 @@ void perfect_search::batch_search_mf(cid_ctx *ctx, const std::vector<std::string
     batch.flush(ctx, b, emit);
     if (g_timing && batched)
         fprintf(stderr, "timing: -s -m batched: %zu cid_search_perfect_segments calls %.0f ms (upload, kernels, read-back)\n", batch.n_calls, batch.ms_calls);
+    if (g_timing && batched && nearest)
+        fprintf(stderr, "timing: -s -m --nearest: %zu cid_search_nearest_segments calls %.0f ms (upload, kernels, read-back)\n", batch.n_calls, batch.ms_nearest);
 }
 
 // ---------------------------------------------------------------------------------------------- batch_search_pe.rs

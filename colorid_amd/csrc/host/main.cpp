@@ -637,7 +637,8 @@ int cmd_search(int argc, char **argv) {
                                                      {'f', "filter", true, false}, {'p', "p_shared", true, false}, {'g', "gene_search", false, false},
                                                      {'s', "perfect_search", false, false}, {'m', "multi_fasta", false, false},
                                                      {'Q', "quality", true, false}, {0, "coverage", false, false},
-                                                     {0, "alleles", true, false}, {0, "max-missing", true, false}}));
+                                                     {0, "alleles", true, false}, {0, "max-missing", true, false},
+                                                     {0, "nearest", false, false}}));
     for (const char *req : {"bigsi", "query"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const std::vector<std::string> files1 = a.values.at("query");
@@ -651,6 +652,15 @@ int cmd_search(int argc, char **argv) {
         die("error: --max-missing needs --alleles PREFIX (it chooses which accessions go to PREFIX.clean.tsv)");
     }
     const long long max_missing = max_missing_arg(a);
+    // -s -m --alleles PREFIX --nearest [-p MIN_SHARE]: for the cells the tables cannot call, the closest allele (PREFIX.nearest.tsv, from
+    // cid_search_nearest_segments on every batch).  The per-record route of groups and colour stripes has no counters: refused here,
+    // before the GPU context is made
+    const bool nearest = a.flags.count("nearest") != 0;
+    if (nearest) {
+        if (!a.has("alleles")) die("error: --nearest needs -s -m --alleles PREFIX (it writes PREFIX.nearest.tsv beside the allele tables)");
+        if (a.has("gpus") || a.has("devices") || a.has("placement") || cli_env("COLORID_REDUCE"))
+            die("error: --nearest runs on one GPU: it does not go with --gpus, --devices, --placement or COLORID_REDUCE");
+    }
     // -g -m --coverage: where on each record an accession hits (cid_search_cover).  FASTA records on one GPU; everything else is refused
     // here, before the GPU context is made
     const bool coverage = a.flags.count("coverage") != 0;
@@ -702,9 +712,14 @@ int cmd_search(int argc, char **argv) {
         batch_search_pe::batch_search_cover(ctx, files1, b, cov);
     } else if (a.flags.count("perfect_search")) {
         if (a.flags.count("multi_fasta")) {
+            if (nearest && b.colors.size() > 8192)
+                die("error: --nearest serves indices of at most 8192 accessions; %s has %zu", a.one("bigsi").c_str(), b.colors.size());
             AlleleTable table;
-            perfect_search::batch_search_mf(ctx, files1, b, a.has("alleles") ? &table : nullptr);
+            const std::unique_ptr<NearestTable> near(nearest ? new NearestTable(b.colors.size()) : nullptr);
+            perfect_search::batch_search_mf(ctx, files1, b, a.has("alleles") ? &table : nullptr, near.get());
             if (a.has("alleles")) { fflush(stdout); table.write(a.one("alleles"), max_missing); }
+            const double min_share = cov;   // -p: for --nearest the least share of a record's k-mers that is worth a line
+            if (near) near->write(a.one("alleles"), b.colors, min_share);
         } else perfect_search::batch_search(ctx, files1, b);
     } else if (a.flags.count("gene_search") && a.flags.count("multi_fasta") &&
                std::none_of(files1.begin(), files1.end(), [](const std::string &f) { return ends_with(f, "gz"); })) {
@@ -1024,6 +1039,10 @@ int main(int argc, char **argv) {
                "                             named LOCUS_ALLELE), and from them the accessions x loci table: PREFIX.raw.tsv (allele, or NA for\n"
                "                             several or none), PREFIX.detailed.tsv (MULTI / NOT_CALLED), PREFIX.report.out; --max-missing N:\n"
                "                             PREFIX.clean.tsv without, PREFIX.dropped.txt with the accessions of more than N NA cells\n"
+               "    search -b idx.bxi -q scheme.fasta -s -m --alleles PREFIX --nearest [-p 0.35]   also PREFIX.nearest.tsv: for every accession\n"
+               "                             and locus without a perfect allele, the known allele that shares most of its k-mers with the\n"
+               "                             accession (share >= -p): a novel allele shares > 0.9, an absent locus nothing; one GPU, at most\n"
+               "                             8192 accessions\n"
                "    alleles -r ROWS -o PREFIX [--max-missing N]   the same tables from the saved stdout of a `search -s -m` run; no GPU\n\n"
                "INDEX MAINTENANCE:\n"
                "    collapse -b OUT -i idx.bxi -g groups.tsv      several accessions as one colour (groups.tsv: accession TAB group per line;\n"

@@ -12,6 +12,9 @@ COVER_NONE = 0xFFFFFFFF         # first_window / last_window of a (segment, colo
 # one cell of cid_search_cover's output (include/colorid_hip.h: cid_cover)
 COVER_DTYPE = np.dtype([(f, "<u4") for f in ("kmers_hit", "windows_hit", "bases_covered", "n_runs", "longest_run", "first_window", "last_window",
                                              "reserved")])
+NEAREST_NONE = 0xFFFFFFFF       # seg of a (group, colour) that no segment of the group hits
+# one cell of cid_search_nearest_segments' output (include/colorid_hip.h: cid_nearest)
+NEAREST_DTYPE = np.dtype([(f, "<u4") for f in ("seg", "kmers_hit", "n_kmers", "n_perfect")])
 
 
 def _p(a):
@@ -260,6 +263,26 @@ class Index:
         check(self.lib.cid_search_perfect_segments_dev(self.ctx.h, self.h, vp(d_kmers) if d_kmers else None, vp(d_seg_off) if d_seg_off else None,
                                                        n_segs, n_kmers, vp(d_and_words) if d_and_words else None,
                                                        vp(d_missing) if d_missing else None))
+
+    # ---- nearest segment per group: the closest allele of every locus
+    def search_nearest_segments(self, kmers, seg_off, group_off):
+        """segments as for search_segments; group g = segments [group_off[g], group_off[g+1]) -> structured array [n_groups, n_colors] of
+        NEAREST_DTYPE: the segment of the group with the largest share kmers_hit / n_kmers (exact; ties to the lowest segment), seg ==
+        NEAREST_NONE where no segment of the group hits the colour; n_perfect = the group's segments the colour holds completely"""
+        kmers = np.ascontiguousarray(kmers, np.uint8).reshape(-1, self.k)
+        seg_off = np.ascontiguousarray(seg_off, np.uint64)
+        group_off = np.ascontiguousarray(group_off, np.uint64)
+        n_segs, n_groups = len(seg_off) - 1, len(group_off) - 1
+        out = np.zeros((n_groups, self.n_colors), NEAREST_DTYPE)
+        out["seg"] = NEAREST_NONE
+        check(self.lib.cid_search_nearest_segments(self.ctx.h, self.h, _p(kmers), _p(seg_off), n_segs, _p(group_off), n_groups, _p(out)))
+        return out
+
+    def search_nearest_segments_dev(self, d_kmers, d_seg_off, n_segs, n_kmers, d_group_off, n_groups, d_out):
+        """d_out: n_groups x n_colors cells of 16 bytes in device memory, 16-byte aligned"""
+        check(self.lib.cid_search_nearest_segments_dev(self.ctx.h, self.h, vp(d_kmers) if d_kmers else None, vp(d_seg_off) if d_seg_off else None,
+                                                       n_segs, n_kmers, vp(d_group_off) if d_group_off else None, n_groups,
+                                                       vp(d_out) if d_out else None))
 
     # ---- coverage search: where on each query a colour hits
     def search_cover(self, kmers, seg_off, flags=None):

@@ -240,6 +240,36 @@ int cid_search_perfect_segments(cid_ctx *, const cid_index *, const uint8_t *kme
 int cid_search_perfect_segments_dev(cid_ctx *, const cid_index *, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs,
                                     uint64_t n_kmers, uint64_t *d_and_words, uint8_t *d_any_row_missing);
 
+/* ---- Nearest segment per group (EXTENDED): which allele of a locus an accession is closest to (`search -s -m --alleles --nearest`).
+ *      Segments as for cid_search_segments.  group_off[n_groups + 1] cuts the SEGMENTS into consecutive groups — one group = the alleles
+ *      of one locus: group g = segments [group_off[g], group_off[g+1]); ascending, group_off[0] = 0, group_off[n_groups] = n_segs; an
+ *      empty group is allowed.
+ *      Let hits[s][c] be cid_search_segments' counter and len_s the segment's k-mer count.  For group g and colour c the candidates are
+ *      the segments s of g with len_s > 0 and hits[s][c] > 0.  They are ordered by share hits / len, descending; shares are compared
+ *      exactly, as hits_a * len_b against hits_b * len_a in 64-bit integers (both factors are below 2^32; there is no float anywhere);
+ *      ties go to the lowest s.  That is a total order: the answer does not depend on how the reduction is split.
+ *      out[g * n_colors + c] = {seg = the best s, kmers_hit = hits[best][c], n_kmers = len_best, n_perfect}, where n_perfect is the
+ *      number of segments of g with len_s > 0 && hits[s][c] == len_s.  With no candidate the cell is {CID_NEAREST_NONE, 0, 0, 0}.  If a
+ *      perfect segment exists the best share is 1 and seg is the first perfect one.  n_groups == 0 or n_segs == 0 is CID_OK and touches
+ *      nothing.
+ *      Errors as cid_search_segments (a null argument, a bad seg_off; a minimizer index or more than 8192 colours: CID_ERR_UNSUPPORTED),
+ *      and CID_ERR_INVALID for group_off[0] != 0, a descending group_off or a last element != n_segs (host form: checked before anything
+ *      is launched).
+ *      Host form: the n_segs * n_colors counters never leave the device.  The call goes through in slices of segments whose counters fit
+ *      "dense_report_bytes", a slice's k-mers in chunks of "upload_chunk_bytes"; a cut may fall anywhere, also inside a group.  Only the
+ *      n_groups * n_colors * 16 bytes of `out` come back.
+ *      _dev: everything in device memory, d_kmers and d_out 16-byte aligned, n_kmers = d_seg_off[n_segs]; asynchronous on the ctx stream;
+ *      presets d_out itself; 4 * n_segs * n_colors bytes of ctx scratch.  Every index read from d_group_off is bounded to [0, n_segs]
+ *      before it is used: a wrong d_group_off gives wrong cells, never an access outside the arrays. ---- */
+#define CID_NEAREST_NONE 0xFFFFFFFFu
+typedef struct cid_nearest {
+    uint32_t seg, kmers_hit, n_kmers, n_perfect;
+} cid_nearest;
+int cid_search_nearest_segments(cid_ctx *, const cid_index *, const uint8_t *kmers, const uint64_t *seg_off, size_t n_segs,
+                                const uint64_t *group_off, size_t n_groups, cid_nearest *out);
+int cid_search_nearest_segments_dev(cid_ctx *, const cid_index *, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs,
+                                    uint64_t n_kmers, const uint64_t *d_group_off, size_t n_groups, cid_nearest *d_out);
+
 /* ---- Coverage search (EXTENDED): WHERE on each query an accession hits (`search -g -m --coverage`).  The segmented search with the
  *      windows kept in sequence order.  A segment is one record: L windows numbered 0 .. L-1, window w covers bases [w, w + k_size).
  *      `kmers` holds one canonical upper-case k-mer per window, in order (k_size ASCII bytes each), segment s = windows
