@@ -58,6 +58,9 @@ SIGNATURES = {
     "cid_pairs_add_index": (C.c_int, [vp, vp]),
     "cid_pairs_fetch": (C.c_int, [vp, vp]),
     "cid_pairs_destroy": (None, [vp]),
+    "cid_dists_create": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "cid_dists_rows": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp]),
+    "cid_dists_destroy": (None, [vp]),
     "cid_search_count": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp]),
     "cid_search_count_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp]),
     "cid_search_perfect": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.POINTER(C.c_int)]),

@@ -1,4 +1,4 @@
-// Shared by the translation units behind the C ABI (cid_api_ctx / _index / _search / _readid / _pairs .hip); not part of the ABI.
+// Shared by the translation units behind the C ABI (cid_api_ctx / _index / _search / _readid / _pairs / _dists .hip); not part of the ABI.
 // stage_records: the one path of .bxi row records (cid_records.hpp) from a caller's memory to the kernels of load, merge, subset and compare.
 #pragma once
 #include "../../include/colorid_hip.h"

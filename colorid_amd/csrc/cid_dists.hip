@@ -1,0 +1,162 @@
+// `colorid dists` kernels for MI355X (gfx950): the pairwise allele distances of a cgMLST table (cid_dists_*).  The table is n_acc x n_loci
+// u32 allele codes, 0 = no call.  For two accessions i, j:  compared = #loci both called,  differ = #loci both called with unequal codes.
+// The device keeps the codes TRANSPOSED, T[locus][accession] with the accession stride padded to a multiple of 64 (the padding is zero =
+// missing), and per accession the bitmask of its called loci, maskT[word][accession].  Integer counts only: exact, whatever the schedule.
+#include "cid_kernels.hpp"
+
+namespace cid {
+
+constexpr uint32_t kDistsTile = 64;     // accessions per side of a workgroup's tile of pairs
+constexpr uint32_t kDistsChunk = 32;    // loci staged in LDS at a time: 2 x 32 x 64 x 4 = 16 KiB
+constexpr uint32_t kMissRow = 0xFFFFFFFFu, kMissCol = 0xFFFFFFFEu;   // what a missing cell is staged as on either side of a tile
+static_assert(kBlock == 256 && kWave == 64, "k_dists_*: 256 threads = 16 x 16 blocks of 4 x 4 pairs, staged by four waves");
+
+// One upload piece — the accessions [a0, a0 + na) as the caller holds them, row-major na x L — into T, 64 x 64 tiles through LDS so that
+// both the reads (along the loci) and the writes (along the accessions) are contiguous.  A code of 0xFFFFFFFE / 0xFFFFFFFF sets *err.
+// Grid: (ceil(L / 64), ceil(na / 64)).
+__global__ __launch_bounds__(kBlock) void k_dists_put(const uint32_t *codes, uint32_t a0, uint32_t na, uint32_t L, uint32_t *T, uint64_t Ap,
+                                                      uint32_t *err) {
+    __shared__ uint32_t tile[kDistsTile][kDistsTile + 1];
+    const uint32_t x = threadIdx.x & 63u, y = threadIdx.x >> 6;
+    const uint32_t l_base = blockIdx.x * kDistsTile, a_base = blockIdx.y * kDistsTile;
+    bool bad = false;
+    for (uint32_t r = y; r < kDistsTile; r += 4) {
+        const uint32_t a = a_base + r, l = l_base + x;
+        const uint32_t v = (a < na && l < L) ? codes[(uint64_t)a * L + l] : 0u;
+        bad |= v >= kMissCol;
+        tile[r][x] = v;
+    }
+    if (bad) atomicOr(err, 1u);
+    __syncthreads();
+    for (uint32_t r = y; r < kDistsTile; r += 4) {
+        const uint32_t l = l_base + r, a = a_base + x;
+        if (l < L && a < na) T[(uint64_t)l * Ap + a0 + a] = tile[x][r];
+    }
+}
+
+// The called-loci bitmasks of the same piece: one wave per (accession, 64 loci), bit b of word w = locus 64 w + b is called.
+__global__ __launch_bounds__(kBlock) void k_dists_mask(const uint32_t *codes, uint32_t a0, uint32_t na, uint32_t L, uint32_t W,
+                                                       unsigned long long *maskT, uint64_t Ap) {
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint64_t g = (uint64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    if (g >= (uint64_t)na * W) return;   // wave-uniform
+    const uint32_t a = (uint32_t)(g / W), w = (uint32_t)(g % W);
+    const uint32_t l = w * 64u + lane;
+    const uint32_t v = l < L ? codes[(uint64_t)a * L + l] : 0u;
+    const unsigned long long m = __ballot(v != 0u);
+    if (lane == 0) maskT[(uint64_t)w * Ap + a0 + a] = m;
+}
+
+// A workgroup owns the 64 x 64 pairs (row accessions row0 + 64 by .. + 63) x (column accessions 64 bx .. + 63) and walks the loci in
+// chunks of 32 staged in LDS as [locus][64 accessions], one array per side; a missing cell is staged as kMissRow on the row side and
+// kMissCol on the column side, two values no code may have (cid_dists_create refuses them), so it equals nothing — the diagonal tile
+// included — and the inner loop is equal += (a == b) and nothing else.  Thread (ty, tx) of the 16 x 16 keeps the 4 x 4 pairs (4 ty .. + 3)
+// x (4 tx .. + 3) in registers and reads its four row codes and its four column codes of a locus with one 16-byte LDS read each: a wave's
+// column addresses are 256 contiguous bytes, its row addresses four broadcasts — no bank conflict with the rows 256 bytes apart.
+// The next chunk's cells are fetched into registers before the current one is counted.  Loci past L are staged as missing (chunk tail);
+// row accessions past A are staged as missing and never stored, column accessions past A read T's zero padding (tile tails).
+// compared[i][j] = popcount(mask_i & mask_j) over the W mask words, differ = compared - equal.
+// BOUND: equal <= compared <= L < 2^32.
+__global__ __launch_bounds__(kBlock) void k_dists_tile(DistsParams p) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_row[kDistsChunk][kDistsTile];
+    __shared__ __attribute__((aligned(16))) uint32_t s_col[kDistsChunk][kDistsTile];
+    const uint32_t t = threadIdx.x, tx = t & 15u, ty = t >> 4;
+    const uint32_t sx = t & 63u, sl = t >> 6;   // staging: wave sl takes the loci sl, sl + 4, .. of a chunk, lane sx the accession
+    const uint64_t col_base = (uint64_t)blockIdx.x * kDistsTile, row_base = (uint64_t)p.row0 + (uint64_t)blockIdx.y * kDistsTile;
+    const bool row_ok = row_base + sx < p.A;
+    constexpr uint32_t kPer = kDistsChunk / 4;
+    uint32_t fr[kPer], fc[kPer];
+    auto fetch = [&](uint32_t l0) {
+#pragma unroll
+        for (uint32_t i = 0; i < kPer; ++i) {
+            const uint32_t l = l0 + sl + 4u * i;
+            fr[i] = (l < p.L && row_ok) ? p.T[(uint64_t)l * p.Ap + row_base + sx] : 0u;
+            fc[i] = l < p.L ? p.T[(uint64_t)l * p.Ap + col_base + sx] : 0u;
+        }
+    };
+    uint32_t eq[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) eq[r][c] = 0;
+    fetch(0);
+    for (uint32_t l0 = 0; l0 < p.L; l0 += kDistsChunk) {
+        __syncthreads();   // the chunk before has been counted by every wave
+#pragma unroll
+        for (uint32_t i = 0; i < kPer; ++i) {
+            s_row[sl + 4u * i][sx] = fr[i] ? fr[i] : kMissRow;
+            s_col[sl + 4u * i][sx] = fc[i] ? fc[i] : kMissCol;
+        }
+        __syncthreads();
+        if (p.L - l0 > kDistsChunk) fetch(l0 + kDistsChunk);
+#pragma unroll 2
+        for (uint32_t l = 0; l < kDistsChunk; ++l) {
+            const uint4 a4 = *reinterpret_cast<const uint4 *>(&s_row[l][4u * ty]);
+            const uint4 b4 = *reinterpret_cast<const uint4 *>(&s_col[l][4u * tx]);
+            const uint32_t a[4] = {a4.x, a4.y, a4.z, a4.w}, b[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) eq[r][c] += a[r] == b[c] ? 1u : 0u;
+        }
+    }
+    uint32_t cmp[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) cmp[r][c] = 0;
+    for (uint32_t w = 0; w < p.W; ++w) {
+        const unsigned long long *m = p.maskT + (uint64_t)w * p.Ap;
+        unsigned long long mi[4], mj[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const uint64_t i = row_base + 4u * ty + (uint32_t)r;
+            mi[r] = i < p.A ? m[i] : 0ull;
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) mj[c] = m[col_base + 4u * tx + (uint32_t)c];   // (< Ap: the padding's masks are zero)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) cmp[r][c] += (uint32_t)__popcll(mi[r] & mj[c]);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const uint64_t local = (uint64_t)blockIdx.y * kDistsTile + 4u * ty + (uint32_t)r;   // the row within [row0, row0 + n_rows)
+        if (local >= p.n_rows) continue;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint64_t j = col_base + 4u * tx + (uint32_t)c;
+            if (j >= p.A) continue;
+            p.differ[local * p.A + j] = cmp[r][c] - eq[r][c];
+            if (p.compared) p.compared[local * p.A + j] = cmp[r][c];
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// launchers
+
+hipError_t launch_dists_put(const uint32_t *d_codes, uint32_t a0, uint32_t na, uint32_t L, uint32_t *T, unsigned long long *maskT, uint64_t Ap,
+                            uint32_t *d_err, hipStream_t stream) {
+    if (na == 0 || L == 0) return hipSuccess;
+    if ((na + kDistsTile - 1) / kDistsTile > kDistsMaxRowTiles) return hipErrorInvalidValue;
+    const uint32_t W = (L + 63u) / 64u;
+    hipLaunchKernelGGL(k_dists_put, dim3((L + kDistsTile - 1) / kDistsTile, (na + kDistsTile - 1) / kDistsTile), dim3(kBlock), 0, stream, d_codes, a0,
+                       na, L, T, Ap, d_err);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const uint64_t waves = (uint64_t)na * W;
+    hipLaunchKernelGGL(k_dists_mask, dim3((unsigned)((waves + 3) / 4)), dim3(kBlock), 0, stream, d_codes, a0, na, L, W, maskT, Ap);
+    return hipGetLastError();
+}
+
+hipError_t launch_dists_tile(const DistsParams &p, hipStream_t stream) {
+    if (p.n_rows == 0 || p.A == 0) return hipSuccess;
+    const uint32_t row_tiles = (p.n_rows + kDistsTile - 1) / kDistsTile;
+    if (row_tiles > kDistsMaxRowTiles || (uint64_t)p.row0 + p.n_rows > p.A) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dists_tile, dim3((unsigned)(p.Ap / kDistsTile), row_tiles), dim3(kBlock), 0, stream, p);
+    return hipGetLastError();
+}
+
+}  // namespace cid

@@ -279,6 +279,21 @@ struct PairsParams {
 hipError_t launch_pairs_check(const uint32_t *d_records, uint32_t w32_rec, uint64_t n_records, uint64_t bloom_size, uint32_t n_colors,
                               uint32_t *d_err, hipStream_t stream);
 hipError_t launch_pairs(PairsParams p, int n_cu, hipStream_t stream);
+// `dists`: the allele distances of a cgMLST table (cid_dists.hip).  T: the codes transposed, L rows of Ap u32 (Ap = A rounded up to 64, the
+// padding zero); maskT: W = ceil(L / 64) rows of Ap u64, the called-loci bitmasks.  launch_dists_put deposits the accessions [a0, a0 + na)
+// of a row-major piece into both and ORs 1 into *d_err for a code of 0xFFFFFFFE or 0xFFFFFFFF.  launch_dists_tile fills the rows [row0,
+// row0 + n_rows) of differ and (unless null) compared, each n_rows x A u32; at most kDistsMaxRowTiles tiles of 64 rows a launch.
+struct DistsParams {
+    const uint32_t *T;
+    const unsigned long long *maskT;
+    uint64_t Ap;
+    uint32_t A, L, W, row0, n_rows;
+    uint32_t *differ, *compared;
+};
+constexpr uint32_t kDistsMaxRowTiles = 65535;
+hipError_t launch_dists_put(const uint32_t *d_codes, uint32_t a0, uint32_t na, uint32_t L, uint32_t *T, unsigned long long *maskT, uint64_t Ap,
+                            uint32_t *d_err, hipStream_t stream);
+hipError_t launch_dists_tile(const DistsParams &p, hipStream_t stream);
 hipError_t launch_get_rows(const uint64_t *mat, uint32_t rs, const uint64_t *d_row_ids, uint32_t *d_words, uint32_t w32,
                            uint64_t n_rows, hipStream_t stream);
 hipError_t launch_insert_kmers(const InsertParams &p, hipStream_t stream);

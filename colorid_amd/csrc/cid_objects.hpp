@@ -84,6 +84,15 @@ struct cid_pairs {
     unsigned long long *shared = nullptr;   // n_colors x n_colors, row-major
 };
 
+// `dists`: the allele codes of one cgMLST table (cid_dists_*), transposed, and the called-loci bitmasks (cid_dists.hip)
+struct cid_dists {
+    cid_ctx *ctx = nullptr;
+    uint32_t n_acc = 0, n_loci = 0, n_words = 0;   // n_words = ceil(n_loci / 64)
+    uint64_t acc_pad = 0;                           // n_acc rounded up to a multiple of 64: the row stride of both arrays
+    uint32_t *codes_t = nullptr;                    // n_loci x acc_pad
+    unsigned long long *mask_t = nullptr;           // n_words x acc_pad
+};
+
 namespace cid {
 // grow-only per-role device buffers of a ctx
 int slot_reserve(cid_ctx *c, int s, size_t bytes, void **out);

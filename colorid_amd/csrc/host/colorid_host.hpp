@@ -403,12 +403,15 @@ void read_counts_five_fields(const std::string &reads_file, const std::string &p
 // also .clean.tsv and .dropped.txt).  add(): one row, label and accession; add_rows_file(): the rows of a saved stdout, lines of fewer
 // than four TAB-separated fields (banner, warnings) skipped.  A label without '_' makes write() end the run, naming it, before any file
 // is made.  write() says on stderr how many accessions x loci it wrote.
+struct AlleleCodes;
 class AlleleTable {
   public:
     void add(const char *label, size_t label_len, const std::string &accession);
     void add(const std::string &label, const std::string &accession) { add(label.data(), label.size(), accession); }
     void add_rows_file(const std::string &path);
     void write(const std::string &prefix, long long max_missing) const;
+    // the raw table as allele codes (dists.cpp); max_missing >= 0: only the accessions that write() puts into PREFIX.clean.tsv
+    AlleleCodes codes(long long max_missing) const;
   private:
     struct Cell { std::string allele; size_t n = 0; };   // the first row's allele, the number of rows
     std::vector<std::string> accessions_;                // in order of their first row
@@ -443,6 +446,27 @@ class NearestTable {
     std::string bad_label_;
     bool bad_ = false;
 };
+
+// ---------------------------------------------------------------- allele distances and clusters (dists.cpp)
+// An accessions x loci table as u32 codes, what cid_dists_create takes: per locus the allele texts are numbered from 1 in order of first
+// appearance, 0 = no call (NA or an empty cell).  Made from an AlleleTable in memory (AlleleTable::codes) or from a table file in the form
+// of PREFIX.raw.tsv / PREFIX.clean.tsv (from_file: a missing header, a line with another number of cells — named by its number — and a
+// repeated accession end the run; it touches no GPU).
+struct AlleleCodes {
+    std::vector<std::string> accessions, loci;
+    std::vector<uint32_t> codes;   // accessions x loci, row-major
+    static AlleleCodes from_file(const std::string &path);
+};
+// `dists`: PREFIX.dists.tsv and PREFIX.compared.tsv (A x A, one line per accession), written row block by row block from cid_dists_rows —
+// the host never holds a whole matrix; with cluster also PREFIX.clusters.tsv: single linkage of the pairs with compared >= min_compared
+// (at least 1) and differ <= threshold, and every accession's nearest comparable neighbour.  ctx is not used (may be null) for a table
+// without accessions or without loci.  phase (may be null) is told when a part is done (COLORID_TIMING).  Says on stderr what it wrote.
+struct DistsOptions {
+    bool cluster = false;
+    uint64_t threshold = 0;      // --cluster T
+    uint64_t min_compared = 1;   // --min-compared M
+};
+void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, const DistsOptions &opt, void (*phase)(const char *) = nullptr);
 
 // ---------------------------------------------------------------- several GPUs (--gpus N / --devices a,b,..)
 // When set, the drivers below shard every query over the group's ranks (cid_group_*); results are identical.

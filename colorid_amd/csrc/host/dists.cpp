@@ -1,0 +1,235 @@
+// Pairwise allele distances and single-linkage clusters of a cgMLST table (`colorid dists -t TABLE -o PREFIX`, `search -s -m --alleles
+// PREFIX --dists`): the step after the accessions x loci table.  No reference counterpart (workflows/MLST/process_MLST.py stops at the table).
+//   table        PREFIX.raw.tsv / PREFIX.clean.tsv as alleles.cpp writes them: header = an empty first cell, then the loci; per accession its
+//                name and one cell per locus; NA or an empty cell = no call
+//   codes        per locus the allele texts numbered from 1 in order of first appearance, 0 = no call (AlleleCodes): what cid_dists_* takes
+//   compared     for two accessions, the loci at which both have a call;  differ: those of them at which the calls are not the same text
+//   PREFIX.dists.tsv, PREFIX.compared.tsv   header = an empty first cell, then the accessions; per accession its name and one integer per
+//                accession (differ / compared), written row block by row block: the host never holds an A x A matrix
+//   PREFIX.clusters.tsv (--cluster T [--min-compared M])   i and j are linked when compared >= M (at least 1: a pair without a common locus
+//                never links) and differ <= T; clusters = connected components, numbered from 1 in order of their first member
+#include "colorid_host.hpp"
+
+#include <algorithm>
+#include <numeric>
+
+namespace colorid {
+
+namespace {
+
+// The one encoder of both entrances: allele text -> code, per locus, in order of first appearance; "" and NA are no call.
+class AlleleEncoder {
+  public:
+    explicit AlleleEncoder(size_t n_loci) : maps_(n_loci) {}
+    uint32_t code(size_t locus, const char *text, size_t len) {
+        if (len == 0 || (len == 2 && text[0] == 'N' && text[1] == 'A')) return 0;
+        auto &m = maps_[locus];
+        key_.assign(text, len);   // (looked up first: an emplace makes its node before it looks)
+        const auto it = m.find(key_);
+        if (it != m.end()) return it->second;
+        if (m.size() >= 0xFFFFFFFDull) die("dists: more than 0xFFFFFFFD alleles at one locus");
+        return m.emplace(key_, (uint32_t)m.size() + 1u).first->second;
+    }
+  private:
+    std::vector<std::unordered_map<std::string, uint32_t>> maps_;
+    std::string key_;
+};
+
+void check_shape(size_t n_acc, size_t n_loci) {
+    if (n_acc > 0xFFFFFFFFull || n_loci > 0xFFFFFFFFull) die("dists: %zu accessions x %zu loci: more than 2^32 - 1 of either", n_acc, n_loci);
+}
+
+FILE *dists_out(const std::string &path) {
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) die("dists: could not create %s", path.c_str());
+    setvbuf(f, nullptr, _IOFBF, 1u << 20);
+    return f;
+}
+void dists_close(FILE *f, const std::string &path) {
+    if (fclose(f) != 0) die("dists: writing %s failed", path.c_str());
+}
+
+// name TAB v[0] TAB v[1] ... NL appended to `line`
+void append_row(std::string &line, const std::string &name, const uint32_t *v, size_t n) {
+    line += name;
+    char buf[12];
+    for (size_t j = 0; j < n; ++j) {
+        char *p = buf + sizeof buf;
+        uint32_t x = v[j];
+        do { *--p = (char)('0' + x % 10u); x /= 10u; } while (x);
+        *--p = '\t';
+        line.append(p, (size_t)(buf + sizeof buf - p));
+    }
+    line += '\n';
+}
+
+}  // namespace
+
+AlleleCodes AlleleTable::codes(long long max_missing) const {
+    AlleleCodes t;
+    t.loci.assign(loci_.begin(), loci_.end());
+    check_shape(accessions_.size(), t.loci.size());
+    AlleleEncoder enc(t.loci.size());
+    std::vector<uint32_t> row(t.loci.size());
+    for (size_t a = 0; a < accessions_.size(); ++a) {
+        const auto &cells = cells_[a];
+        size_t na = 0, l = 0;
+        auto it = cells.begin();   // ordered as the loci are: a merge walk, as write() does
+        for (const std::string &locus : t.loci) {
+            row[l] = 0;
+            if (it != cells.end() && it->first == locus) {
+                if (it->second.n == 1) row[l] = enc.code(l, it->second.allele.data(), it->second.allele.size());
+                else ++na;
+                ++it;
+            } else ++na;
+            ++l;
+        }
+        if (max_missing >= 0 && (long long)na > max_missing) continue;   // not in PREFIX.clean.tsv
+        t.accessions.push_back(accessions_[a]);
+        t.codes.insert(t.codes.end(), row.begin(), row.end());
+    }
+    return t;
+}
+
+AlleleCodes AlleleCodes::from_file(const std::string &path) {
+    FILE *f = fopen(path.c_str(), "r");
+    if (!f) die("dists: could not open %s", path.c_str());
+    AlleleCodes t;
+    char *line = nullptr;
+    size_t cap = 0, line_no = 0;
+    ssize_t n;
+    std::unique_ptr<AlleleEncoder> enc;
+    std::unordered_map<std::string, size_t> seen;   // accession -> its line
+    std::vector<std::pair<const char *, size_t>> cells;
+    while ((n = getline(&line, &cap, f)) >= 0) {
+        ++line_no;
+        size_t len = (size_t)n;
+        if (len && line[len - 1] == '\n') --len;
+        if (len && line[len - 1] == '\r') --len;
+        if (line_no > 1 && len == 0) continue;
+        cells.clear();
+        for (const char *p = line, *end = line + len;;) {
+            const char *tab = static_cast<const char *>(memchr(p, '\t', (size_t)(end - p)));
+            cells.emplace_back(p, (size_t)((tab ? tab : end) - p));
+            if (!tab) break;
+            p = tab + 1;
+        }
+        if (line_no == 1) {
+            if (cells[0].second != 0)
+                die("dists: %s has no header: its first line begins with '%.*s', not with an empty cell before the loci", path.c_str(),
+                    (int)std::min<size_t>(cells[0].second, 60), cells[0].first);
+            if (!(cells.size() == 2 && cells[1].second == 0))   // ("\t" alone: a table without loci)
+                for (size_t i = 1; i < cells.size(); ++i) t.loci.emplace_back(cells[i].first, cells[i].second);
+            enc.reset(new AlleleEncoder(t.loci.size()));
+            continue;
+        }
+        if (cells.size() != t.loci.size() + 1)
+            die("dists: %s line %zu has %zu cells after the name, the header has %zu loci", path.c_str(), line_no, cells.size() - 1, t.loci.size());
+        std::string name(cells[0].first, cells[0].second);
+        const auto ins = seen.emplace(name, line_no);
+        if (!ins.second)
+            die("dists: %s line %zu repeats the accession '%s' of line %zu", path.c_str(), line_no, name.c_str(), ins.first->second);
+        t.accessions.push_back(std::move(name));
+        for (size_t l = 0; l < t.loci.size(); ++l) t.codes.push_back(enc->code(l, cells[l + 1].first, cells[l + 1].second));
+    }
+    free(line);
+    fclose(f);
+    if (line_no == 0) die("dists: %s has no header: it is empty", path.c_str());
+    check_shape(t.accessions.size(), t.loci.size());
+    return t;
+}
+
+void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, const DistsOptions &opt, void (*phase)(const char *)) {
+    const size_t A = t.accessions.size(), L = t.loci.size();
+    const std::string d_path = prefix + ".dists.tsv", c_path = prefix + ".compared.tsv", k_path = prefix + ".clusters.tsv";
+    FILE *fd = dists_out(d_path), *fc = dists_out(c_path);
+    std::string header;
+    for (const std::string &a : t.accessions) { header += '\t'; header += a; }
+    if (A == 0) header += '\t';   // the raw table's convention for a header without columns
+    header += '\n';
+    fputs(header.c_str(), fd);
+    fputs(header.c_str(), fc);
+    const uint64_t min_compared = std::max<uint64_t>(opt.min_compared, 1);
+    // clustering state, fed row by row: union-find over the links, and per accession its nearest comparable neighbour
+    std::vector<uint32_t> parent(opt.cluster ? A : 0);
+    std::iota(parent.begin(), parent.end(), 0u);
+    auto find = [&](uint32_t x) {
+        while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
+        return x;
+    };
+    constexpr size_t kNone = ~(size_t)0;
+    struct Near { size_t j = kNone; uint32_t differ = 0, compared = 0; };
+    std::vector<Near> nearest(opt.cluster ? A : 0);
+    auto feed = [&](size_t i, const uint32_t *differ, const uint32_t *compared) {
+        Near best;
+        for (size_t j = 0; j < A; ++j) {
+            if (j == i || compared[j] < min_compared) continue;
+            if (best.j == kNone || differ[j] < best.differ || (differ[j] == best.differ && compared[j] > best.compared))
+                best = Near{j, differ[j], compared[j]};
+            if (j > i && differ[j] <= opt.threshold) {
+                const uint32_t a = find((uint32_t)i), b = find((uint32_t)j);
+                if (a != b) parent[std::max(a, b)] = std::min(a, b);
+            }
+        }
+        nearest[i] = best;
+    };
+    std::string line;
+    if (A && L) {
+        cid_dists *d = nullptr;
+        if (cid_dists_create(ctx, t.codes.data(), (uint32_t)A, (uint32_t)L, &d) != CID_OK) die("cid_dists_create: %s", cid_last_error());
+        if (phase) phase("allele codes uploaded");
+        // row blocks of whole 64-row tiles, about 32 MiB per matrix
+        size_t block = std::max<size_t>(64, ((32u << 20) / (A * 4)) & ~(size_t)63);
+        block = std::min(block, A);
+        std::vector<uint32_t> differ(block * A), compared(block * A);
+        for (size_t r0 = 0; r0 < A; r0 += block) {
+            const size_t nr = std::min(block, A - r0);
+            if (cid_dists_rows(d, (uint32_t)r0, (uint32_t)nr, differ.data(), compared.data()) != CID_OK) die("cid_dists_rows: %s", cid_last_error());
+            for (size_t r = 0; r < nr; ++r) {
+                line.clear();
+                append_row(line, t.accessions[r0 + r], &differ[r * A], A);
+                fwrite(line.data(), 1, line.size(), fd);
+                line.clear();
+                append_row(line, t.accessions[r0 + r], &compared[r * A], A);
+                fwrite(line.data(), 1, line.size(), fc);
+                if (opt.cluster) feed(r0 + r, &differ[r * A], &compared[r * A]);
+            }
+        }
+        cid_dists_destroy(d);
+    } else {   // no accession or no locus: nothing is compared anywhere, every cell is 0
+        const std::vector<uint32_t> zero(A, 0);
+        for (size_t i = 0; i < A; ++i) {
+            line.clear();
+            append_row(line, t.accessions[i], zero.data(), A);
+            fwrite(line.data(), 1, line.size(), fd);
+            fwrite(line.data(), 1, line.size(), fc);
+        }
+    }
+    dists_close(fd, d_path);
+    dists_close(fc, c_path);
+    if (phase) phase("distances computed and written");
+    fprintf(stderr, "dists: %zu accessions x %zu loci written to %s, %s\n", A, L, d_path.c_str(), c_path.c_str());
+    if (!opt.cluster) return;
+    std::vector<uint32_t> size(A, 0), number(A, 0);
+    for (size_t i = 0; i < A; ++i) ++size[find((uint32_t)i)];
+    size_t n_multi = 0, in_multi = 0;
+    uint32_t next = 0;
+    FILE *fk = dists_out(k_path);
+    fputs("accession\tcluster\tsize\tnearest\tdiffer\tcompared\n", fk);
+    for (size_t i = 0; i < A; ++i) {
+        const uint32_t root = find((uint32_t)i);
+        if (!number[root]) {   // (the root is the component's first member: unions keep the smaller index)
+            number[root] = ++next;
+            if (size[root] >= 2) { ++n_multi; in_multi += size[root]; }
+        }
+        const Near &nb = nearest[i];
+        if (nb.j == kNone) fprintf(fk, "%s\t%u\t%u\t-\t-\t-\n", t.accessions[i].c_str(), number[root], size[root]);
+        else fprintf(fk, "%s\t%u\t%u\t%s\t%u\t%u\n", t.accessions[i].c_str(), number[root], size[root], t.accessions[nb.j].c_str(), nb.differ, nb.compared);
+    }
+    dists_close(fk, k_path);
+    if (phase) phase("clusters written");
+    fprintf(stderr, "dists: %zu clusters of 2 or more at <= %llu differing loci hold %zu accessions, written to %s\n", n_multi,
+            (unsigned long long)opt.threshold, in_multi, k_path.c_str());
+}
+
+}  // namespace colorid

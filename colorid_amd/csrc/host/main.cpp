@@ -9,7 +9,8 @@
 // them are duplicates — the question before `subset -x`); fold (an index at a smaller Bloom size that divides its own, the file
 // `build -s` writes at that size: an over-sized index shrunk, or two indices brought to one size before `merge`); collapse (several
 // accessions of an index as one colour, the rows `build` writes over the members' sequences joined: strain-level index -> taxon-level);
-// alleles (the accessions x loci table of a cgMLST scheme from saved `search -s -m` rows; `search -s -m --alleles` makes it in the run).
+// alleles (the accessions x loci table of a cgMLST scheme from saved `search -s -m` rows; `search -s -m --alleles` makes it in the run);
+// dists (pairwise allele distances and single-linkage clusters of such a table; `search -s -m --alleles PREFIX --dists` makes them in the run).
 // Minimizer indices (.mxi): build -m [-v M], info, read_id, batch_id.  Not provided (outside the query path): read_filter.
 #include <algorithm>
 #include <cctype>
@@ -632,13 +633,33 @@ long long max_missing_arg(const Args &a) {
     return n;
 }
 
+// --cluster T / --min-compared M (search --dists, dists): a number of loci
+uint64_t loci_arg(const Args &a, const char *key) {
+    const std::string &v = a.one(key);
+    char *end = nullptr;
+    errno = 0;
+    const long long n = strtoll(v.c_str(), &end, 10);
+    if (v.empty() || *end || n < 0 || errno) die("error: --%s expects a number of loci (0 or more), got '%s'", key, v.c_str());
+    return (uint64_t)n;
+}
+// what --cluster and --min-compared ask for; refuses --min-compared without --cluster
+DistsOptions dists_options(const Args &a) {
+    DistsOptions o;
+    if (a.has("min-compared") && !a.has("cluster"))
+        die("error: --min-compared needs --cluster T (it is the least number of loci two accessions must share to be linked)");
+    if (a.has("cluster")) { o.cluster = true; o.threshold = loci_arg(a, "cluster"); }
+    if (a.has("min-compared")) o.min_compared = loci_arg(a, "min-compared");
+    return o;
+}
+
 int cmd_search(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, with_common({{'b', "bigsi", true, false}, {'q', "query", true, true}, {'r', "reverse", true, true},
                                                      {'f', "filter", true, false}, {'p', "p_shared", true, false}, {'g', "gene_search", false, false},
                                                      {'s', "perfect_search", false, false}, {'m', "multi_fasta", false, false},
                                                      {'Q', "quality", true, false}, {0, "coverage", false, false},
                                                      {0, "alleles", true, false}, {0, "max-missing", true, false},
-                                                     {0, "nearest", false, false}}));
+                                                     {0, "nearest", false, false}, {0, "dists", false, false},
+                                                     {0, "cluster", true, false}, {0, "min-compared", true, false}}));
     for (const char *req : {"bigsi", "query"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const std::vector<std::string> files1 = a.values.at("query");
@@ -661,6 +682,13 @@ int cmd_search(int argc, char **argv) {
         if (a.has("gpus") || a.has("devices") || a.has("placement") || cli_env("COLORID_REDUCE"))
             die("error: --nearest runs on one GPU: it does not go with --gpus, --devices, --placement or COLORID_REDUCE");
     }
+    // -s -m --alleles PREFIX --dists [--cluster T [--min-compared M]]: after the tables, the pairwise allele distances of the raw table's
+    // accessions (the clean table's with --max-missing) and their clusters, on this run's context: the files `colorid dists -t
+    // PREFIX.raw.tsv` writes.  Refused here, before the GPU context is made
+    const bool dists = a.flags.count("dists") != 0;
+    if (dists && !a.has("alleles")) die("error: --dists needs -s -m --alleles PREFIX (it writes PREFIX.dists.tsv from the allele table)");
+    if (!dists && a.has("cluster")) die("error: --cluster needs --dists (it clusters the allele distances)");
+    const DistsOptions dists_opt = dists_options(a);
     // -g -m --coverage: where on each record an accession hits (cid_search_cover).  FASTA records on one GPU; everything else is refused
     // here, before the GPU context is made
     const bool coverage = a.flags.count("coverage") != 0;
@@ -720,6 +748,7 @@ int cmd_search(int argc, char **argv) {
             if (a.has("alleles")) { fflush(stdout); table.write(a.one("alleles"), max_missing); }
             const double min_share = cov;   // -p: for --nearest the least share of a record's k-mers that is worth a line
             if (near) near->write(a.one("alleles"), b.colors, min_share);
+            if (dists) dists_run(ctx, table.codes(max_missing), a.one("alleles"), dists_opt);
         } else perfect_search::batch_search(ctx, files1, b);
     } else if (a.flags.count("gene_search") && a.flags.count("multi_fasta") &&
                std::none_of(files1.begin(), files1.end(), [](const std::string &f) { return ends_with(f, "gz"); })) {
@@ -745,6 +774,27 @@ int cmd_alleles(int argc, char **argv) {
     AlleleTable table;
     table.add_rows_file(a.one("rows"));
     table.write(a.one("output"), max_missing);
+    return 0;
+}
+
+// dists: -t TABLE -o PREFIX [--cluster T [--min-compared M]] — PREFIX.dists.tsv and PREFIX.compared.tsv (and PREFIX.clusters.tsv) from
+// a table in the form of PREFIX.raw.tsv / PREFIX.clean.tsv.  The table is read and checked before the GPU is opened; a table without
+// accessions or without loci needs none.
+int cmd_dists(int argc, char **argv) {
+    const Args a = parse(argc, argv, 2, {{'t', "table", true, false}, {'o', "output", true, false}, {0, "cluster", true, false},
+                                         {0, "min-compared", true, false}, {0, "device", true, false}});
+    for (const char *req : {"table", "output"})
+        if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
+    const DistsOptions opt = dists_options(a);
+    const AlleleCodes table = AlleleCodes::from_file(a.one("table"));
+    phase_done("table read");
+    cid_ctx *ctx = nullptr;
+    if (!table.accessions.empty() && !table.loci.empty()) {
+        ctx = make_ctx(a);
+        phase_done("GPU context");
+    }
+    dists_run(ctx, table, a.one("output"), opt, phase_done);
+    if (ctx) cid_ctx_destroy(ctx);
     return 0;
 }
 
@@ -1024,12 +1074,12 @@ int main(int argc, char **argv) {
     // src/main.rs:16-20: init_log() prints this banner on stdout before anything else
     printf("\n ************** initializing logger *****************\n\n");
     if (argc < 2) {
-        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare|collapse|alleles> [FLAGS]\n");
+        fprintf(stderr, "colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare|collapse|dists|alleles> [FLAGS]\n");
         return 1;
     }
     const std::string cmd = argv[1];
     if (cmd == "--help" || cmd == "-h" || cmd == "help") {
-        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare|collapse|alleles> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
+        printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare|collapse|dists|alleles> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
                "SEARCH:\n"
                "    search -b idx.bxi -q panel.fasta -g -m [-p 0.35]               every FASTA record its own gene query\n"
                "    search -b idx.bxi -q panel.fasta -g -m --coverage [-p 0.35]    the same rows, and where on the record the accession hits:\n"
@@ -1043,6 +1093,11 @@ int main(int argc, char **argv) {
                "                             and locus without a perfect allele, the known allele that shares most of its k-mers with the\n"
                "                             accession (share >= -p): a novel allele shares > 0.9, an absent locus nothing; one GPU, at most\n"
                "                             8192 accessions\n"
+               "    search -b idx.bxi -q scheme.fasta -s -m --alleles PREFIX --dists [--cluster T [--min-compared M]]   also PREFIX.dists.tsv and\n"
+               "                             PREFIX.compared.tsv: for every two accessions of the raw table (of the clean one with --max-missing)\n"
+               "                             the loci where both have an allele and the alleles differ / where both have one; --cluster T:\n"
+               "                             PREFIX.clusters.tsv, single linkage of the pairs at most T loci apart that share at least M (1)\n"
+               "    dists -t TABLE -o PREFIX [--cluster T [--min-compared M]]   the same files from a table in the form of PREFIX.raw.tsv\n"
                "    alleles -r ROWS -o PREFIX [--max-missing N]   the same tables from the saved stdout of a `search -s -m` run; no GPU\n\n"
                "INDEX MAINTENANCE:\n"
                "    collapse -b OUT -i idx.bxi -g groups.tsv      several accessions as one colour (groups.tsv: accession TAB group per line;\n"
@@ -1070,6 +1125,7 @@ int main(int argc, char **argv) {
     if (cmd == "fold") return leave(cmd_fold(argc, argv));
     if (cmd == "compare") return leave(cmd_compare(argc, argv));
     if (cmd == "collapse") return leave(cmd_collapse(argc, argv));
+    if (cmd == "dists") return leave(cmd_dists(argc, argv));
     if (cmd == "alleles") return leave(cmd_alleles(argc, argv));
     if (cmd == "debug-kmers") return cmd_debug_kmers(argc, argv);
     if (cmd == "debug-records") return cmd_debug_records(argc, argv);

@@ -389,6 +389,38 @@ class Pairs:
         self.close()
 
 
+class Dists:
+    """Pairwise allele distances of one cgMLST table (cid_dists, `colorid dists`): codes is n_acc x n_loci uint32, 0 = no call."""
+
+    def __init__(self, ctx, codes):
+        self.ctx, self.lib = ctx, ctx.lib
+        codes = np.ascontiguousarray(codes, np.uint32)
+        assert codes.ndim == 2
+        self.n_acc, self.n_loci = codes.shape
+        buf = codes if codes.size else np.zeros(1, np.uint32)
+        h = vp()
+        check(self.lib.cid_dists_create(ctx.h, _p(buf), self.n_acc, self.n_loci, C.byref(h)))
+        self.h = h
+        ctx._children.add(self)
+
+    def rows(self, row0=0, n_rows=None, compared=True):
+        """(differ, compared) of the rows [row0, row0 + n_rows), each n_rows x n_acc uint32; compared=False: (differ, None)"""
+        if n_rows is None:
+            n_rows = self.n_acc - row0
+        differ = np.zeros((n_rows, self.n_acc), np.uint32)
+        comp = np.zeros((n_rows, self.n_acc), np.uint32) if compared else None
+        check(self.lib.cid_dists_rows(self.h, row0, n_rows, _p(differ), _p(comp)))
+        return differ, comp
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.cid_dists_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
 class KmerSet:
     """Device-resident distinct canonical k-mers with multiplicities (cid_kmerset, k <= 32)."""
 

@@ -193,6 +193,23 @@ int cid_pairs_add_index(cid_pairs *, const cid_index *);
 int cid_pairs_fetch(cid_pairs *, uint64_t *shared);
 void cid_pairs_destroy(cid_pairs *);
 
+/* ---- `colorid dists` (EXTENDED; no reference counterpart): pairwise allele distances of a cgMLST table — the accessions x loci table of
+ *      `search -s -m --alleles` with every allele of a locus as a number.  For two accessions: at how many loci both have a call
+ *      (compared) and at how many of those the calls differ (differ).  Integer counts: exact and independent of scheduling. ---- */
+typedef struct cid_dists cid_dists;   /* device-resident allele codes of one table */
+/* codes: n_acc x n_loci u32, row-major (one row per accession).  0 = no call (missing); 1 .. 0xFFFFFFFD = an allele of that locus
+ * (codes of different loci are unrelated); 0xFFFFFFFE and 0xFFFFFFFF are refused (CID_ERR_INVALID, checked on the device before anything
+ * is kept).  CID_ERR_INVALID: null argument, n_acc == 0 or n_loci == 0.  CID_ERR_UNSUPPORTED (message states the byte count): the codes
+ * plus one 64-row block of results do not fit in free device memory. */
+int cid_dists_create(cid_ctx *, const uint32_t *codes, uint32_t n_acc, uint32_t n_loci, cid_dists **out);
+/* Rows [row0, row0 + n_rows) of the two A x A matrices, each n_rows x n_acc u32, row-major:
+ *   compared[i][j] = #loci l with codes[i][l] != 0 && codes[j][l] != 0          (diagonal: accession i's called loci)
+ *   differ[i][j]   = #loci l with both != 0 && codes[i][l] != codes[j][l]       (diagonal: 0)
+ * compared may be NULL.  n_rows == 0 is a no-op; row0 + n_rows > n_acc is CID_ERR_INVALID.  A block whose results exceed the ctx's
+ * "dense_report_bytes" is cut into slices of at least one row inside the call. */
+int cid_dists_rows(cid_dists *, uint32_t row0, uint32_t n_rows, uint32_t *differ, uint32_t *compared);
+void cid_dists_destroy(cid_dists *);
+
 /* ---- a5: proportional search, the hot loop of batch_search_pe::batch_search
  *      (src/batch_search_pe.rs:45-84 and :125-164).  For each distinct k-mer: n hashes -> n rows -> AND;
  *      hits[c] += 1 for every set colour c; if exactly one colour is set: n_unique[c] += 1,

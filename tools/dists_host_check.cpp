@@ -1,0 +1,58 @@
+// Stand-alone host check of colorid_amd/csrc/host/dists.cpp under ASan + UBSan, no GPU and no libcolorid_hip.so: the table parser, the
+// allele encoder (both entrances), the row-block driver and the clustering, with a plain C++ cid_dists_* behind them.
+//   make -C tools bin/dists_host_check ;  tools/bin/dists_host_check TABLE PREFIX [T [M]]     (writes PREFIX.dists.tsv, .compared.tsv, .clusters.tsv)
+#include <cstdarg>
+#include "../colorid_amd/csrc/host/colorid_host.hpp"
+
+namespace colorid {
+void die(const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    fprintf(stderr, "colorid: ");
+    vfprintf(stderr, fmt, ap);
+    fprintf(stderr, "\n");
+    va_end(ap);
+    exit(101);
+}
+}  // namespace colorid
+
+struct cid_dists { std::vector<uint32_t> codes; uint32_t A, L; };
+extern "C" {
+const char *cid_last_error(void) { return "stub"; }
+int cid_dists_create(cid_ctx *, const uint32_t *codes, uint32_t A, uint32_t L, cid_dists **out) {
+    *out = new cid_dists{std::vector<uint32_t>(codes, codes + (size_t)A * L), A, L};
+    return 0;
+}
+int cid_dists_rows(cid_dists *d, uint32_t row0, uint32_t n, uint32_t *differ, uint32_t *compared) {
+    for (uint32_t r = 0; r < n; ++r)
+        for (uint32_t j = 0; j < d->A; ++j) {
+            uint32_t c = 0, x = 0;
+            for (uint32_t l = 0; l < d->L; ++l) {
+                const uint32_t a = d->codes[(size_t)(row0 + r) * d->L + l], b = d->codes[(size_t)j * d->L + l];
+                if (a && b) { ++c; x += a != b; }
+            }
+            differ[(size_t)r * d->A + j] = x;
+            if (compared) compared[(size_t)r * d->A + j] = c;
+        }
+    return 0;
+}
+void cid_dists_destroy(cid_dists *d) { delete d; }
+}
+
+int main(int argc, char **argv) {
+    using namespace colorid;
+    if (argc < 3) return 2;
+    DistsOptions o;
+    if (argc > 3) { o.cluster = true; o.threshold = strtoull(argv[3], nullptr, 10); }
+    if (argc > 4) o.min_compared = strtoull(argv[4], nullptr, 10);
+    const AlleleCodes t = AlleleCodes::from_file(argv[1]);
+    dists_run(nullptr, t, argv[2], o);
+    // the in-memory entrance over the same cells
+    AlleleTable tab;
+    for (size_t a = 0; a < t.accessions.size(); ++a)
+        for (size_t l = 0; l < t.loci.size(); ++l)
+            if (t.codes[a * t.loci.size() + l]) tab.add(t.loci[l] + "_" + std::to_string(t.codes[a * t.loci.size() + l]), t.accessions[a]);
+    const AlleleCodes u = tab.codes(-1);
+    fprintf(stderr, "in memory: %zu x %zu\n", u.accessions.size(), u.loci.size());
+    return 0;
+}
