@@ -1,7 +1,9 @@
 // C ABI of libcolorid_hip.so, part 3: the searches — a5 proportional (src/batch_search_pe.rs:45-84, :125-164) and a4 perfect
-// (src/perfect_search.rs:25-52, :83-110), whole indices and colour stripes, device-pointer and host-pointer forms.
-// Kernels: cid_search.hip.
+// (src/perfect_search.rs:25-52, :83-110), whole indices and colour stripes, device-pointer and host-pointer forms — and the searches
+// over many segments a call: counters, perfect, nearest per group (one host walk for the three: walk_segments, cid_segplan.hpp), coverage.
+// Kernels: cid_search.hip, cid_segments.hip, cid_perfect_segments.hip, cid_nearest.hip, cid_cover.hip.
 #include "cid_api_common.hpp"
+#include "cid_segplan.hpp"
 
 using cid::aligned16;
 using cid::check_not_mini;
@@ -75,6 +77,11 @@ int search_count_to_host(cid_ctx *c, const cid_index *ix, const cid::DevKeys &ke
     return CID_OK;
 }
 
+// u64 words of the padded row -> the BitVec's w32 u32 words
+void unpack_and_words(const uint64_t *row, size_t w32, uint32_t *words_le) {
+    for (size_t w = 0; w < w32; ++w) words_le[w] = (uint32_t)(row[w / 2] >> (32 * (w & 1)));
+}
+
 int search_perfect_to_host(cid_ctx *c, const cid_index *ix, const cid::DevKeys &keys, uint32_t *and_words_le, int *any_row_missing) {
     void *d_out;
     int rc = slot_reserve(c, S_MISC, (size_t)ix->rs * 8 + 16, &d_out);
@@ -89,10 +96,8 @@ int search_perfect_to_host(cid_ctx *c, const cid_index *ix, const cid::DevKeys &
     HIP_TRY(hipMemcpyAsync(&missing, d_missing, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *any_row_missing = missing ? 1 : 0;
-    for (uint32_t w = 0; w < ix->w32; ++w) {
-        const uint32_t v = (uint32_t)(h[w / 2] >> (32 * (w & 1)));
-        and_words_le[w] = missing ? 0u : v;
-    }
+    if (missing) memset(and_words_le, 0, (size_t)ix->w32 * 4);
+    else unpack_and_words(h.data(), ix->w32, and_words_le);
     return CID_OK;
 }
 
@@ -105,10 +110,9 @@ int check_segments_index(const cid_ctx *c, const cid_index *ix) {
     return CID_OK;
 }
 
-// device-resident inputs and outputs; `zero`: clear the outputs first (else they are added to); asynchronous on the ctx stream
+// device-resident inputs and outputs, n_segs < 2^32; `zero`: clear the outputs first (else they are added to); asynchronous on the ctx stream
 int search_segments_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_seg_off, size_t n_segs, uint64_t n_kmers,
                            uint32_t *d_hits, uint8_t *d_missing, bool zero) {
-    if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
     if (!d_seg_off || !d_hits) return fail(CID_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
     cid::SegmentParams q;
@@ -122,7 +126,6 @@ int search_segments_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kme
     HIP_TRY(cid::launch_search_segments(q, c->stream));
     return CID_OK;
 }
-
 
 // The segmented perfect search on device-resident inputs and outputs, asynchronous on the ctx stream.  `preset`: set the words to all
 // ones and the flags to 0 first (else they are ANDed into / OR-ed: the second launch over a row that a chunk boundary cut)
@@ -142,6 +145,52 @@ int perfect_segments_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_km
     return CID_OK;
 }
 
+// A host seg_off of n_segs + 1 entries by the rules of cid_segplan.hpp; `bound`: max_len and what it counts, for the refusal
+int check_host_seg_off(const uint64_t *seg_off, size_t n_segs, uint64_t max_len, const char *bound) {
+    const cid::OffFault f = cid::check_seg_off(seg_off, n_segs, max_len);
+    if (f.rule == cid::OFF_FIRST_NONZERO) return fail(CID_ERR_INVALID, "seg_off[0] must be 0");
+    if (f.rule == cid::OFF_DECREASES) return fail(CID_ERR_INVALID, "seg_off decreases at segment %zu", (size_t)f.at);
+    if (f.rule == cid::OFF_TOO_LONG) return fail(CID_ERR_INVALID, "segment %zu has %s or more", (size_t)f.at, bound);
+    return CID_OK;
+}
+
+// segments per slice of a host-pointer call whose device copy of the results takes seg_bytes a segment (cid_ctx_tune "dense_report_bytes")
+size_t segments_per_slice(const cid_ctx *c, size_t seg_bytes, size_t n_segs) {
+    return std::min(std::max<size_t>(c->tune.dense_report_bytes / seg_bytes, 1), n_segs);
+}
+
+// The host-pointer form of the segmented searches.  The device copy of the results holds a slice of per_slice segments; a slice's k-mers
+// go up in chunks of upload_chunk_bytes, each with its own offsets: the slice's segments clipped to the chunk (cid::plan_slice), so a
+// segment cut by a chunk boundary goes through two launches that combine into the same row.  Per slice, on the ctx stream: its rows
+// (and flags, if any) are preset; the offsets go up; per chunk the k-mers go up and launch(d_kmers, d_off, n_loc, nk, seg) searches nk
+// k-mers whose n_loc segments start at segment `seg` of the slice; finish(s0, s1, the device copy of seg_off[s0 .. s1]) ends the slice,
+// reads back what it has to and synchronises the stream: the next slice rewrites the host offsets and reuses the k-mer and offset slots.
+struct SlicePreset { void *rows; size_t row_bytes; int fill; void *flags; };   // the entry point's S_REPORT and S_NK slots
+template <class Launch, class Finish>
+int walk_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint64_t *seg_off, size_t n_segs, size_t per_slice, SlicePreset pre,
+                  Launch launch, Finish finish) {
+    const size_t k = ix->k, n_kmers = seg_off[n_segs];
+    size_t chunk = upload_chunk_kmers(c, k);
+    if (chunk > n_kmers) chunk = n_kmers ? n_kmers : 1;
+    void *d_k, *d_off;
+    int rc = slot_reserve(c, S_KMERS, chunk * k, &d_k); if (rc) return rc;
+    std::vector<uint64_t> loc;
+    std::vector<cid::SegPiece> pieces;
+    for (size_t s0 = 0; s0 < n_segs; s0 += per_slice) {
+        const size_t s1 = std::min(n_segs, s0 + per_slice);
+        cid::plan_slice(seg_off, s0, s1, chunk, loc, pieces);
+        HIP_TRY(hipMemsetAsync(pre.rows, pre.fill, (s1 - s0) * pre.row_bytes, c->stream));
+        if (pre.flags) HIP_TRY(hipMemsetAsync(pre.flags, 0, s1 - s0, c->stream));
+        rc = slot_reserve(c, S_SEQOFF, loc.size() * 8, &d_off); if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(d_off, loc.data(), loc.size() * 8, hipMemcpyHostToDevice, c->stream));
+        for (const cid::SegPiece &pc : pieces) {
+            HIP_TRY(hipMemcpyAsync(d_k, kmers + pc.k0 * k, pc.nk * k, hipMemcpyHostToDevice, c->stream));
+            if ((rc = launch((const uint8_t *)d_k, (const uint64_t *)d_off + pc.loc0, pc.n_loc, pc.nk, pc.seg0 - s0))) return rc;
+        }
+        if ((rc = finish(s0, s1, (const uint64_t *)d_off))) return rc;
+    }
+    return CID_OK;
+}
 
 // The coverage search's two launches, device-resident inputs and outputs, asynchronous on the ctx stream.  d_rows: one row of rs u64 per
 // window; the host form gathers a slice chunk by chunk (d_kmers, d_flags and d_rows then start at the chunk's first window) and
@@ -411,12 +460,11 @@ int cid_search_segments_dev(cid_ctx *c, const cid_index *ix, const uint8_t *d_km
     int rc = check_segments_index(c, ix);
     if (rc) return rc;
     if (n_segs == 0) return CID_OK;
+    if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
     return search_segments_launch(c, ix, d_kmers, d_seg_off, n_segs, n_kmers, d_hits, d_any_row_missing, true);
 }
 
-// Host-pointer form.  The device copy of `hits` holds a slice of segments (dense_report_bytes); a slice's k-mers go up in chunks of
-// upload_chunk_bytes, each with its own offsets: the slice's segments clipped to the chunk, so a segment cut by a chunk boundary is
-// counted in two launches that add into the same row.
+// Host-pointer form (walk_segments): a slice's counters are zeroed, every chunk's launch adds into them, and they come back per slice.
 int cid_search_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint64_t *seg_off, size_t n_segs, uint32_t *hits,
                         uint8_t *any_row_missing) {
     int rc = check_segments_index(c, ix);
@@ -424,57 +472,22 @@ int cid_search_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, c
     if (n_segs == 0) return CID_OK;
     if (!seg_off || !hits) return fail(CID_ERR_INVALID, "null argument");
     if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
-    if (seg_off[0] != 0) return fail(CID_ERR_INVALID, "seg_off[0] must be 0");
-    for (size_t s = 0; s < n_segs; ++s) {
-        if (seg_off[s + 1] < seg_off[s]) return fail(CID_ERR_INVALID, "seg_off decreases at segment %zu", s);
-        if (seg_off[s + 1] - seg_off[s] >= (1ull << 32)) return fail(CID_ERR_INVALID, "segment %zu has 2^32 k-mers or more", s);
-    }
-    const uint64_t n_kmers = seg_off[n_segs];
-    if (n_kmers && !kmers) return fail(CID_ERR_INVALID, "null argument");
+    if ((rc = check_host_seg_off(seg_off, n_segs, 1ull << 32, "2^32 k-mers"))) return rc;
+    if (seg_off[n_segs] && !kmers) return fail(CID_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t C = ix->n_colors, k = ix->k;
-    size_t chunk = upload_chunk_kmers(c, k);
-    if (chunk > n_kmers) chunk = n_kmers ? (size_t)n_kmers : 1;
-    size_t per_slice = (size_t)(c->tune.dense_report_bytes / (C * 4));
-    if (per_slice == 0) per_slice = 1;
-    if (per_slice > n_segs) per_slice = n_segs;
-    void *d_k, *d_hits, *d_miss, *d_off;
-    rc = slot_reserve(c, S_KMERS, chunk * k, &d_k); if (rc) return rc;
+    const size_t C = ix->n_colors, per_slice = segments_per_slice(c, C * 4, n_segs);
+    void *d_hits, *d_miss;
     rc = slot_reserve(c, S_REPORT, per_slice * C * 4, &d_hits); if (rc) return rc;
     rc = slot_reserve(c, S_NK, per_slice, &d_miss); if (rc) return rc;
-    std::vector<uint64_t> loc;   // the slice's chunks' offset arrays, one after the other
-    struct Piece { size_t k0, nk, sa, n_loc, loc0; };
-    std::vector<Piece> pieces;
-    for (size_t s0 = 0; s0 < n_segs; s0 += per_slice) {
-        const size_t s1 = std::min(n_segs, s0 + per_slice);
-        loc.clear();
-        pieces.clear();
-        size_t sa = s0;
-        for (uint64_t k0 = seg_off[s0]; k0 < seg_off[s1]; k0 += chunk) {
-            const uint64_t k1 = std::min<uint64_t>(seg_off[s1], k0 + chunk);
-            while (seg_off[sa + 1] <= k0) ++sa;          // the segment that holds k-mer k0
-            size_t sb = sa;
-            while (seg_off[sb + 1] < k1) ++sb;           // the one that holds k-mer k1 - 1
-            pieces.push_back(Piece{(size_t)k0, (size_t)(k1 - k0), sa, sb - sa + 1, loc.size()});
-            for (size_t s = sa; s <= sb + 1; ++s) loc.push_back(std::min(std::max(seg_off[s], k0), k1) - k0);
-        }
-        HIP_TRY(hipMemsetAsync(d_hits, 0, (s1 - s0) * C * 4, c->stream));
-        HIP_TRY(hipMemsetAsync(d_miss, 0, s1 - s0, c->stream));
-        if (!pieces.empty()) {
-            rc = slot_reserve(c, S_SEQOFF, loc.size() * 8, &d_off); if (rc) return rc;
-            HIP_TRY(hipMemcpyAsync(d_off, loc.data(), loc.size() * 8, hipMemcpyHostToDevice, c->stream));
-        }
-        for (const Piece &pc : pieces) {
-            HIP_TRY(hipMemcpyAsync(d_k, kmers + pc.k0 * k, pc.nk * k, hipMemcpyHostToDevice, c->stream));
-            rc = search_segments_launch(c, ix, (const uint8_t *)d_k, (const uint64_t *)d_off + pc.loc0, pc.n_loc, pc.nk,
-                                        (uint32_t *)d_hits + (pc.sa - s0) * C, (uint8_t *)d_miss + (pc.sa - s0), false);
-            if (rc) return rc;
-        }
-        HIP_TRY(hipMemcpyAsync(hits + s0 * C, d_hits, (s1 - s0) * C * 4, hipMemcpyDeviceToHost, c->stream));
-        if (any_row_missing) HIP_TRY(hipMemcpyAsync(any_row_missing + s0, d_miss, s1 - s0, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return CID_OK;
+    return walk_segments(c, ix, kmers, seg_off, n_segs, per_slice, SlicePreset{d_hits, C * 4, 0, d_miss},
+        [&](const uint8_t *d_k, const uint64_t *d_off, size_t n_loc, size_t nk, size_t seg) {
+            return search_segments_launch(c, ix, d_k, d_off, n_loc, nk, (uint32_t *)d_hits + seg * C, (uint8_t *)d_miss + seg, false); },
+        [&](size_t s0, size_t s1, const uint64_t *) -> int {
+            HIP_TRY(hipMemcpyAsync(hits + s0 * C, d_hits, (s1 - s0) * C * 4, hipMemcpyDeviceToHost, c->stream));
+            if (any_row_missing) HIP_TRY(hipMemcpyAsync(any_row_missing + s0, d_miss, s1 - s0, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            return CID_OK;
+        });
 }
 
 // ------------------------------------------------------------------------------------------------ segmented perfect search (cid_perfect_segments.hip)
@@ -498,10 +511,8 @@ int cid_search_perfect_segments_dev(cid_ctx *c, const cid_index *ix, const uint8
     return CID_OK;
 }
 
-// Host-pointer form, chunked as cid_search_segments is.  The device copy of the words holds a slice of segments (dense_report_bytes); a
-// slice's k-mers go up in chunks of upload_chunk_bytes, each with its own offsets: the slice's segments clipped to the chunk, so a segment
-// cut by a chunk boundary is ANDed by two launches into the same row (preset once per slice) and its flag OR-ed the same way.  The finish
-// kernel runs once per slice, over the slice's true offsets.
+// Host-pointer form (walk_segments): a slice's words are preset to all ones and its flags to 0 once, every chunk's launch ANDs and ORs into
+// them, and the finish kernel runs once per slice, over the slice's true offsets.
 int cid_search_perfect_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint64_t *seg_off, size_t n_segs,
                                 uint32_t *and_words_le, uint8_t *any_row_missing) {
     int rc = check_segments_index(c, ix);
@@ -509,62 +520,27 @@ int cid_search_perfect_segments(cid_ctx *c, const cid_index *ix, const uint8_t *
     if (n_segs == 0) return CID_OK;
     if (!seg_off || !and_words_le) return fail(CID_ERR_INVALID, "null argument");
     if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
-    if (seg_off[0] != 0) return fail(CID_ERR_INVALID, "seg_off[0] must be 0");
-    for (size_t s = 0; s < n_segs; ++s) {
-        if (seg_off[s + 1] < seg_off[s]) return fail(CID_ERR_INVALID, "seg_off decreases at segment %zu", s);
-        if (seg_off[s + 1] - seg_off[s] >= (1ull << 32)) return fail(CID_ERR_INVALID, "segment %zu has 2^32 k-mers or more", s);
-    }
-    const uint64_t n_kmers = seg_off[n_segs];
-    if (n_kmers && !kmers) return fail(CID_ERR_INVALID, "null argument");
+    if ((rc = check_host_seg_off(seg_off, n_segs, 1ull << 32, "2^32 k-mers"))) return rc;
+    if (seg_off[n_segs] && !kmers) return fail(CID_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t k = ix->k, rs = ix->rs, w32 = ix->w32;
-    size_t chunk = upload_chunk_kmers(c, k);
-    if (chunk > n_kmers) chunk = n_kmers ? (size_t)n_kmers : 1;
-    size_t per_slice = (size_t)(c->tune.dense_report_bytes / (rs * 8));
-    if (per_slice == 0) per_slice = 1;
-    if (per_slice > n_segs) per_slice = n_segs;
-    void *d_k, *d_words, *d_miss, *d_off;
-    rc = slot_reserve(c, S_KMERS, chunk * k, &d_k); if (rc) return rc;
+    const size_t rs = ix->rs, w32 = ix->w32, per_slice = segments_per_slice(c, rs * 8, n_segs);
+    void *d_words, *d_miss;
     rc = slot_reserve(c, S_REPORT, per_slice * rs * 8, &d_words); if (rc) return rc;
     rc = slot_reserve(c, S_NK, per_slice, &d_miss); if (rc) return rc;
-    std::vector<uint64_t> loc;   // the slice's true offsets (per_slice + 1 of them, for the finish), then its chunks' clipped offset arrays
-    struct Piece { size_t k0, nk, sa, n_loc, loc0; };
-    std::vector<Piece> pieces;
     std::vector<uint64_t> h_words;
-    for (size_t s0 = 0; s0 < n_segs; s0 += per_slice) {
-        const size_t s1 = std::min(n_segs, s0 + per_slice), ns = s1 - s0;
-        loc.assign(seg_off + s0, seg_off + s1 + 1);
-        pieces.clear();
-        size_t sa = s0;
-        for (uint64_t k0 = seg_off[s0]; k0 < seg_off[s1]; k0 += chunk) {
-            const uint64_t k1 = std::min<uint64_t>(seg_off[s1], k0 + chunk);
-            while (seg_off[sa + 1] <= k0) ++sa;          // the segment that holds k-mer k0
-            size_t sb = sa;
-            while (seg_off[sb + 1] < k1) ++sb;           // the one that holds k-mer k1 - 1
-            pieces.push_back(Piece{(size_t)k0, (size_t)(k1 - k0), sa, sb - sa + 1, loc.size()});
-            for (size_t s = sa; s <= sb + 1; ++s) loc.push_back(std::min(std::max(seg_off[s], k0), k1) - k0);
-        }
-        HIP_TRY(hipMemsetAsync(d_words, 0xFF, ns * rs * 8, c->stream));
-        HIP_TRY(hipMemsetAsync(d_miss, 0, ns, c->stream));
-        rc = slot_reserve(c, S_SEQOFF, loc.size() * 8, &d_off); if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(d_off, loc.data(), loc.size() * 8, hipMemcpyHostToDevice, c->stream));
-        for (const Piece &pc : pieces) {
-            HIP_TRY(hipMemcpyAsync(d_k, kmers + pc.k0 * k, pc.nk * k, hipMemcpyHostToDevice, c->stream));
-            rc = perfect_segments_launch(c, ix, (const uint8_t *)d_k, (const uint64_t *)d_off + pc.loc0, pc.n_loc, pc.nk,
-                                         (uint64_t *)d_words + (pc.sa - s0) * rs, (uint8_t *)d_miss + (pc.sa - s0), false);
-            if (rc) return rc;
-        }
-        HIP_TRY(cid::launch_perfect_segments_finish((uint64_t *)d_words, (const uint8_t *)d_miss, (const uint64_t *)d_off, ns, (uint32_t)rs,
-                                                    ix->n_colors, c->stream));
-        h_words.resize(ns * rs);
-        HIP_TRY(hipMemcpyAsync(h_words.data(), d_words, ns * rs * 8, hipMemcpyDeviceToHost, c->stream));
-        if (any_row_missing) HIP_TRY(hipMemcpyAsync(any_row_missing + s0, d_miss, ns, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        for (size_t s = 0; s < ns; ++s)          // u64 words of the padded row -> the BitVec's u32 words
-            for (size_t w = 0; w < w32; ++w)
-                and_words_le[(s0 + s) * w32 + w] = (uint32_t)(h_words[s * rs + w / 2] >> (32 * (w & 1)));
-    }
-    return CID_OK;
+    return walk_segments(c, ix, kmers, seg_off, n_segs, per_slice, SlicePreset{d_words, rs * 8, 0xFF, d_miss},
+        [&](const uint8_t *d_k, const uint64_t *d_off, size_t n_loc, size_t nk, size_t seg) {
+            return perfect_segments_launch(c, ix, d_k, d_off, n_loc, nk, (uint64_t *)d_words + seg * rs, (uint8_t *)d_miss + seg, false); },
+        [&](size_t s0, size_t s1, const uint64_t *d_true_off) -> int {
+            const size_t ns = s1 - s0;
+            HIP_TRY(cid::launch_perfect_segments_finish((uint64_t *)d_words, (const uint8_t *)d_miss, d_true_off, ns, (uint32_t)rs, ix->n_colors, c->stream));
+            h_words.resize(ns * rs);
+            HIP_TRY(hipMemcpyAsync(h_words.data(), d_words, ns * rs * 8, hipMemcpyDeviceToHost, c->stream));
+            if (any_row_missing) HIP_TRY(hipMemcpyAsync(any_row_missing + s0, d_miss, ns, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            for (size_t s = 0; s < ns; ++s) unpack_and_words(&h_words[s * rs], w32, and_words_le + (s0 + s) * w32);
+            return CID_OK;
+        });
 }
 
 // ------------------------------------------------------------------------------------------------ nearest segment per group (cid_nearest.hip)
@@ -587,10 +563,9 @@ int cid_search_nearest_segments_dev(cid_ctx *c, const cid_index *ix, const uint8
     return CID_OK;
 }
 
-// Host-pointer form.  The cells of all groups stay on the device for the whole call, preset once.  The segments go through in slices whose
-// counters fit dense_report_bytes, a slice's k-mers in chunks of upload_chunk_bytes with clipped offsets, exactly as cid_search_segments
-// does; one k_nearest_groups launch ends the slice and merges the slice's part of every group it touches into the group's cells.  A cut
-// may fall inside a group: the earlier slice holds the lower segment numbers, and the order is total, so the result is that of one pass.
+// Host-pointer form (walk_segments).  The cells of all groups stay on the device for the whole call, preset once; a slice's counters are
+// cid_search_segments', and one k_nearest_groups launch ends the slice and merges its part of every group it touches into the group's cells.
+// A cut may fall inside a group: the earlier slice holds the lower segment numbers, and the order is total, so the result is that of one pass.
 int cid_search_nearest_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const uint64_t *seg_off, size_t n_segs,
                                 const uint64_t *group_off, size_t n_groups, cid_nearest *out) {
     int rc = check_segments_index(c, ix);
@@ -598,66 +573,35 @@ int cid_search_nearest_segments(cid_ctx *c, const cid_index *ix, const uint8_t *
     if (n_groups == 0 || n_segs == 0) return CID_OK;
     if (!seg_off || !group_off || !out) return fail(CID_ERR_INVALID, "null argument");
     if (n_segs >= (1ull << 32) || n_groups >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or groups, or more");
-    if (seg_off[0] != 0) return fail(CID_ERR_INVALID, "seg_off[0] must be 0");
-    for (size_t s = 0; s < n_segs; ++s) {
-        if (seg_off[s + 1] < seg_off[s]) return fail(CID_ERR_INVALID, "seg_off decreases at segment %zu", s);
-        if (seg_off[s + 1] - seg_off[s] >= (1ull << 32)) return fail(CID_ERR_INVALID, "segment %zu has 2^32 k-mers or more", s);
-    }
-    if (group_off[0] != 0) return fail(CID_ERR_INVALID, "group_off[0] must be 0");
-    for (size_t g = 0; g < n_groups; ++g)
-        if (group_off[g + 1] < group_off[g]) return fail(CID_ERR_INVALID, "group_off decreases at group %zu", g);
-    if (group_off[n_groups] != n_segs)
-        return fail(CID_ERR_INVALID, "group_off ends at %llu, not at the %zu segments", (unsigned long long)group_off[n_groups], n_segs);
-    const uint64_t n_kmers = seg_off[n_segs];
-    if (n_kmers && !kmers) return fail(CID_ERR_INVALID, "null argument");
+    if ((rc = check_host_seg_off(seg_off, n_segs, 1ull << 32, "2^32 k-mers"))) return rc;
+    const cid::OffFault g = cid::check_group_off(group_off, n_groups, n_segs);
+    if (g.rule == cid::OFF_FIRST_NONZERO) return fail(CID_ERR_INVALID, "group_off[0] must be 0");
+    if (g.rule == cid::OFF_DECREASES) return fail(CID_ERR_INVALID, "group_off decreases at group %zu", (size_t)g.at);
+    if (g.rule == cid::OFF_WRONG_END) return fail(CID_ERR_INVALID, "group_off ends at %llu, not at the %zu segments", (unsigned long long)g.at, n_segs);
+    if (seg_off[n_segs] && !kmers) return fail(CID_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
-    const size_t C = ix->n_colors, k = ix->k;
-    size_t chunk = upload_chunk_kmers(c, k);
-    if (chunk > n_kmers) chunk = n_kmers ? (size_t)n_kmers : 1;
-    size_t per_slice = (size_t)(c->tune.dense_report_bytes / (C * 4));
-    if (per_slice == 0) per_slice = 1;
-    if (per_slice > n_segs) per_slice = n_segs;
-    void *d_k, *d_hits, *d_off, *d_groups, *d_cells;
-    rc = slot_reserve(c, S_KMERS, chunk * k, &d_k); if (rc) return rc;
+    const size_t C = ix->n_colors, per_slice = segments_per_slice(c, C * 4, n_segs);
+    void *d_hits, *d_groups, *d_cells;
     rc = slot_reserve(c, S_REPORT, per_slice * C * 4, &d_hits); if (rc) return rc;
     rc = slot_reserve(c, S_ROWIDS, (n_groups + 1) * 8, &d_groups); if (rc) return rc;
     rc = slot_reserve(c, S_WORDS, n_groups * C * sizeof(cid_nearest), &d_cells); if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(d_groups, group_off, (n_groups + 1) * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(cid::launch_nearest_preset(d_cells, (uint64_t)n_groups * C, c->stream));
-    std::vector<uint64_t> loc;   // the slice's true offsets (its segments + 1 of them, for the lengths), then its chunks' clipped offset arrays
-    struct Piece { size_t k0, nk, sa, n_loc, loc0; };
-    std::vector<Piece> pieces;
     size_t ga = 0;               // the first group that reaches into the slice
-    for (size_t s0 = 0; s0 < n_segs; s0 += per_slice) {
-        const size_t s1 = std::min(n_segs, s0 + per_slice), ns = s1 - s0;
-        loc.assign(seg_off + s0, seg_off + s1 + 1);
-        pieces.clear();
-        size_t sa = s0;
-        for (uint64_t k0 = seg_off[s0]; k0 < seg_off[s1]; k0 += chunk) {
-            const uint64_t k1 = std::min<uint64_t>(seg_off[s1], k0 + chunk);
-            while (seg_off[sa + 1] <= k0) ++sa;          // the segment that holds k-mer k0
-            size_t sb = sa;
-            while (seg_off[sb + 1] < k1) ++sb;           // the one that holds k-mer k1 - 1
-            pieces.push_back(Piece{(size_t)k0, (size_t)(k1 - k0), sa, sb - sa + 1, loc.size()});
-            for (size_t s = sa; s <= sb + 1; ++s) loc.push_back(std::min(std::max(seg_off[s], k0), k1) - k0);
-        }
-        HIP_TRY(hipMemsetAsync(d_hits, 0, ns * C * 4, c->stream));
-        rc = slot_reserve(c, S_SEQOFF, loc.size() * 8, &d_off); if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(d_off, loc.data(), loc.size() * 8, hipMemcpyHostToDevice, c->stream));
-        for (const Piece &pc : pieces) {
-            HIP_TRY(hipMemcpyAsync(d_k, kmers + pc.k0 * k, pc.nk * k, hipMemcpyHostToDevice, c->stream));
-            rc = search_segments_launch(c, ix, (const uint8_t *)d_k, (const uint64_t *)d_off + pc.loc0, pc.n_loc, pc.nk,
-                                        (uint32_t *)d_hits + (pc.sa - s0) * C, nullptr, false);
-            if (rc) return rc;
-        }
-        while (group_off[ga + 1] <= s0) ++ga;            // (group_off ends at n_segs > s0)
-        size_t gb = ga;                                  // the last group that starts before the slice's end
-        while (gb + 1 < n_groups && group_off[gb + 1] < s1) ++gb;
-        cid::NearestParams q{(const uint32_t *)d_hits, (const uint64_t *)d_off, (const uint64_t *)d_groups + ga, gb - ga + 1, ga, s0, s1, (uint32_t)C,
-                             reinterpret_cast<uint4 *>(d_cells)};
-        HIP_TRY(cid::launch_nearest_groups(q, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));        // loc is rewritten for the next slice
-    }
+    rc = walk_segments(c, ix, kmers, seg_off, n_segs, per_slice, SlicePreset{d_hits, C * 4, 0, nullptr},
+        [&](const uint8_t *d_k, const uint64_t *d_off, size_t n_loc, size_t nk, size_t seg) {
+            return search_segments_launch(c, ix, d_k, d_off, n_loc, nk, (uint32_t *)d_hits + seg * C, nullptr, false); },
+        [&](size_t s0, size_t s1, const uint64_t *d_true_off) -> int {
+            while (group_off[ga + 1] <= s0) ++ga;            // (group_off ends at n_segs > s0)
+            size_t gb = ga;                                  // the last group that starts before the slice's end
+            while (gb + 1 < n_groups && group_off[gb + 1] < s1) ++gb;
+            cid::NearestParams q{(const uint32_t *)d_hits, d_true_off, (const uint64_t *)d_groups + ga, gb - ga + 1, ga, s0, s1, (uint32_t)C,
+                                 reinterpret_cast<uint4 *>(d_cells)};
+            HIP_TRY(cid::launch_nearest_groups(q, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            return CID_OK;
+        });
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, d_cells, n_groups * C * sizeof(cid_nearest), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return CID_OK;
@@ -691,11 +635,7 @@ int cid_search_cover(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, cons
     if (n_segs == 0) return CID_OK;
     if (!seg_off || !out) return fail(CID_ERR_INVALID, "null argument");
     if (n_segs >= (1ull << 32)) return fail(CID_ERR_INVALID, "2^32 segments or more");
-    if (seg_off[0] != 0) return fail(CID_ERR_INVALID, "seg_off[0] must be 0");
-    for (size_t s = 0; s < n_segs; ++s) {
-        if (seg_off[s + 1] < seg_off[s]) return fail(CID_ERR_INVALID, "seg_off decreases at segment %zu", s);
-        if (seg_off[s + 1] - seg_off[s] >= (1ull << 32) - 128) return fail(CID_ERR_INVALID, "segment %zu has 2^32 - 128 windows or more", s);
-    }
+    if ((rc = check_host_seg_off(seg_off, n_segs, (1ull << 32) - 128, "2^32 - 128 windows"))) return rc;
     if (seg_off[n_segs] && !kmers) return fail(CID_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(c->device));
     const size_t C = ix->n_colors, k = ix->k, row_bytes = (size_t)ix->rs * 8, cell_bytes = C * sizeof(cid_cover);

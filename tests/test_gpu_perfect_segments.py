@@ -128,11 +128,11 @@ def test_every_outcome_occurs(orc):
     assert all(seen)
 
 
-@pytest.mark.parametrize("switches", [("upload_chunk_bytes",), ("upload_chunk_bytes", "dense_report_bytes")], ids=lambda s: "+".join(s))
+@pytest.mark.parametrize("switches", [("upload_chunk_bytes",), ("dense_report_bytes",), ("upload_chunk_bytes", "dense_report_bytes")], ids=lambda s: "+".join(s))
 @pytest.mark.parametrize("layout", [LAYOUTS[0], LAYOUTS[2], LAYOUTS[5], LAYOUTS[6]], ids=lambda l: "C%d" % l[0])
 def test_chunked_uploads_and_sliced_words_change_nothing(orc, layout, switches):
     """one tile of 64 k-mers per upload chunk — every longer segment is ANDed by several launches into one row, and chunks cut across
-    runs of short segments — alone, and with one segment's words per slice of the device copy"""
+    runs of short segments — alone, and with one segment's words per slice of the device copy; and such slices alone"""
     import colorid_amd
     oix, kmers, seg_off, want_words, want_missing, _ = case(orc, layout)
     k = layout[2]
