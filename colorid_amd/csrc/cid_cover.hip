@@ -10,15 +10,15 @@
 //   bases_covered = |union of [w, w + k) over the windows with P| = windows_hit + sum over interior gaps of min(gap, k - 1)
 //                   + (k - 1 if any window hit), a gap being the absent windows between two consecutive runs.
 //
-// Two launches.  k_cover_rows is k_search_segments' staging and gather (stage_and_hash, gather_and; tiles of 64 consecutive windows of the
-// whole array) with another end: instead of counting, every lane stores its AND words to rows[window][rs], a window-major matrix of u64 —
-// a sub-pass of the wave writes 1 KiB of consecutive bytes.  Invalid windows are not hashed and store zeros.
+// Two launches.  k_cover_rows has the segmented searches' tiles, staging and gather (cid_segwalk.hpp: TileWave; tiles of 64 consecutive
+// windows of the whole array) but no segments and so no walk: every lane stores its AND words to rows[window][rs], a window-major matrix
+// of u64 — a sub-pass of the wave writes 1 KiB of consecutive bytes.  Invalid windows are not hashed and store zeros.
 // k_cover_stats runs one wave per (segment, 64-colour word j).  It walks the segment's tiles in order: lane l loads rows[t*64 + l][j]
 // (zero outside the segment, so segments may start and end inside a tile), the wave transposes the 64 x 64 bit block across its lanes, and
 // lane c, which then holds the 64 window bits of colour 64j + c, folds them into its statistics with plain bit operations; the state
 // (open run, zeros since the last run, counts) is carried in registers from tile to tile.  Lanes hold consecutive colours, so the
 // 32-byte cells they write are consecutive.
-#include "cid_gather.hpp"
+#include "cid_segwalk.hpp"
 
 namespace cid {
 
@@ -26,39 +26,22 @@ template <int LOG_LPR, bool NARROW>
 __global__ __launch_bounds__(kBlock) void k_cover_rows(CoverParams q) {
     extern __shared__ __align__(16) uint8_t smem[];
     const SearchParams &p = q.s;
-    constexpr int LPR = 1 << LOG_LPR;
-    constexpr int KPW = kWave / LPR;  // windows per sub-pass
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
+    const TileWave<LOG_LPR, NARROW> w(p, smem);   // (a lane past the row's real width loads nothing and stores zeros)
 
-    uint8_t *wbase = smem + (size_t)wave * p.wave_bytes;
-    uint32_t *img = reinterpret_cast<uint32_t *>(wbase);
-    uint32_t *ridx = reinterpret_cast<uint32_t *>(wbase + kmer_img_bytes(p.k));
-
-    const uint64_t n_tiles = (p.n_kmers + kWave - 1) / kWave;
-    const uint64_t tile0 = (uint64_t)blockIdx.x * p.tiles_per_block;
-    const uint64_t tile1 = tile0 + p.tiles_per_block < n_tiles ? tile0 + p.tiles_per_block : n_tiles;
-    const uint64_t per_wave = (p.tiles_per_block + kBlock / kWave - 1) / (kBlock / kWave);
-    const uint64_t w0 = tile0 + (uint64_t)wave * per_wave;
-    const uint64_t w1 = w0 + per_wave < tile1 ? w0 + per_wave : tile1;
-    const uint32_t col = lane & (LPR - 1);
-    const uint32_t col_word = NARROW ? 0u : 2u * col;
-    const bool col_live = col_word < p.w64;  // lanes past the row's real width load nothing and store zeros
-
-    for (uint64_t tile = w0; tile < w1; ++tile) {
+    for (uint64_t tile = w.w0; tile < w.w1; ++tile) {
         const uint64_t first = tile * kWave;
         const uint32_t n_live = p.n_kmers - first < (uint64_t)kWave ? (uint32_t)(p.n_kmers - first) : (uint32_t)kWave;
-        const bool valid = (uint32_t)lane < n_live && (!q.flags || (q.flags[first + lane] & 1u));
+        const bool valid = (uint32_t)w.lane < n_live && (!q.flags || (q.flags[first + w.lane] & 1u));
         const uint64_t vmask = __ballot(valid);   // wave-uniform: bit i = window first + i holds a k-mer
-        stage_and_hash(img, ridx, p.kmers, nullptr, p.n_kmers, first, p.k, p.n_hash, p.mod, lane, !valid);
+        stage_and_hash(w.img, w.ridx, p.kmers, nullptr, p.n_kmers, first, p.k, p.n_hash, p.mod, w.lane, !valid);
 #pragma unroll 1
-        for (int sub = 0; sub < LPR; ++sub) {
-            const int kk = sub * KPW + (lane >> LOG_LPR);
+        for (int sub = 0; sub < w.LPR; ++sub) {
+            const int kk = w.kk(sub);
             if ((uint32_t)kk >= n_live) continue;
             V16 a{0, 0};
             uint32_t zm;
-            if (((vmask >> kk) & 1ull) && col_live) a = gather_and<NARROW, false>(p.mat, p.rs, ridx, kk, col_word, p.n_hash, zm);
-            uint64_t *dst = q.rows + (first + (uint32_t)kk) * p.rs + col_word;
+            if (((vmask >> kk) & 1ull) && w.col_live) a = gather_and<NARROW, false>(p.mat, p.rs, w.ridx, kk, w.col_word, p.n_hash, zm);
+            uint64_t *dst = q.rows + (first + (uint32_t)kk) * p.rs + w.col_word;
             if constexpr (NARROW) *dst = a.x;
             else *reinterpret_cast<ulonglong2 *>(dst) = make_ulonglong2(a.x, a.y);
         }
@@ -153,14 +136,7 @@ __global__ __launch_bounds__(kBlock) void k_cover_stats(CoverParams q) {
 }
 
 hipError_t launch_cover_rows(const CoverParams &q, hipStream_t stream) {
-    const SearchParams &p = q.s;
-    if (p.rs > 128) return hipErrorInvalidValue;   // wide rows: refused by the ABI before it gets here
-    const bool narrow = p.rs == 1;
-    const int log_lpr = narrow ? 0 : log2u(p.rs / 2);
-    const size_t shmem = search_smem_bytes(p);
-    const int grid = grid_for(p.n_kmers, p.tiles_per_block);
-    if (grid == 0) return hipSuccess;
-    CID_LAUNCH_BY_LAYOUT(k_cover_rows, log_lpr, narrow, grid, shmem, stream, q);
+    CID_LAUNCH_TILES(k_cover_rows, q.s, false, stream, q);
 }
 
 hipError_t launch_cover_stats(const CoverParams &q, hipStream_t stream) {

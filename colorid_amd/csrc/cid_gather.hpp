@@ -382,6 +382,20 @@ static hipError_t launch_one(KernelT kernel, int grid, size_t shmem, hipStream_t
         }                                                                                    \
     } while (0)
 
+// The whole launch of a tile kernel KERNEL<LOG_LPR, NARROW> over the k-mers of the SearchParams p: rows of at most 128 words, the layout
+// they imply, the LDS p asks for, one workgroup per p.tiles_per_block tiles; no k-mers, or `nothing_to_do` (the launcher's own reason,
+// looked at after the refusal), no launch.  Returns from the launcher.
+#define CID_LAUNCH_TILES(KERNEL, p, nothing_to_do, stream, params)                                                      \
+    do {                                                                                                                \
+        if ((p).rs > 128) return hipErrorInvalidValue;   /* wide rows: refused by the ABI before it gets here */        \
+        const bool narrow_ = (p).rs == 1;                                                                               \
+        const int log_lpr_ = narrow_ ? 0 : log2u((p).rs / 2);                                                           \
+        const size_t shmem_ = search_smem_bytes(p);                                                                     \
+        const int grid_ = grid_for((p).n_kmers, (p).tiles_per_block);                                                   \
+        if (grid_ == 0 || (nothing_to_do)) return hipSuccess;                                                           \
+        CID_LAUNCH_BY_LAYOUT(KERNEL, log_lpr_, narrow_, grid_, shmem_, stream, params);                                 \
+    } while (0)
+
 #define CID_LAUNCH_BY_LAYOUT2(KERNEL, log_lpr, narrow, FLAG, grid, shmem, stream, params)           \
     do {                                                                                           \
         if (narrow) return launch_one(KERNEL<0, true, FLAG>, grid, shmem, stream, params);         \

@@ -17,7 +17,7 @@
 //   4. kernel-specific epilogue on the AND words.
 // read_id kernels: one wave per read(-pair); see k_readid / k_readid_list.
 // This file: a5 (k_search_count), a4 (k_search_perfect), their wide-row variants and the colour-stripe finalize.
-#include "cid_gather.hpp"
+#include "cid_segwalk.hpp"   // TileWave, group_and: k_search_perfect
 
 namespace cid {
 
@@ -214,46 +214,34 @@ __global__ __launch_bounds__(kBlock, UNROLL == 1 ? 4 : 3) void k_search_count(Se
 template <int LOG_LPR, bool NARROW>
 __global__ __launch_bounds__(kBlock) void k_search_perfect(SearchParams p) {
     extern __shared__ __align__(16) uint8_t smem[];
+    const TileWave<LOG_LPR, NARROW> w(p, smem);
     constexpr int LPR = 1 << LOG_LPR;
-    constexpr int KPW = kWave / LPR;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
+    const int lane = w.lane;
+    const uint32_t col = w.col, col_word = w.col_word;
+    const bool col_live = w.col_live;
 
     uint64_t *s_and = reinterpret_cast<uint64_t *>(smem);  // [rs] block-level AND
-    uint8_t *wbase = smem + 16ull * p.c_pad + (size_t)wave * p.wave_bytes;
-    uint32_t *img = reinterpret_cast<uint32_t *>(wbase);
-    uint32_t *ridx = reinterpret_cast<uint32_t *>(wbase + kmer_img_bytes(p.k));
-
     for (uint32_t c = threadIdx.x; c < p.rs; c += blockDim.x) s_and[c] = ~0ull;
     __syncthreads();
 
-    const uint64_t n_tiles = (p.n_kmers + kWave - 1) / kWave;
-    const uint64_t tile0 = (uint64_t)blockIdx.x * p.tiles_per_block;
-    const uint64_t tile1 = tile0 + p.tiles_per_block < n_tiles ? tile0 + p.tiles_per_block : n_tiles;
-    const uint32_t col = lane & (LPR - 1);
-    const uint32_t col_word = NARROW ? 0u : 2u * col;
-    const bool col_live = col_word < p.w64;
-
     V16 acc{~0ull, ~0ull};
     uint32_t missing = 0;
-    for (uint64_t tile = tile0 + wave; tile < tile1; tile += kBlock / kWave) {
+    for (uint64_t tile = w.tile0 + w.wave; tile < w.tile1; tile += kBlock / kWave) {   // (strided, not the wave's contiguous share)
         const uint64_t first = tile * kWave;
-        stage_and_hash(img, ridx, p.kmers, p.codes, p.n_kmers, first, p.k, p.n_hash, p.mod, lane);
+        stage_and_hash(w.img, w.ridx, p.kmers, p.codes, p.n_kmers, first, p.k, p.n_hash, p.mod, lane);
 #pragma unroll 1
         for (int sub = 0; sub < LPR; ++sub) {
-            const int kk = sub * KPW + (lane >> LOG_LPR);
+            const int kk = w.kk(sub);
             const bool live = first + kk < p.n_kmers;
             uint32_t zm = 0;
             if (live && col_live) {
-                const V16 a = gather_and<NARROW, true>(p.mat, p.rs, ridx, kk, col_word, p.n_hash, zm);
+                const V16 a = gather_and<NARROW, true>(p.mat, p.rs, w.ridx, kk, col_word, p.n_hash, zm);
                 acc.x &= a.x; acc.y &= a.y;
             } else {
                 zm = ~0u;  // a dead lane holds no bits of any row
             }
             // a row is absent (== all-zero) iff every live lane of its group saw a zero slice for that seed
-            uint32_t all_zero = zm;
-#pragma unroll
-            for (int o = 1; o < LPR; o <<= 1) all_zero &= __shfl_xor(all_zero, o, kWave);
+            const uint32_t all_zero = group_and<LOG_LPR>(zm);
             const uint32_t seeds = p.n_hash >= 32 ? ~0u : ((1u << p.n_hash) - 1u);
             if (p.zero_acc) {  // striped: a row is absent only if it is zero in every stripe
                 if (live && col == 0) p.zero_acc[first + kk] &= (all_zero & seeds);
@@ -501,12 +489,7 @@ hipError_t launch_search_perfect(const SearchParams &p, hipStream_t stream) {
         const int g = grid_for(p.n_kmers, p.tiles_per_block);
         return g ? launch_one(k_search_perfect_wide, g, (size_t)(kBlock / kWave) * p.wave_bytes, stream, p) : hipSuccess;
     }
-    const bool narrow = p.rs == 1;
-    const int log_lpr = narrow ? 0 : log2u(p.rs / 2);
-    const size_t shmem = search_smem_bytes(p);
-    const int grid = grid_for(p.n_kmers, p.tiles_per_block);
-    if (grid == 0) return hipSuccess;
-    CID_LAUNCH_BY_LAYOUT(k_search_perfect, log_lpr, narrow, grid, shmem, stream, p);
+    CID_LAUNCH_TILES(k_search_perfect, p, false, stream, p);
 }
 
 hipError_t warm_search() {   // see warm_readid

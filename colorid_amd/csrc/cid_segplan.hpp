@@ -1,12 +1,15 @@
 // The segmented searches' offsets on the host: the one check of seg_off and of group_off, and the one walk that cuts a slice of segments
 // into upload chunks with offsets of their own.  Segment s is the k-mers [seg_off[s], seg_off[s + 1]), group g the segments [group_off[g],
-// group_off[g + 1]).  Plain integer C++ (no HIP types), as cid_readbatch.hpp: also compiled with g++ by tests/test_segplan_cpu.py.
+// group_off[g + 1]).  And the one lookup the kernels share with it: the segment of a k-mer (segment_of, host and device: cid_segwalk.hpp).
+// Plain integer C++ (no HIP types), as cid_readbatch.hpp: also compiled with g++ by tests/test_segplan_cpu.py.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <vector>
+
+#include "cid_records.hpp"   // CID_HD
 
 namespace cid {
 
@@ -23,6 +26,18 @@ inline OffFault check_seg_off(const uint64_t *seg_off, size_t n_segs, uint64_t m
     }
     return OffFault{};
 }
+// The segment that holds `kmer`: the last s in [0, n_segs) with seg_off[s] <= kmer, so that ties — empty segments — resolve to the last
+// equal offset.  n_segs >= 1.  The result is in [0, n_segs) whatever seg_off holds (the kernels rely on that, not on the host's check:
+// the device-pointer forms never see the offsets on the host); reads seg_off[1 .. n_segs - 1] at most.
+CID_HD uint64_t segment_of(const uint64_t *seg_off, uint64_t n_segs, uint64_t kmer) {
+    uint64_t lo = 0, hi = n_segs - 1;
+    while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo + 1) / 2;
+        if (seg_off[mid] <= kmer) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
 // group_off[0] == 0 first; then no group decreases; last, the array ends at n_segs.  Reads group_off[0 .. n_groups]
 inline OffFault check_group_off(const uint64_t *group_off, size_t n_groups, size_t n_segs) {
     if (group_off[0] != 0) return OffFault{OFF_FIRST_NONZERO, 0};

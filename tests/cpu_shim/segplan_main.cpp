@@ -1,6 +1,7 @@
 // Stand-alone check (g++ -fsanitize=address,undefined) that cid_segplan.hpp reads nothing beyond the n_segs + 1 entries of seg_off and
 // the n_groups + 1 of group_off: both are heap arrays of EXACTLY that many entries, so a read past either is a sanitizer report.  Every
-// malformed array must be refused with the right rule and index, and plan_slice must tile every slice of a handful of layouts; exit
+// malformed array must be refused with the right rule and index, plan_slice must tile every slice of a handful of layouts, and the
+// kernels' lookup (segment_of) must stay inside the n_segs entries it may read and inside [0, n_segs) with what it returns; exit
 // status 0 = all as expected.  Test infrastructure only.
 #include "../../colorid_amd/csrc/cid_segplan.hpp"
 
@@ -48,6 +49,26 @@ static void walk(const char *what, const std::vector<uint64_t> &lens, size_t per
         ok = ok && next == off[s1] && used == loc.size();
         if (!ok) { fprintf(stderr, "%s: per_slice %zu, chunk %zu, slice at %zu: the pieces do not tile it\n", what, per_slice, chunk, s0); ++failures; }
     }
+}
+
+// segment_of over a heap array of EXACTLY n_segs entries (it never needs seg_off[n_segs]): with true offsets every k-mer lands in the
+// segment that holds it; with offsets that break every rule the result still indexes [0, n_segs)
+static void lookup(const char *what, const std::vector<uint64_t> &lens) {
+    std::vector<uint64_t> off(1, 0), holder;
+    for (size_t s = 0; s < lens.size(); ++s) {
+        off.push_back(off.back() + lens[s]);
+        holder.insert(holder.end(), lens[s], s);
+    }
+    const size_t n_segs = lens.size();
+    off.pop_back();
+    const std::unique_ptr<uint64_t[]> so = exact(off);
+    for (size_t kmer = 0; kmer < holder.size(); ++kmer)
+        if (cid::segment_of(so.get(), n_segs, kmer) != holder[kmer]) { fprintf(stderr, "%s: k-mer %zu is not in segment %zu\n", what, kmer, (size_t)holder[kmer]); ++failures; }
+    std::vector<uint64_t> bad(n_segs);
+    for (size_t s = 0; s < n_segs; ++s) bad[s] = s % 3 == 0 ? ~0ull : (n_segs - s) * 7;   // decreasing, huge, first entry not 0
+    const std::unique_ptr<uint64_t[]> sb = exact(bad);
+    for (const uint64_t kmer : {0ull, 1ull, 63ull, 64ull, 1000ull, 1ull << 32, ~0ull})
+        if (cid::segment_of(sb.get(), n_segs, kmer) >= n_segs) { fprintf(stderr, "%s: malformed offsets took k-mer %llu out of range\n", what, (unsigned long long)kmer); ++failures; }
 }
 
 int main() {
@@ -104,7 +125,11 @@ int main() {
             walk("boundary on a boundary", {64, 64, 128, 64}, per_slice, chunk);
             walk("one segment over three chunks", {3, 3 * chunk - 10, 5}, per_slice, chunk);
         }
+    lookup("mixed lengths", mixed);
+    lookup("one segment", {5});
+    lookup("a trailing empty segment", {1, 0});
+    lookup("leading empty segments", {0, 0, 64, 64, 0, 128, 1});
     if (failures) return 1;
-    puts("segplan: every malformed array refused within its bounds, every slice tiled");
+    puts("segplan: every malformed array refused within its bounds, every slice tiled, every k-mer in its segment");
     return 0;
 }

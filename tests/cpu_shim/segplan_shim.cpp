@@ -13,6 +13,10 @@ void shim_check_group_off(const uint64_t *group_off, uint64_t n_groups, uint64_t
     const cid::OffFault f = cid::check_group_off(group_off, (size_t)n_groups, (size_t)n_segs);
     out[0] = f.rule; out[1] = f.at;
 }
+// out[i] = the segment of kmers[i]
+void shim_segment_of(const uint64_t *seg_off, uint64_t n_segs, const uint64_t *kmers, uint64_t n, uint64_t *out) {
+    for (uint64_t i = 0; i < n; ++i) out[i] = cid::segment_of(seg_off, n_segs, kmers[i]);
+}
 // loc_out: room for loc_cap words, pieces_out: 5 words (k0, nk, seg0, n_loc, loc0) for each of piece_cap pieces; out[2] = the
 // numbers of loc words and of pieces (nothing is copied when either exceeds its room)
 void shim_plan_slice(const uint64_t *seg_off, uint64_t s0, uint64_t s1, uint64_t chunk, uint64_t *loc_out, uint64_t loc_cap, uint64_t *pieces_out,

@@ -234,3 +234,39 @@ def test_errors(orc, hip_ctx):
     wide.close()
     good()
     hx.close()
+
+
+@pytest.mark.parametrize("layout", seg.WALK_LAYOUTS, ids=lambda l: "C%d" % l[0])
+def test_a_wave_with_several_tiles(orc, hip_ctx, layout):
+    """test_gpu_segments' launch of two tiles a wave and its references (walk_case): the running AND carried from a wave's first tile to
+    its second, flushed between two segments, and flushed before a boundary tile"""
+    import torch
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    cs = seg.walk_case(orc, layout, n_cu)
+    seg_off, n_segs, n_kmers = cs["seg_off"], len(cs["seg_off"]) - 1, len(cs["idx"])
+    seg.check_walk_covers_the_tile_pairs(seg_off, n_cu)
+    oix = cs["oix"]
+    hx = to_hip_index(hip_ctx, oix)
+    rs = hx.device_matrix()[1]
+    dk = torch.from_numpy(cs["pool"][cs["idx"]].reshape(-1)).cuda()
+    do = torch.from_numpy(seg_off.astype(np.int64)).cuda()
+    d_words = torch.full((n_segs, rs), 0x5A5A5A5A12345678, dtype=torch.int64, device="cuda")
+    d_miss = torch.full((n_segs,), 0xA5, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    hx.search_perfect_segments_dev(dk.data_ptr(), do.data_ptr(), n_segs, n_kmers, d_words.data_ptr(), d_miss.data_ptr())
+    hip_ctx.synchronize()
+    w = d_words.cpu().numpy().view("<u4")
+    assert not w[:, oix.w32:].any()
+    got_words, got_missing = w[:, :oix.w32], d_miss.cpu().numpy().astype(bool)
+    bad = np.flatnonzero((got_words != cs["words"]).any(axis=1))
+    print(f"{layout}: {n_segs} segments, {len(bad)} differ in the words, {int((got_missing != cs['missing']).sum())} in the flag; "
+          f"{int(cs['words'].any(axis=1).sum())} with a perfect hit")
+    assert len(bad) == 0, f"segments {bad[:10]} (lengths {np.diff(seg_off)[bad[:10]]})"
+    assert np.array_equal(got_missing, cs["missing"])
+    # the planted classes: a perfect hit in c0 and c1, in c1 alone, in c1 and c2 — neighbours differ
+    c0, c1, c2 = cs["colours"]
+    lens = np.diff(seg_off)
+    for cls, (have, lack) in enumerate((((c0, c1), (c2,)), ((c1,), (c0, c2)), ((c1, c2), (c0,)))):
+        s = np.flatnonzero((np.arange(n_segs) % 7 == cls) & (lens >= 28))
+        assert len(s) and all(bit(got_words[s], c).all() for c in have) and not any(bit(got_words[s], c).any() for c in lack), cls
+    hx.close()

@@ -223,3 +223,128 @@ def test_errors(orc, hip_ctx):
     wide.close()
     good()
     hx.close()
+
+
+# ------------------------------------------------------------------------------------------------ a wave with several tiles
+# Every call above is a few thousand k-mers: four tiles per workgroup, one per wave, so a wave's counters are flushed only at its end.
+# The library gives a workgroup n_tiles // (32 * n_cu) tiles once that exceeds four; from 8 on a wave owns two consecutive tiles and
+# carries one segment's counters from the first to the second, or flushes between them.  16 384 * n_cu k-mers is the smallest such call.
+
+WALK_PATTERN = [128, 64, 64, 100, 28, 64, 1, 63, 640, 0, 0, 64]     # 19 tiles: the wave pairs fall on it in both phases
+WALK_LAYOUTS = [(4, 4, 16, 750_000), (129, 4, 16, 40_009)]          # rs = 1 (narrow); rs = 4 with dead lanes.  k = 16: 16 bytes a k-mer
+WALK_POOL = 4096
+_walk_cases = {}
+
+
+def walk_case(orc, layout, n_cu):
+    """16 384 * n_cu + 37 k-mers drawn from a pool of 4 096 distinct ones, and what the oracle's answer for every pool k-mer alone (its AND
+    word, its absent-row flag) implies per segment.  -> dict, made once: pool, idx (the pool index of every k-mer), seg_off, hits
+    [n_segs, C] uint32, missing [n_segs] bool, words [n_segs, w32] uint32 (zero where flagged or empty), and the oracle index.
+    Segment s draws from a part of the pool chosen by s % 7: the first quarter is planted into colours c0 and c1, the second into c1 and
+    c2, the rest into none — so neighbouring segments have perfect hits in different colours, or none, and only unplanted k-mers can meet
+    an absent row."""
+    key = (layout, n_cu)
+    if key in _walk_cases:
+        return _walk_cases[key]
+    n_colors, n_hash, k, m = layout
+    rng = np.random.default_rng(n_colors * 977 + n_cu)
+    n_kmers = 16_384 * n_cu + 37
+    reps = n_kmers // sum(WALK_PATTERN) + 1
+    lens = np.tile(WALK_PATTERN, reps)
+    lens = np.insert(lens, len(WALK_PATTERN) * (reps // 2), 5000)
+    n_whole = int(np.searchsorted(np.cumsum(lens), n_kmers, side="right"))      # segments that fit; the next one is cut to the ragged tail
+    lens = np.concatenate([lens[:n_whole], [n_kmers - int(lens[:n_whole].sum())], [0]])
+    n_segs = len(lens)
+    seg_off = np.zeros(n_segs + 1, np.uint64)
+    seg_off[1:] = np.cumsum(lens)
+    assert int(seg_off[-1]) == n_kmers
+
+    pool = np.unique(random_kmers(rng, WALK_POOL + 64, k), axis=0)[:WALK_POOL]
+    assert len(pool) == WALK_POOL
+    pool = pool[rng.permutation(WALK_POOL)]
+    oix = random_index(orc, rng, m, n_hash, k, n_colors, density=0.3, zero_row_frac=0.002)
+    q = WALK_POOL // 4
+    c0, c1, c2 = 0, n_colors // 2, n_colors - 1
+    for p in range(2 * q):
+        for c in ((c0, c1) if p < q else (c1, c2)):
+            oix.insert(c, pool[p].tobytes())
+    pool_words = np.zeros((WALK_POOL, oix.w32), np.uint32)
+    pool_missing = np.zeros(WALK_POOL, bool)
+    for p in range(WALK_POOL):
+        pool_words[p], pool_missing[p] = oix.search_perfect(pool[p:p + 1])
+    pool_bits = np.unpackbits(pool_words.view(np.uint8), axis=1, bitorder="little")[:, :n_colors]
+    assert pool_missing.any() and not pool_missing[:2 * q].any()
+
+    lo = np.array([0, 0, q, 0, 0, 0, 0])[np.arange(n_segs) % 7]
+    hi = np.array([q, 2 * q, 2 * q, 4 * q, 4 * q, 4 * q, 4 * q])[np.arange(n_segs) % 7]
+    idx = (np.repeat(lo, lens) + rng.random(n_kmers) * np.repeat(hi - lo, lens)).astype(np.int64)
+
+    full = np.flatnonzero(lens > 0)                           # reduceat wants strictly increasing starts: the non-empty segments
+    starts = seg_off[:-1][full].astype(np.int64)
+    missing = np.zeros(n_segs, bool)
+    missing[full] = np.logical_or.reduceat(pool_missing[idx], starts)
+    words = np.zeros((n_segs, oix.w32), np.uint32)
+    words[full] = np.bitwise_and.reduceat(pool_words[idx], starts, axis=0)
+    words[missing] = 0
+    hits = np.zeros((n_segs, n_colors), np.uint32)
+    for b in range(0, len(full), 4096):                       # block-wise over segments: no n_kmers x C array
+        blk = full[b:b + 4096]
+        k0, k1 = int(seg_off[blk[0]]), int(seg_off[blk[-1] + 1])
+        hits[blk] = np.add.reduceat(pool_bits[idx[k0:k1]], starts[b:b + 4096] - k0, axis=0, dtype=np.uint32)
+    for a in (pool, idx, seg_off, hits, missing, words):
+        a.setflags(write=False)
+    _walk_cases[key] = dict(oix=oix, pool=pool, idx=idx, seg_off=seg_off, hits=hits, missing=missing, words=words, colours=(c0, c1, c2))
+    return _walk_cases[key]
+
+
+def check_walk_covers_the_tile_pairs(seg_off, n_cu):
+    """the launch gives a wave two tiles, and every way two consecutive tiles of a wave can relate to the segments occurs in it"""
+    n_segs, n_kmers = len(seg_off) - 1, int(seg_off[-1])
+    n_tiles = (n_kmers + 63) // 64
+    tpb = n_tiles // (32 * n_cu)
+    assert tpb >= 8                                           # pick_tiles_per_block: 8 tiles a workgroup, two a wave
+    per_wave = (tpb + 3) // 4
+    first = np.arange(n_tiles, dtype=np.uint64) * 64
+    last = np.minimum(first + 63, n_kmers - 1)
+    sa = np.searchsorted(seg_off[:n_segs], first, side="right") - 1
+    sb = np.searchsorted(seg_off[:n_segs], last, side="right") - 1
+    one = sa == sb
+    t = np.arange(n_tiles - 1)
+    t = t[(t % tpb) % per_wave != per_wave - 1]               # tile t and t + 1 belong to one wave
+    a, b = t, t + 1
+    seen = {
+        "carried without a flush": (one[a] & one[b] & (sa[a] == sa[b])).sum(),
+        "flushed between two segments": (one[a] & one[b] & (sa[a] != sa[b]) & (seg_off[sa[a] + 1] == first[b])).sum(),
+        "a whole tile, then a boundary tile": (one[a] & ~one[b]).sum(),
+        "a boundary tile, then a whole tile": (~one[a] & one[b]).sum(),
+        "empty segments at a tile edge": ((np.diff(seg_off) == 0)[:-1] & (seg_off[:-2] % 64 == 0) & (seg_off[:-2] > 0) & (seg_off[:-2] < n_kmers)).sum(),
+    }
+    print(f"{n_kmers} k-mers, {n_tiles} tiles, {tpb} a workgroup:", seen)
+    assert all(seen.values()), seen
+
+
+@pytest.mark.parametrize("layout", WALK_LAYOUTS, ids=lambda l: "C%d" % l[0])
+def test_a_wave_with_several_tiles(orc, hip_ctx, layout):
+    import torch
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    cs = walk_case(orc, layout, n_cu)
+    seg_off, n_segs, n_kmers = cs["seg_off"], len(cs["seg_off"]) - 1, len(cs["idx"])
+    check_walk_covers_the_tile_pairs(seg_off, n_cu)
+    hx = to_hip_index(hip_ctx, cs["oix"])
+    dk = torch.from_numpy(cs["pool"][cs["idx"]].reshape(-1)).cuda()
+    do = torch.from_numpy(seg_off.astype(np.int64)).cuda()
+    d_hits = torch.full((n_segs, layout[0]), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+    d_miss = torch.full((n_segs,), 0xA5, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    hx.search_segments_dev(dk.data_ptr(), do.data_ptr(), n_segs, n_kmers, d_hits.data_ptr(), d_miss.data_ptr())
+    hip_ctx.synchronize()
+    got_hits, got_missing = d_hits.cpu().numpy().view(np.uint32), d_miss.cpu().numpy().astype(bool)
+    bad = np.flatnonzero((got_hits != cs["hits"]).any(axis=1))
+    print(f"{layout}: {n_segs} segments, {len(bad)} differ in hits, {int((got_missing != cs['missing']).sum())} in the flag; "
+          f"{int(cs['missing'].sum())} flagged")
+    assert len(bad) == 0, f"segments {bad[:10]} (lengths {np.diff(seg_off)[bad[:10]]})"
+    assert np.array_equal(got_missing, cs["missing"])
+    lens = np.diff(seg_off).astype(np.int64)
+    perfect = (lens > 0) & ~got_missing & (got_hits == lens[:, None]).any(axis=1)
+    assert perfect.any() and cs["missing"].any() and ((lens > 0) & ~cs["missing"] & ~perfect).any()
+    hx.close()

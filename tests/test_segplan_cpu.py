@@ -1,6 +1,7 @@
 """CPU check of the offset checks and the slice-and-chunk walk behind the segmented searches' host forms (colorid_amd/csrc/cid_segplan.hpp,
 compiled with g++): every slice of seeded random layouts against a few-line restatement and against the properties the kernels rely on,
-every malformed offset array refused with its rule and index — and, in a stand-alone program under AddressSanitizer, within its bounds."""
+every malformed offset array refused with its rule and index, the kernels' segment lookup (segment_of) against numpy and in range whatever
+the offsets hold — and, in a stand-alone program under AddressSanitizer, all of it within its bounds."""
 import ctypes as C
 import os
 import subprocess
@@ -25,6 +26,8 @@ def shim(tmp_path_factory):
     L.shim_check_group_off.restype = None
     L.shim_plan_slice.argtypes = [u64p, C.c_uint64, C.c_uint64, C.c_uint64, u64p, C.c_uint64, u64p, C.c_uint64, u64p]
     L.shim_plan_slice.restype = None
+    L.shim_segment_of.argtypes = [u64p, C.c_uint64, u64p, C.c_uint64, u64p]
+    L.shim_segment_of.restype = None
     return L
 
 
@@ -200,6 +203,41 @@ def test_each_malformed_group_off_is_refused_with_its_rule_and_index(shim, bad):
     for end in (n_segs - 1, n_segs + 1, 2**40):
         assert check_group(shim, good[:-1] + [end], n_segs) == (WRONG_END, end)     # `at` is where the array ends
     assert check_group(shim, [0], 0) == (OK, 0) and check_group(shim, [0, 0, 0], 0) == (OK, 0)
+
+
+def segment_of(shim, off, n_segs, kmers):
+    off = np.ascontiguousarray(off, np.uint64)
+    kmers = np.ascontiguousarray(kmers, np.uint64)
+    out = np.full(len(kmers), 2**64 - 1, np.uint64)
+    shim.shim_segment_of(_ptr(off), n_segs, _ptr(kmers), len(kmers), _ptr(out))
+    return out
+
+
+@pytest.mark.parametrize("lens", [[5], [0, 0, 3, 0, 0, 0, 64, 1, 0, 63, 0, 0], [0, 1], [1, 0], [64, 64, 0, 128, 1], "random"],
+                         ids=["one", "empties-everywhere", "leading", "trailing", "tile-edges", "random"])
+def test_the_segment_of_every_kmer(shim, lens):
+    """the kernels' lookup (segment_of): the last segment whose offset is <= the k-mer, so an empty segment never holds one"""
+    if lens == "random":
+        lens = random_lengths(np.random.default_rng(7))
+    off = offsets(lens)
+    n_segs, n_kmers = len(lens), int(off[-1])
+    kmers = np.arange(n_kmers, dtype=np.uint64)
+    got = segment_of(shim, off, n_segs, kmers)
+    assert np.array_equal(got, np.searchsorted(off[:n_segs], kmers, side="right") - 1)
+    assert (np.asarray(lens)[got.astype(np.int64)] > 0).all()                    # the segment that really holds the k-mer
+    assert np.array_equal(np.bincount(got.astype(np.int64), minlength=n_segs), lens)
+
+
+@pytest.mark.parametrize("n_segs", [1, 2, 3, 8, 33])
+def test_the_segment_stays_in_range_whatever_the_offsets_hold(shim, n_segs):
+    """any contents — decreasing, all equal, huge, a first entry that is not 0 — and any k-mer: the result indexes the kernels' outputs"""
+    rng = np.random.default_rng(n_segs)
+    arrays = [rng.integers(0, 300, n_segs + 1), np.sort(rng.integers(0, 300, n_segs + 1))[::-1], np.full(n_segs + 1, 2**64 - 1, np.uint64),
+              np.zeros(n_segs + 1), np.full(n_segs + 1, 150), rng.integers(0, 2**63, n_segs + 1)]
+    kmers = np.array(list(range(310)) + [2**32 - 1, 2**32, 2**63, 2**64 - 1], np.uint64)
+    for off in arrays:
+        got = segment_of(shim, np.asarray(off).astype(np.uint64), n_segs, kmers)
+        assert (got < n_segs).all(), (off, got)
 
 
 def test_the_checks_and_the_walk_stay_inside_their_arrays(tmp_path):
