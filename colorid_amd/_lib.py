@@ -72,6 +72,7 @@ SIGNATURES = {
     "cid_search_nearest_segments_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t, C.c_uint64, vp, C.c_size_t, vp]),
     "cid_search_cover": (C.c_int, [vp, vp, vp, vp, vp, C.c_size_t, vp]),
     "cid_search_cover_dev": (C.c_int, [vp, vp, vp, vp, vp, C.c_size_t, C.c_uint64, vp]),
+    "cid_search_gather": (C.c_int, [vp, vp, vp, vp, C.c_size_t, C.c_uint64, C.c_size_t, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     "cid_search_count_codes_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp]),
     "cid_search_count_stripe_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp]),
     "cid_search_unique_finalize_dev": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp]),
@@ -113,6 +114,7 @@ SIGNATURES = {
     "cid_search_count_set": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
     "cid_search_perfect_set": (C.c_int, [vp, vp, vp, vp, C.POINTER(C.c_int)]),
     "cid_search_count_set_report": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
+    "cid_search_gather_set": (C.c_int, [vp, vp, vp, C.c_uint64, C.c_size_t, vp, C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     "cid_unique_freq_modes_dev": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_uint32, vp]),
     "cid_readid_count": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, vp]),
     "cid_readid_count_sparse": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, C.POINTER(C.c_uint64)]),

@@ -36,6 +36,14 @@ inline uint32_t pick_tiles_per_block(const cid_ctx *c, uint64_t n_kmers) {
     return (uint32_t)tpb;
 }
 
+// k-mers per chunk of the pipelined host-pointer calls (cid_ctx_tune "upload_chunk_bytes" / CID_UPLOAD_CHUNK_BYTES: 256 MiB at k + 8 bytes
+// a k-mer).  Chunks start on a tile boundary: 64*k bytes keep the 16-byte alignment of the k-mer array; a budget below k + 8 bytes
+// (0 included) still moves a tile per chunk
+inline size_t upload_chunk_kmers(const cid_ctx *c, size_t k) {
+    const size_t chunk = ((size_t)c->tune.upload_chunk_bytes / (k + 8) + 63) & ~(size_t)63;
+    return chunk ? chunk : 64;
+}
+
 // check_record's bits as the error of the call
 inline int fail_malformed_records(uint32_t err) {
     return fail(CID_ERR_INVALID, "malformed row record(s):%s%s%s%s", (err & 1) ? " word count != ceil(n_colors/32)" : "",

@@ -11,6 +11,7 @@ using cid::check_ready;
 using cid::fail;
 using cid::pick_tiles_per_block;
 using cid::slot_reserve;
+using cid::upload_chunk_kmers;
 using namespace cid::slots;
 
 namespace {
@@ -48,14 +49,6 @@ int fill_search_params(const cid_ctx *c, const cid_index *ix, const cid::DevKeys
 // a caller's device pointers as keys of the index's k
 cid::DevKeys caller_keys(const cid_index *ix, const uint8_t *d_kmers, const uint64_t *d_codes, const uint32_t *d_freq, size_t n_kmers) {
     return cid::DevKeys{d_kmers, d_codes, d_freq, n_kmers, ix ? ix->k : 0, nullptr};
-}
-
-// k-mers per chunk of the pipelined host-pointer calls (cid_ctx_tune "upload_chunk_bytes" / CID_UPLOAD_CHUNK_BYTES: 256 MiB at k + 8 bytes
-// a k-mer).  Chunks start on a tile boundary: 64*k bytes keep the 16-byte alignment of the k-mer array; a budget below k + 8 bytes
-// (0 included) still moves a tile per chunk
-size_t upload_chunk_kmers(const cid_ctx *c, size_t k) {
-    const size_t chunk = ((size_t)c->tune.upload_chunk_bytes / (k + 8) + 63) & ~(size_t)63;
-    return chunk ? chunk : 64;
 }
 
 // host results for k-mers that are already on the device
@@ -195,8 +188,8 @@ int walk_segments(cid_ctx *c, const cid_index *ix, const uint8_t *kmers, const u
 // The coverage search's two launches, device-resident inputs and outputs, asynchronous on the ctx stream.  d_rows: one row of rs u64 per
 // window; the host form gathers a slice chunk by chunk (d_kmers, d_flags and d_rows then start at the chunk's first window) and
 // computes the statistics once over the whole slice.
-int fill_cover_params(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, uint64_t n_kmers, cid::CoverParams &q) {
-    int rc = fill_search_params(c, ix, caller_keys(ix, d_kmers, nullptr, nullptr, n_kmers), q.s);
+int fill_cover_params(cid_ctx *c, const cid_index *ix, const cid::DevKeys &keys, cid::CoverParams &q) {
+    int rc = fill_search_params(c, ix, keys, q.s);
     if (rc) return rc;
     q.s.c_pad = 0;   // no histogram: the k-mer image and the hash rows are all the LDS the gather needs
     q.s.wave_bytes = (cid::kmer_img_bytes(ix->k) + cid::kWave * ix->n_hash * 4u + 15u) & ~15u;
@@ -204,18 +197,13 @@ int fill_cover_params(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, u
 }
 
 int search_cover_rows_launch(cid_ctx *c, const cid_index *ix, const uint8_t *d_kmers, const uint8_t *d_flags, uint64_t n_kmers, uint64_t *d_rows) {
-    cid::CoverParams q{};
-    int rc = fill_cover_params(c, ix, d_kmers, n_kmers, q);
-    if (rc) return rc;
-    q.flags = d_flags; q.rows = d_rows;
-    HIP_TRY(cid::launch_cover_rows(q, c->stream));
-    return CID_OK;
+    return cid::cover_rows_launch(c, ix, caller_keys(ix, d_kmers, nullptr, nullptr, n_kmers), d_flags, d_rows);
 }
 
 int search_cover_stats_launch(cid_ctx *c, const cid_index *ix, const uint64_t *d_seg_off, const uint8_t *d_flags, size_t n_segs, uint64_t n_kmers,
                               const uint64_t *d_rows, cid_cover *d_out) {
     cid::CoverParams q{};
-    int rc = fill_cover_params(c, ix, nullptr, 0, q);
+    int rc = fill_cover_params(c, ix, cid::DevKeys{}, q);
     if (rc) return rc;
     q.s.n_kmers = n_kmers;
     q.flags = d_flags; q.rows = const_cast<uint64_t *>(d_rows); q.seg_off = d_seg_off; q.n_segs = n_segs; q.out = reinterpret_cast<uint32_t *>(d_out);
@@ -233,6 +221,15 @@ int check_cover_grid(const cid_index *ix, size_t n_segs) {
 }  // namespace
 
 namespace cid {
+
+int cover_rows_launch(cid_ctx *c, const cid_index *ix, const DevKeys &keys, const uint8_t *d_flags, uint64_t *d_rows) {
+    CoverParams q{};
+    int rc = fill_cover_params(c, ix, keys, q);
+    if (rc) return rc;
+    q.flags = d_flags; q.rows = d_rows;
+    HIP_TRY(launch_cover_rows(q, c->stream));
+    return CID_OK;
+}
 
 int search_count_launch(cid_ctx *c, const cid_index *ix, const DevKeys &keys, uint64_t *d_hits, uint64_t *d_n_unique, uint64_t *d_sum_unique_freq,
                         uint32_t *d_unique_colour, bool zero_counters) {

@@ -33,7 +33,7 @@ __global__ __launch_bounds__(kBlock) void k_cover_rows(CoverParams q) {
         const uint32_t n_live = p.n_kmers - first < (uint64_t)kWave ? (uint32_t)(p.n_kmers - first) : (uint32_t)kWave;
         const bool valid = (uint32_t)w.lane < n_live && (!q.flags || (q.flags[first + w.lane] & 1u));
         const uint64_t vmask = __ballot(valid);   // wave-uniform: bit i = window first + i holds a k-mer
-        stage_and_hash(w.img, w.ridx, p.kmers, nullptr, p.n_kmers, first, p.k, p.n_hash, p.mod, w.lane, !valid);
+        stage_and_hash(w.img, w.ridx, p.kmers, p.codes, p.n_kmers, first, p.k, p.n_hash, p.mod, w.lane, !valid);
 #pragma unroll 1
         for (int sub = 0; sub < w.LPR; ++sub) {
             const int kk = w.kk(sub);
@@ -46,22 +46,6 @@ __global__ __launch_bounds__(kBlock) void k_cover_rows(CoverParams q) {
             else *reinterpret_cast<ulonglong2 *>(dst) = make_ulonglong2(a.x, a.y);
         }
     }
-}
-
-// The 64 x 64 bit block held as one u64 per lane (lane l = row l), transposed: six butterfly steps, each swapping the off-diagonal
-// s x s sub-blocks between lanes l and l ^ s.  Afterwards lane c holds column c: bit l = bit c of what lane l had.
-__device__ __forceinline__ uint64_t transpose_bits64(uint64_t x, int lane) {
-    constexpr uint64_t kLow[6] = {0x00000000FFFFFFFFull, 0x0000FFFF0000FFFFull, 0x00FF00FF00FF00FFull,
-                                  0x0F0F0F0F0F0F0F0Full, 0x3333333333333333ull, 0x5555555555555555ull};   // bit indices with bit s clear
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        const int s = 32 >> i;
-        const uint64_t m = kLow[i];
-        const uint32_t ylo = __shfl_xor((uint32_t)x, s, kWave), yhi = __shfl_xor((uint32_t)(x >> 32), s, kWave);
-        const uint64_t y = ((uint64_t)yhi << 32) | ylo;
-        x = (lane & s) ? (((y >> s) & m) | (x & ~m)) : ((x & m) | ((y & m) << s));
-    }
-    return x;
 }
 
 struct CoverState {

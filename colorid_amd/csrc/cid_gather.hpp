@@ -291,6 +291,22 @@ __device__ __forceinline__ uint64_t wave_uniform(uint64_t v) {
     return ((uint64_t)wave_uniform((uint32_t)(v >> 32)) << 32) | wave_uniform((uint32_t)v);
 }
 
+// The 64 x 64 bit block held as one u64 per lane (lane l = row l), transposed: six butterfly steps, each swapping the off-diagonal
+// s x s sub-blocks between lanes l and l ^ s.  Afterwards lane c holds column c: bit l = bit c of what lane l had.
+__device__ __forceinline__ uint64_t transpose_bits64(uint64_t x, int lane) {
+    constexpr uint64_t kLow[6] = {0x00000000FFFFFFFFull, 0x0000FFFF0000FFFFull, 0x00FF00FF00FF00FFull,
+                                  0x0F0F0F0F0F0F0F0Full, 0x3333333333333333ull, 0x5555555555555555ull};   // bit indices with bit s clear
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        const int s = 32 >> i;
+        const uint64_t m = kLow[i];
+        const uint32_t ylo = __shfl_xor((uint32_t)x, s, kWave), yhi = __shfl_xor((uint32_t)(x >> 32), s, kWave);
+        const uint64_t y = ((uint64_t)yhi << 32) | ylo;
+        x = (lane & s) ? (((y >> s) & m) | (x & ~m)) : ((x & m) | ((y & m) << s));
+    }
+    return x;
+}
+
 // ------------------------------------------------------------------------------------------------ bases as bytes
 __device__ __forceinline__ bool good_base(uint32_t b) {  // src/seq.rs:59-64
     const uint32_t u = b & 0xDFu;

@@ -85,6 +85,9 @@ int search_count_launch(cid_ctx *c, const cid_index *ix, const DevKeys &keys, ui
                         uint32_t *d_unique_colour, bool zero_counters = true);
 // a4 launch: d_and (rs words) and d_missing (int) are preset here; asynchronous
 int search_perfect_launch(cid_ctx *c, const cid_index *ix, const DevKeys &keys, uint64_t *d_and, int *d_missing);
+// k_cover_rows on keys of either encoding: every key's AND words to d_rows[key * row stride + word] (d_flags: cid_search_cover's, or NULL);
+// asynchronous on the ctx stream, the caller has checked the index (at most 8192 colours, no minimizers) and set the device
+int cover_rows_launch(cid_ctx *c, const cid_index *ix, const DevKeys &keys, const uint8_t *d_flags, uint64_t *d_rows);
 // a5 / a4 on k-mers that are already on the device (keys.k must be the index's); outputs go to HOST buffers
 int search_count_keys(cid_ctx *c, const cid_index *ix, const DevKeys &keys, uint64_t *hits, uint64_t *n_unique, uint64_t *sum_unique_freq,
                       uint32_t *unique_colour);

@@ -225,6 +225,32 @@ struct CoverParams {
 };
 hipError_t launch_cover_rows(const CoverParams &p, hipStream_t stream);
 hipError_t launch_cover_stats(const CoverParams &p, hipStream_t stream);
+// Greedy cover of a query by accessions (cid_gather_cover.hip; include/colorid_hip.h: cid_search_gather) over k_cover_rows' matrix.
+// GatherRound is the state the rounds share, all of it on the device; the host reads its first 16 bytes once a round.
+struct GatherRound {
+    uint32_t stop;                    // set by k_gather_pick: this round emits nothing and there is no next one
+    uint32_t colour;                  // the round's pick (bounded by n_colors wherever it is read back)
+    uint64_t n_out;                   // rows emitted so far
+    unsigned long long live, n_hit;   // k-mers not yet explained; k-mers with a colour at all
+};
+struct GatherParams {
+    const uint64_t *rows;          // [n_kmers][rs]
+    const uint32_t *freq;          // [n_kmers] or nullptr = 1 everywhere
+    uint64_t n_kmers;
+    uint32_t rs, w64, n_colors;
+    uint32_t tiles_per_wave;       // k_gather_mark, k_gather_fold: consecutive 64-row tiles of one wave
+    uint64_t *alive;               // [ceil(n_kmers / 64)] bit l of word t: row 64t + l is live and has a colour
+    uint64_t *removed;             // [ceil(n_kmers / 64)] the rows the round's pick takes out
+    unsigned long long *cnt_new;   // [n_colors] new_t[c]
+    unsigned long long *total, *total_weight;   // [n_colors]
+    GatherRound *round;
+    void *out;                     // [max_rows] cid_gather_row
+    uint64_t min_new, max_rows;
+};
+hipError_t launch_gather_init(const GatherParams &p, hipStream_t stream);     // alive, n_hit, live
+hipError_t launch_gather_totals(const GatherParams &p, hipStream_t stream);   // total, total_weight (added to: caller zeroes)
+hipError_t launch_gather_pick(const GatherParams &p, hipStream_t stream);     // arg-max of cnt_new -> a row, or stop
+hipError_t launch_gather_round(const GatherParams &p, hipStream_t stream);    // mark the pick's rows, subtract their bits from cnt_new
 hipError_t launch_put_rows(uint64_t *mat, uint32_t rs, const uint64_t *d_row_ids, const uint32_t *d_words, uint32_t w32,
                            uint64_t n_rows, hipStream_t stream);
 hipError_t launch_put_records(uint64_t *mat, uint32_t rs, const uint32_t *d_records, uint32_t w32_rec, uint32_t w_off, uint32_t w32_take,

@@ -481,8 +481,23 @@ void batch_search(cid_ctx *, const std::vector<std::string> &files, const Bigsi 
 void batch_search_mf(cid_ctx *, const std::vector<std::string> &files, const Bigsi &b, AlleleTable *alleles = nullptr, NearestTable *nearest = nullptr);
 }
 namespace batch_search_pe {
+// `search --gather PREFIX` (no reference counterpart): PREFIX.gather.tsv, the greedy cover of every query by accessions
+// (cid_search_gather: what each accession ADDS to the ones listed before it).  One block per query: a row per round, then the
+// `unexplained` line.  The file is made by open (and removed should the run die), appended to per query, whole after finish.
+struct GatherOut {
+    std::string path;
+    FILE *f = nullptr;
+    uint64_t min_new = 1000;
+    size_t max_rows = 0;          // 0: the number of accessions
+    size_t n_rounds = 0;
+    double ms_calls = 0.0;
+    void open(const std::string &prefix);
+    // rows[n_rows] of the query's n_kmers distinct k-mers, n_hit of which have an accession at all
+    void add(const std::string &query, const Bigsi &b, size_t n_kmers, const cid_gather_row *rows, size_t n_rows, uint64_t n_hit);
+    void finish();
+};
 void batch_search(cid_ctx *, const std::vector<std::string> &files1, const std::vector<std::string> &files2, const Bigsi &b,
-                  int64_t filter, double cov, bool gene_search, uint8_t qual_offset);     // batch_search_pe.rs:9-179
+                  int64_t filter, double cov, bool gene_search, uint8_t qual_offset, GatherOut *gather = nullptr);     // batch_search_pe.rs:9-179
 void batch_search_mf(cid_ctx *, const std::vector<std::string> &files, const Bigsi &b, double cov);   // -g -m: every FASTA record its own query
 void batch_search_cover(cid_ctx *, const std::vector<std::string> &files, const Bigsi &b, double cov);   // -g -m --coverage: + where on the record
 }

@@ -452,9 +452,46 @@ void perfect_search::batch_search_mf(cid_ctx *ctx, const std::vector<std::string
 
 // ---------------------------------------------------------------------------------------------- batch_search_pe.rs
 
+void batch_search_pe::GatherOut::open(const std::string &prefix) {
+    path = prefix + ".gather.tsv";
+    f = fopen(path.c_str(), "w");
+    if (f) remove_on_die(path);
+    if (!f) die("could not create %s!", path.c_str());
+    fputs("query\trank\taccession\tnew_kmers\tnew_share\tnew_depth\ttotal_kmers\tgenome_cov\ttotal_depth\tlive_before\texpected_false\n", f);
+}
+
+void batch_search_pe::GatherOut::add(const std::string &query, const Bigsi &b, size_t n_kmers, const cid_gather_row *rows, size_t n_rows, uint64_t n_hit) {
+    auto ratio = [](uint64_t a, uint64_t d) { return d ? (double)a / (double)d : 0.0; };
+    uint64_t live = n_kmers;
+    for (size_t r = 0; r < n_rows; ++r) {
+        const cid_gather_row &g = rows[r];
+        const double n_ref = (double)b.n_ref_kmers[g.colour];
+        fprintf(f, "%s\t%zu\t%s\t%llu\t%.4f\t%.2f\t%llu\t%.2f\t%.2f\t%llu\t%.1f\n", query.c_str(), r + 1, b.colors[g.colour].c_str(),
+                (unsigned long long)g.new_kmers, ratio(g.new_kmers, n_kmers), ratio(g.new_weight, g.new_kmers), (unsigned long long)g.total_kmers,
+                (double)g.total_kmers / n_ref, ratio(g.total_weight, g.total_kmers), (unsigned long long)g.live_before,
+                (double)g.live_before * false_prob((double)b.bloom_size, (double)b.num_hash, n_ref));
+        live = g.live_before - g.new_kmers;
+    }
+    // what no listed accession explains; the total columns: the k-mers with an accession at all, and their share of the query's
+    fprintf(f, "%s\t-\tunexplained\t%llu\t%.4f\t-\t%llu\t%.2f\t-\t%llu\t-\n", query.c_str(), (unsigned long long)live, ratio(live, n_kmers),
+            (unsigned long long)n_hit, ratio(n_hit, n_kmers), (unsigned long long)live);
+    if (fflush(f) != 0) die("could not write %s!", path.c_str());
+    n_rounds += n_rows;
+}
+
+void batch_search_pe::GatherOut::finish() {
+    if (fclose(f) != 0) die("could not write %s!", path.c_str());
+    f = nullptr;
+    keep_on_die(path);
+    if (g_timing) fprintf(stderr, "timing: --gather: %zu rounds, %.0f ms in cid_search_gather (rows, totals, rounds, read-back)\n", n_rounds, ms_calls);
+}
+
 void batch_search_pe::batch_search(cid_ctx *ctx, const std::vector<std::string> &files1, const std::vector<std::string> &files2,
-                                   const Bigsi &b, int64_t filter, double cov, bool gene_search, uint8_t qual_offset) {
+                                   const Bigsi &b, int64_t filter, double cov, bool gene_search, uint8_t qual_offset, GatherOut *gather) {
     const size_t C = b.colors.size();
+    std::vector<cid_gather_row> g_rows(gather ? std::min(gather->max_rows ? gather->max_rows : C, C) : 0);
+    size_t g_n = 0;
+    uint64_t g_hit = 0;
     for (size_t i = 0; i < files1.size(); ++i) {
         const std::string &file1 = files1[i];
         const bool gz = file1.size() >= 2 && file1.compare(file1.size() - 2, 2, "gz") == 0;
@@ -502,6 +539,11 @@ void batch_search_pe::batch_search(cid_ctx *ctx, const std::vector<std::string> 
                 if (!gene_search) ks.counts(counts.data());
             }
             if (gz) fprintf(stderr, "Search: %ld sec\n", secs_since(t0));
+            if (gather) {
+                const auto tg = Clock::now();
+                CID_TRY(cid_search_gather_set(ctx, b.index, ks.one, gather->min_new, g_rows.size(), g_rows.data(), &g_n, &g_hit));
+                gather->ms_calls += ms_since(tg);
+            }
             ks.destroy();
         } else {  // host k-mer map (k > 32, lower-case fastq, or COLORID_HOST_KMERS)
             fprintf(stderr, "k-mer map on the host\n");
@@ -520,10 +562,16 @@ void batch_search_pe::batch_search(cid_ctx *ctx, const std::vector<std::string> 
                                      gene_search ? nullptr : n_unique.data(), gene_search ? nullptr : sum_freq.data(),
                                      gene_search ? nullptr : uc.data()));
             if (gz) fprintf(stderr, "Search: %ld sec\n", secs_since(t0));
+            if (gather) {
+                const auto tg = Clock::now();
+                CID_TRY(cid_search_gather(ctx, b.index, km.keys(), km.counts().data(), km.size(), gather->min_new, g_rows.size(), g_rows.data(), &g_n, &g_hit));
+                gather->ms_calls += ms_since(tg);
+            }
             counts = km.counts();
         }
         if (!gene_search) generate_report(file1, b, hits, n_unique, sum_freq, uc, counts.data(), n_kmers, cov, have_modes ? &modes : nullptr);
         else generate_report_gene(file1, b, hits, n_kmers, cov);
+        if (gather) gather->add(file1, b, n_kmers, g_rows.data(), g_n, g_hit);
     }
 }
 

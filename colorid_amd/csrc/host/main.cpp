@@ -652,6 +652,16 @@ DistsOptions dists_options(const Args &a) {
     return o;
 }
 
+// what --gather-min and --gather-max carry: a count of at least 1
+uint64_t gather_arg(const Args &a, const char *key) {
+    const std::string v = a.one(key);
+    char *end = nullptr;
+    errno = 0;
+    const unsigned long long n = strtoull(v.c_str(), &end, 10);
+    if (v.empty() || v[0] == '-' || *end || errno || n == 0) die("error: --%s expects a number of 1 or more, got '%s'", key, v.c_str());
+    return (uint64_t)n;
+}
+
 int cmd_search(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, with_common({{'b', "bigsi", true, false}, {'q', "query", true, true}, {'r', "reverse", true, true},
                                                      {'f', "filter", true, false}, {'p', "p_shared", true, false}, {'g', "gene_search", false, false},
@@ -659,10 +669,28 @@ int cmd_search(int argc, char **argv) {
                                                      {'Q', "quality", true, false}, {0, "coverage", false, false},
                                                      {0, "alleles", true, false}, {0, "max-missing", true, false},
                                                      {0, "nearest", false, false}, {0, "dists", false, false},
-                                                     {0, "cluster", true, false}, {0, "min-compared", true, false}}));
+                                                     {0, "cluster", true, false}, {0, "min-compared", true, false},
+                                                     {0, "gather", true, false}, {0, "gather-min", true, false}, {0, "gather-max", true, false}}));
     for (const char *req : {"bigsi", "query"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const std::vector<std::string> files1 = a.values.at("query");
+    // --gather PREFIX [--gather-min N] [--gather-max R]: after each query's search, the greedy cover of its k-mers by accessions
+    // (cid_search_gather) into PREFIX.gather.tsv.  The query's whole k-mer map against a whole index on one GPU; everything else is
+    // refused here, before the GPU context is made
+    batch_search_pe::GatherOut gather;
+    if (a.has("gather")) {
+        const std::pair<const char *, const char *> other[] = {{"gene_search", "-g"}, {"perfect_search", "-s"}, {"multi_fasta", "-m"}, {"coverage", "--coverage"}};
+        for (const auto &o : other)
+            if (a.flags.count(o.first)) die("error: --gather reads a whole query's k-mers against the index and does not go with %s", o.second);
+        for (const char *opt : {"gpus", "devices", "placement"})
+            if (a.has(opt)) die("error: --gather runs on one GPU: it does not go with --%s", opt);
+        if (cli_env("COLORID_REDUCE")) die("error: --gather runs on one GPU: it does not go with COLORID_REDUCE");
+    } else {
+        for (const char *opt : {"gather-min", "gather-max"})
+            if (a.has(opt)) die("error: --%s needs --gather PREFIX (it bounds the rows of PREFIX.gather.tsv)", opt);
+    }
+    if (a.has("gather-min")) gather.min_new = gather_arg(a, "gather-min");
+    if (a.has("gather-max")) gather.max_rows = (size_t)gather_arg(a, "gather-max");
     // -s -m --alleles PREFIX [--max-missing N]: the rows of -s -m, and the accessions x loci table made from them (AlleleTable) once
     // the last file is done.  What does not go together is refused here, before the GPU context is made
     if (a.has("alleles")) {
@@ -753,6 +781,13 @@ int cmd_search(int argc, char **argv) {
     } else if (a.flags.count("gene_search") && a.flags.count("multi_fasta") &&
                std::none_of(files1.begin(), files1.end(), [](const std::string &f) { return ends_with(f, "gz"); })) {
         batch_search_pe::batch_search_mf(ctx, files1, b, cov);   // -g -m: every FASTA record is its own query
+    } else if (a.has("gather")) {
+        if (b.m_size) die("error: --gather does not serve an index with minimizers: %s", a.one("bigsi").c_str());
+        if (b.colors.size() > 8192)
+            die("error: --gather serves indices of at most 8192 accessions; %s has %zu", a.one("bigsi").c_str(), b.colors.size());
+        gather.open(a.one("gather"));
+        batch_search_pe::batch_search(ctx, files1, files2, b, filter, cov, false, quality, &gather);
+        gather.finish();
     } else {
         batch_search_pe::batch_search(ctx, files1, files2, b, filter, cov, a.flags.count("gene_search") > 0, quality);
     }
@@ -1081,6 +1116,11 @@ int main(int argc, char **argv) {
     if (cmd == "--help" || cmd == "-h" || cmd == "help") {
         printf("colorid 0.1.4.3 (MI355X)\nUSAGE:\n    colorid <build|search|info|read_id|batch_id|hashcheck|merge|subset|fold|compare|collapse|dists|alleles> [FLAGS]      (flags: colorid <subcommand> --help)\n\n"
                "SEARCH:\n"
+               "    search -b idx.bxi -q R1.fq.gz [-r R2.fq.gz] [-f N] --gather PREFIX [--gather-min 1000] [--gather-max R]   the usual rows, and\n"
+               "                             PREFIX.gather.tsv: the accessions that explain the sample, greedily — the one with most of the\n"
+               "                             sample's k-mers, then the one with most of what is left, ... until an accession adds fewer than\n"
+               "                             --gather-min k-mers or --gather-max rows are out; shared k-mers count once; one GPU, at most\n"
+               "                             8192 accessions\n"
                "    search -b idx.bxi -q panel.fasta -g -m [-p 0.35]               every FASTA record its own gene query\n"
                "    search -b idx.bxi -q panel.fasta -g -m --coverage [-p 0.35]    the same rows, and where on the record the accession hits:\n"
                "                             bases covered / record length, longest covered stretch (bases), stretches, first and last\n"

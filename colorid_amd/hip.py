@@ -12,6 +12,9 @@ COVER_NONE = 0xFFFFFFFF         # first_window / last_window of a (segment, colo
 # one cell of cid_search_cover's output (include/colorid_hip.h: cid_cover)
 COVER_DTYPE = np.dtype([(f, "<u4") for f in ("kmers_hit", "windows_hit", "bases_covered", "n_runs", "longest_run", "first_window", "last_window",
                                              "reserved")])
+# one row of cid_search_gather's output (include/colorid_hip.h: cid_gather_row)
+GATHER_DTYPE = np.dtype([("colour", "<u4"), ("reserved", "<u4")] + [(f, "<u8") for f in ("new_kmers", "new_weight", "total_kmers", "total_weight",
+                                                                                         "live_before")])
 NEAREST_NONE = 0xFFFFFFFF       # seg of a (group, colour) that no segment of the group hits
 # one cell of cid_search_nearest_segments' output (include/colorid_hip.h: cid_nearest)
 NEAREST_DTYPE = np.dtype([(f, "<u4") for f in ("seg", "kmers_hit", "n_kmers", "n_perfect")])
@@ -301,6 +304,19 @@ class Index:
         check(self.lib.cid_search_cover_dev(self.ctx.h, self.h, vp(d_kmers) if d_kmers else None, vp(d_seg_off) if d_seg_off else None,
                                             vp(d_flags) if d_flags else None, n_segs, n_kmers, vp(d_out) if d_out else None))
 
+    # ---- greedy cover: the accessions that explain a query, one per round
+    def search_gather(self, kmers, freq=None, min_new=1, max_rows=None):
+        """distinct k-mers and their multiplicities (None = 1 each) -> (rows: array of GATHER_DTYPE in pick order, n_hit = the k-mers with a
+        colour at all); a round whose best colour adds fewer than min_new k-mers ends the call, as do max_rows rows (None: n_colors)"""
+        kmers = np.ascontiguousarray(kmers, np.uint8).reshape(-1, self.k)
+        f = None if freq is None else np.ascontiguousarray(freq, np.uint32)
+        assert f is None or len(f) == len(kmers)
+        max_rows = self.n_colors if max_rows is None else max_rows
+        out = np.zeros(max(min(max_rows, self.n_colors), 1), GATHER_DTYPE)
+        n_out, n_hit = C.c_size_t(0), C.c_uint64(0)
+        check(self.lib.cid_search_gather(self.ctx.h, self.h, _p(kmers), _p(f), len(kmers), min_new, max_rows, _p(out), C.byref(n_out), C.byref(n_hit)))
+        return out[:n_out.value], n_hit.value
+
     # ---- a6/a7/a9/a10
     def readid_count(self, bases, seq_off, read_seq0, d=1, start_sample=3):
         bases = np.ascontiguousarray(bases, np.uint8)
@@ -497,6 +513,14 @@ class KmerSet:
         uc = np.zeros(n, np.uint32)
         check(self.lib.cid_search_count_set(self.ctx.h, index.h, self.h, _p(hits), _p(nu), _p(sf), _p(uc)))
         return hits, nu, sf, uc
+
+    def search_gather(self, index, min_new=1, max_rows=None):
+        """Index.search_gather over this finalized set and its multiplicities"""
+        max_rows = index.n_colors if max_rows is None else max_rows
+        out = np.zeros(max(min(max_rows, index.n_colors), 1), GATHER_DTYPE)
+        n_out, n_hit = C.c_size_t(0), C.c_uint64(0)
+        check(self.lib.cid_search_gather_set(self.ctx.h, index.h, self.h, min_new, max_rows, _p(out), C.byref(n_out), C.byref(n_hit)))
+        return out[:n_out.value], n_hit.value
 
     def search_count_report(self, index):
         """-> (hits, n_unique, sum_unique_freq, mode_unique_freq): what generate_report needs, nothing per k-mer"""

@@ -445,6 +445,35 @@ CID_CORE int cid_search_count_set_report(cid_ctx *, const cid_index *, const cid
 int cid_unique_freq_modes_dev(cid_ctx *, const uint32_t *d_unique_colour, const uint32_t *d_freq, size_t n_kmers, uint32_t n_colors,
                               uint64_t *d_modes);
 
+/* ---- Greedy cover (EXTENDED): the accessions that explain a query, one per round (`search --gather`); the minimum-set-cover reading
+ *      of cid_search_count's hits, known from `sourmash gather`.  K = the query's distinct k-mers, f_k = the multiplicity of k-mer k
+ *      (1 without multiplicities), R_k = the colours set in the AND of k's num_hash rows: what cid_search_count counts.
+ *        total[c] = |{k : c in R_k}| (cid_search_count's hits[c]), total_weight[c] = the sum of f_k over the same k-mers,
+ *        *n_hit = |{k : R_k not empty}|.
+ *      Rounds t = 1, 2, ... over the live set L_1 = K:  new_t[c] = |{k in L_t : c in R_k}|;  c_t = the colour with the largest new_t[c],
+ *      ties to the LOWEST colour index.  The call ends, emitting nothing for the round, when new_t[c_t] < min_new (min_new >= 1) or when
+ *      max_rows rows have been emitted.  Otherwise out[t - 1] = {colour = c_t, reserved = 0, new_kmers = new_t[c_t], new_weight = the
+ *      sum of f_k over the k-mers of L_t that have c_t, total_kmers = total[c_t], total_weight = total_weight[c_t], live_before = |L_t|},
+ *      and L_{t+1} = L_t minus the k-mers that have c_t.  A colour is emitted at most once; two colours with the same k-mers give one
+ *      row, the lower index; at most min(max_rows, n_colors) entries of `out` are written, *n_out says how many.  Everything is
+ *      integer arithmetic and the pick is a total order: the result does not depend on how the device splits the work.
+ *      cid_search_gather: ASCII k-mers in host memory, distinct by the caller's map as for cid_search_count; freq may be NULL.
+ *      cid_search_gather_set: a finalized set, as for cid_search_count_set.  n_kmers == 0 (an empty set) or max_rows == 0 is CID_OK with
+ *      *n_out = 0 and *n_hit set.
+ *      CID_ERR_INVALID: a null argument, min_new == 0, a set of another k_size; CID_ERR_STATE: index or set not finalized;
+ *      CID_ERR_UNSUPPORTED: a minimizer index, or more than 8192 colours.
+ *      Device scratch: one AND row per k-mer, 8 * row_stride_words bytes each (cid_index_row_stride_words), from the ctx's block cache and
+ *      held for the whole call — 3.8 GB for 120 M k-mers at 256 colours — plus 16 bytes per 64 k-mers and 24 per colour.  The matrix is not
+ *      sliced: when a block cannot be had the call returns CID_ERR_NOMEM before anything is launched.  One stream wait per round. ---- */
+typedef struct cid_gather_row {
+    uint32_t colour, reserved;
+    uint64_t new_kmers, new_weight, total_kmers, total_weight, live_before;
+} cid_gather_row;
+int cid_search_gather(cid_ctx *, const cid_index *, const uint8_t *kmers, const uint32_t *freq, size_t n_kmers, uint64_t min_new,
+                      size_t max_rows, cid_gather_row *out, size_t *n_out, uint64_t *n_hit);
+int cid_search_gather_set(cid_ctx *, const cid_index *, const cid_kmerset *, uint64_t min_new, size_t max_rows, cid_gather_row *out,
+                          size_t *n_out, uint64_t *n_hit);
+
 /* ---- a4: perfect search, perfect_search::batch_search / batch_search_mf
  *      (src/perfect_search.rs:25-52, :83-110): AND of all n*K rows.  and_words_le: W32 u32 words;
  *      *any_row_missing = 1 iff some row is absent (the reference's "No perfect hits!"), in which case
