@@ -60,6 +60,8 @@ SIGNATURES = {
     "cid_pairs_destroy": (None, [vp]),
     "cid_dists_create": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
     "cid_dists_rows": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp]),
+    "cid_dists_best": (C.c_int, [vp, vp, C.c_uint32, vp]),
+    "cid_dists_forest": (C.c_int, [vp, C.c_uint32, vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "cid_dists_destroy": (None, [vp]),
     "cid_search_count": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp]),
     "cid_search_count_dev": (C.c_int, [vp, vp, vp, vp, C.c_size_t, vp, vp, vp, vp]),

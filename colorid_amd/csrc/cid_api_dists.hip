@@ -1,6 +1,10 @@
 // C ABI of libcolorid_hip.so, part 6: `colorid dists` — the pairwise allele distances of a cgMLST table: for two accessions the loci both
-// have a call at (compared) and those of them where the calls differ (differ).  Kernels: cid_dists.hip.
+// have a call at (compared) and those of them where the calls differ (differ), and the minimum spanning forest of the accessions under
+// them (cid_dists_best, cid_dists_forest).  Kernels: cid_dists.hip.
 #include "cid_api_common.hpp"
+
+#include <numeric>
+#include <vector>
 
 using cid::fail;
 
@@ -10,6 +14,61 @@ void dists_release(cid_dists *d) {
     if (d->mask_t) (void)hipFree(d->mask_t);
     delete d;
 }
+
+constexpr uint32_t kNone = 0xFFFFFFFFu;   // cid_dists_edge.b of an accession without a candidate
+static_assert(sizeof(cid_dists_edge) == 16, "cid_dists_edge is part of the ABI");
+
+// the packing limit of k_dists_best's key, refused before anything is launched
+int check_best_shape(const cid_dists *d) {
+    uint32_t sd, sc;
+    if (!cid::dists_best_shifts(d->n_acc, d->n_loci, &sd, &sc))
+        return fail(CID_ERR_UNSUPPORTED, "%u accessions x %u loci: 2 ceil(log2(loci + 1)) + ceil(log2 accessions) exceeds the 64 bits of a best-edge key",
+                    d->n_acc, d->n_loci);
+    return CID_OK;
+}
+
+// The device side of one Borůvka round and what stays between rounds: the labels' and the keys' device arrays.
+struct BestRound {
+    cid_dists *d;
+    uint32_t *d_comp = nullptr;
+    unsigned long long *d_best = nullptr;
+    uint32_t shift_differ = 0, shift_compared = 0;
+    explicit BestRound(cid_dists *dd) : d(dd) { (void)cid::dists_best_shifts(d->n_acc, d->n_loci, &shift_differ, &shift_compared); }
+    BestRound(const BestRound &) = delete;
+    BestRound &operator=(const BestRound &) = delete;
+    ~BestRound() {
+        if (d_comp) cid::ctx_free(d->ctx, d_comp);
+        if (d_best) cid::ctx_free(d->ctx, d_best);
+    }
+    int run(const uint32_t *comp, uint32_t min_compared, std::vector<unsigned long long> &keys) {
+        cid_ctx *c = d->ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        const size_t A = d->n_acc;
+        if (!d_comp) {
+            int rc = cid::ctx_alloc(c, A * 4, reinterpret_cast<void **>(&d_comp));
+            if (rc == CID_OK) rc = cid::ctx_alloc(c, A * 8, reinterpret_cast<void **>(&d_best));
+            if (rc != CID_OK) return rc;
+        }
+        keys.resize(A);
+        cid::DistsParams p{};
+        p.T = d->codes_t; p.maskT = d->mask_t; p.Ap = d->acc_pad; p.A = d->n_acc; p.L = d->n_loci; p.W = d->n_words;
+        cid::DistsBestParams b{};
+        b.comp = d_comp; b.best = d_best; b.min_compared = min_compared;
+        hipError_t e = hipMemcpyAsync(d_comp, comp, A * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = cid::launch_dists_best(p, b, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(keys.data(), d_best, A * 8, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t es = hipStreamSynchronize(c->stream);   // (also after a failed launch: comp and keys are the caller's)
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) return fail(CID_ERR_HIP, "cid_dists_best: %s", hipGetErrorString(e));
+        return CID_OK;
+    }
+    cid_dists_edge unpack(uint32_t i, unsigned long long key) const {
+        if (key == cid::kDistsNoBest) return cid_dists_edge{i, kNone, 0, 0};
+        const unsigned long long low = (1ull << shift_compared) - 1, mid = (1ull << (shift_differ - shift_compared)) - 1;
+        const uint32_t compared = d->n_loci - (uint32_t)((key >> shift_compared) & mid);
+        return cid_dists_edge{i, (uint32_t)(key & low), (uint32_t)(key >> shift_differ), compared};
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -107,6 +166,79 @@ int cid_dists_rows(cid_dists *d, uint32_t row0, uint32_t n_rows, uint32_t *diffe
     cid::ctx_free(c, d_differ);
     cid::ctx_free(c, d_compared);
     if (e != hipSuccess) return fail(CID_ERR_HIP, "cid_dists_rows: %s", hipGetErrorString(e));
+    return CID_OK;
+}
+
+// One round: the labels go up, best[] comes back packed and is unpacked here.  Device memory: 12 bytes an accession.
+int cid_dists_best(cid_dists *d, const uint32_t *comp, uint32_t min_compared, cid_dists_edge *best) {
+    if (!d || !comp || !best) return fail(CID_ERR_INVALID, "null argument");
+    if (min_compared == 0) return fail(CID_ERR_INVALID, "min_compared = 0: two accessions without a common locus are never an edge");
+    const int rc = check_best_shape(d);
+    if (rc != CID_OK) return rc;
+    BestRound round(d);
+    std::vector<unsigned long long> keys;
+    const int rr = round.run(comp, min_compared, keys);
+    if (rr != CID_OK) return rr;
+    for (uint32_t i = 0; i < d->n_acc; ++i) best[i] = round.unpack(i, keys[i]);
+    return CID_OK;
+}
+
+// Borůvka's algorithm with the per-component minimum and the merging on the host: a round is one cid_dists_best with the union-find's
+// roots as labels; every component then takes the least (by the edge key) of its members' best edges and is joined along it.  The key is
+// a strict total order, so the chosen edges close no cycle and an edge chosen from both ends joins its two components once.  Every round
+// that joins anything at least halves the components that still have an edge out, and one more round finds nothing: at most
+// floor(log2 A) + 1 rounds.  Device memory: 12 bytes an accession; host memory: 36.
+int cid_dists_forest(cid_dists *d, uint32_t min_compared, cid_dists_edge *edges, uint32_t *n_edges, uint32_t *n_rounds) {
+    if (!d || !n_edges || !n_rounds) return fail(CID_ERR_INVALID, "null argument");
+    *n_edges = *n_rounds = 0;
+    if (!edges && d->n_acc > 1) return fail(CID_ERR_INVALID, "null edges");
+    if (min_compared == 0) return fail(CID_ERR_INVALID, "min_compared = 0: two accessions without a common locus are never an edge");
+    const int rc = check_best_shape(d);
+    if (rc != CID_OK) return rc;
+    const uint32_t A = d->n_acc;
+    if (A == 1) return CID_OK;
+    BestRound round(d);
+    std::vector<uint32_t> parent(A), comp(A);
+    std::iota(parent.begin(), parent.end(), 0u);
+    auto find = [&](uint32_t x) {
+        while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
+        return x;
+    };
+    auto less = [](const cid_dists_edge &x, const cid_dists_edge &y) {   // the edge key
+        if (x.differ != y.differ) return x.differ < y.differ;
+        if (x.compared != y.compared) return x.compared > y.compared;
+        if (x.a != y.a) return x.a < y.a;
+        return x.b < y.b;
+    };
+    std::vector<unsigned long long> keys;
+    std::vector<cid_dists_edge> pick(A);   // per root the component's least edge of the round (b = none: nothing yet)
+    uint32_t n = 0;
+    while (n + 1 < A) {
+        for (uint32_t i = 0; i < A; ++i) comp[i] = find(i);
+        const int rr = round.run(comp.data(), min_compared, keys);
+        if (rr != CID_OK) return rr;
+        ++*n_rounds;
+        for (uint32_t i = 0; i < A; ++i) pick[i].b = kNone;
+        bool any = false;
+        for (uint32_t i = 0; i < A; ++i) {
+            cid_dists_edge e = round.unpack(i, keys[i]);
+            if (e.b == kNone) continue;
+            if (e.a > e.b) std::swap(e.a, e.b);
+            cid_dists_edge &p = pick[comp[i]];
+            if (p.b == kNone || less(e, p)) p = e;
+            any = true;
+        }
+        if (!any) break;
+        for (uint32_t r = 0; r < A; ++r) {
+            if (pick[r].b == kNone) continue;
+            const uint32_t x = find(pick[r].a), y = find(pick[r].b);
+            if (x == y) continue;   // the other end's component chose the same edge
+            parent[std::max(x, y)] = std::min(x, y);
+            edges[n++] = pick[r];
+        }
+    }
+    std::sort(edges, edges + n, less);
+    *n_edges = n;
     return CID_OK;
 }
 

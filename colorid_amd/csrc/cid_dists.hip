@@ -57,12 +57,13 @@ __global__ __launch_bounds__(kBlock) void k_dists_mask(const uint32_t *codes, ui
 // row accessions past A are staged as missing and never stored, column accessions past A read T's zero padding (tile tails).
 // compared[i][j] = popcount(mask_i & mask_j) over the W mask words, differ = compared - equal.
 // BOUND: equal <= compared <= L < 2^32.
-__global__ __launch_bounds__(kBlock) void k_dists_tile(DistsParams p) {
+// The walk is one body (dists_tile_walk) with two epilogues: k_dists_tile stores the counts, k_dists_best keeps a row's best pair.
+__device__ __forceinline__ void dists_tile_walk(const DistsParams &p, uint32_t ty, uint32_t tx, uint64_t row_base, uint64_t col_base,
+                                                uint32_t (&eq)[4][4], uint32_t (&cmp)[4][4]) {
     __shared__ __attribute__((aligned(16))) uint32_t s_row[kDistsChunk][kDistsTile];
     __shared__ __attribute__((aligned(16))) uint32_t s_col[kDistsChunk][kDistsTile];
-    const uint32_t t = threadIdx.x, tx = t & 15u, ty = t >> 4;
+    const uint32_t t = threadIdx.x;
     const uint32_t sx = t & 63u, sl = t >> 6;   // staging: wave sl takes the loci sl, sl + 4, .. of a chunk, lane sx the accession
-    const uint64_t col_base = (uint64_t)blockIdx.x * kDistsTile, row_base = (uint64_t)p.row0 + (uint64_t)blockIdx.y * kDistsTile;
     const bool row_ok = row_base + sx < p.A;
     constexpr uint32_t kPer = kDistsChunk / 4;
     uint32_t fr[kPer], fc[kPer];
@@ -74,7 +75,6 @@ __global__ __launch_bounds__(kBlock) void k_dists_tile(DistsParams p) {
             fc[i] = l < p.L ? p.T[(uint64_t)l * p.Ap + col_base + sx] : 0u;
         }
     };
-    uint32_t eq[4][4];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -100,7 +100,6 @@ __global__ __launch_bounds__(kBlock) void k_dists_tile(DistsParams p) {
                 for (int c = 0; c < 4; ++c) eq[r][c] += a[r] == b[c] ? 1u : 0u;
         }
     }
-    uint32_t cmp[4][4];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
@@ -120,6 +119,13 @@ __global__ __launch_bounds__(kBlock) void k_dists_tile(DistsParams p) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) cmp[r][c] += (uint32_t)__popcll(mi[r] & mj[c]);
     }
+}
+
+__global__ __launch_bounds__(kBlock) void k_dists_tile(DistsParams p) {
+    const uint32_t tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
+    const uint64_t col_base = (uint64_t)blockIdx.x * kDistsTile, row_base = (uint64_t)p.row0 + (uint64_t)blockIdx.y * kDistsTile;
+    uint32_t eq[4][4], cmp[4][4];
+    dists_tile_walk(p, ty, tx, row_base, col_base, eq, cmp);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const uint64_t local = (uint64_t)blockIdx.y * kDistsTile + 4u * ty + (uint32_t)r;   // the row within [row0, row0 + n_rows)
@@ -131,6 +137,49 @@ __global__ __launch_bounds__(kBlock) void k_dists_tile(DistsParams p) {
             p.differ[local * p.A + j] = cmp[r][c] - eq[r][c];
             if (p.compared) p.compared[local * p.A + j] = cmp[r][c];
         }
+    }
+}
+
+// One Borůvka round (cid_dists_best): the same walk, and instead of the store every row accession i keeps the best pair {i, j} over the
+// columns j of another component (b.comp[j] != b.comp[i], which also excludes j == i) that share at least b.min_compared loci with it.
+// Best = least (differ, L - compared, j): fewest differences, then most shared loci, then the lower accession — for a fixed i that is the
+// order of the edge key (differ, -compared, min(i, j), max(i, j)).  The three fields are packed into one u64,
+//     key = differ << (bits_l + bits_a) | (L - compared) << bits_a | j,     bits_l = bits of L, bits_a = bits of A - 1
+// (launch_dists_best refuses a shape whose 2 bits_l + bits_a exceed 64), so the least key is the best pair and a row's result is one
+// 64-bit minimum: over a thread's 4 columns in registers, over the row's 16 tx lanes — adjacent lanes of one wave — by four xor
+// shuffles, and over the A / 64 column tiles by one atomicMin of lane tx = 0 on b.best[i], which the caller has set to kDistsNoBest.
+// No pair gives that value: a candidate has compared >= 1, so its middle field is below L and its key below 2^64 - 1.  The atomic is
+// skipped when the word already holds less; it only ever decreases, so a stale read costs an atomic and never a result.
+// Tails: a row past A is never reported; a column past A has zero masks, compared = 0 < min_compared (>= 1), and is no candidate.
+__global__ __launch_bounds__(kBlock) void k_dists_best(DistsParams p, DistsBestParams b) {
+    const uint32_t tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
+    const uint64_t col_base = (uint64_t)blockIdx.x * kDistsTile, row_base = (uint64_t)p.row0 + (uint64_t)blockIdx.y * kDistsTile;
+    uint32_t eq[4][4], cmp[4][4];
+    dists_tile_walk(p, ty, tx, row_base, col_base, eq, cmp);
+    uint32_t cj[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const uint64_t j = col_base + 4u * tx + (uint32_t)c;
+        cj[c] = j < p.A ? b.comp[j] : 0u;   // (past A: compared = 0 keeps it out whatever the label)
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const uint64_t i = row_base + 4u * ty + (uint32_t)r;   // uniform over the 16 tx lanes of the row
+        const uint32_t ci = i < p.A ? b.comp[i] : 0u;
+        unsigned long long key = kDistsNoBest;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint64_t j = col_base + 4u * tx + (uint32_t)c;
+            const unsigned long long k = ((unsigned long long)(cmp[r][c] - eq[r][c]) << b.shift_differ) |
+                                         ((unsigned long long)(p.L - cmp[r][c]) << b.shift_compared) | j;
+            if (cmp[r][c] >= b.min_compared && cj[c] != ci && k < key) key = k;
+        }
+#pragma unroll
+        for (int m = 1; m < 16; m <<= 1) {
+            const unsigned long long o = __shfl_xor(key, m, 16);
+            key = o < key ? o : key;
+        }
+        if (tx == 0 && i < p.A && key < b.best[i]) atomicMin(&b.best[i], key);
     }
 }
 
@@ -157,6 +206,30 @@ hipError_t launch_dists_tile(const DistsParams &p, hipStream_t stream) {
     if (row_tiles > kDistsMaxRowTiles || (uint64_t)p.row0 + p.n_rows > p.A) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_dists_tile, dim3((unsigned)(p.Ap / kDistsTile), row_tiles), dim3(kBlock), 0, stream, p);
     return hipGetLastError();
+}
+
+bool dists_best_shifts(uint32_t A, uint32_t L, uint32_t *shift_differ, uint32_t *shift_compared) {
+    uint32_t bits_l = 0, bits_a = 0;
+    while (bits_l < 32 && (L >> bits_l)) ++bits_l;                       // ceil(log2(L + 1))
+    while (bits_a < 32 && A && ((A - 1) >> bits_a)) ++bits_a;            // ceil(log2 A)
+    *shift_compared = bits_a;
+    *shift_differ = bits_a + bits_l;
+    return 2 * bits_l + bits_a <= 64;
+}
+
+hipError_t launch_dists_best(DistsParams p, DistsBestParams b, hipStream_t stream) {
+    if (p.A == 0 || p.L == 0) return hipSuccess;
+    if (!dists_best_shifts(p.A, p.L, &b.shift_differ, &b.shift_compared) || b.min_compared == 0) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(b.best, 0xFF, 8ull * p.A, stream);
+    p.differ = p.compared = nullptr;
+    const uint64_t per = 64ull * kDistsMaxRowTiles;   // rows a launch
+    for (uint64_t r0 = 0; r0 < p.A && e == hipSuccess; r0 += per) {
+        p.row0 = (uint32_t)r0;
+        p.n_rows = (uint32_t)std::min<uint64_t>(per, p.A - r0);
+        hipLaunchKernelGGL(k_dists_best, dim3((unsigned)(p.Ap / kDistsTile), (p.n_rows + kDistsTile - 1) / kDistsTile), dim3(kBlock), 0, stream, p, b);
+        e = hipGetLastError();
+    }
+    return e;
 }
 
 }  // namespace cid

@@ -320,6 +320,18 @@ constexpr uint32_t kDistsMaxRowTiles = 65535;
 hipError_t launch_dists_put(const uint32_t *d_codes, uint32_t a0, uint32_t na, uint32_t L, uint32_t *T, unsigned long long *maskT, uint64_t Ap,
                             uint32_t *d_err, hipStream_t stream);
 hipError_t launch_dists_tile(const DistsParams &p, hipStream_t stream);
+// One Borůvka round over the same arrays (p's row0, n_rows, differ and compared are not read): for every accession i, best[i] = the least
+// key = differ << shift_differ | (L - compared) << shift_compared | j over the j with comp[j] != comp[i] and compared(i, j) >=
+// min_compared (>= 1), or kDistsNoBest.  launch_dists_best presets best and fills in the shifts; dists_best_shifts gives them for a shape
+// and says whether the key fits 64 bits: 2 ceil(log2(L + 1)) + ceil(log2 A) <= 64 (else the launcher returns hipErrorInvalidValue).
+struct DistsBestParams {
+    const uint32_t *comp;        // [A] component labels, any u32
+    unsigned long long *best;    // [A]
+    uint32_t min_compared, shift_differ, shift_compared;
+};
+constexpr unsigned long long kDistsNoBest = ~0ull;
+bool dists_best_shifts(uint32_t A, uint32_t L, uint32_t *shift_differ, uint32_t *shift_compared);
+hipError_t launch_dists_best(DistsParams p, DistsBestParams b, hipStream_t stream);
 hipError_t launch_get_rows(const uint64_t *mat, uint32_t rs, const uint64_t *d_row_ids, uint32_t *d_words, uint32_t w32,
                            uint64_t n_rows, hipStream_t stream);
 hipError_t launch_insert_kmers(const InsertParams &p, hipStream_t stream);

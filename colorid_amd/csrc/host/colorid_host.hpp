@@ -461,10 +461,16 @@ struct AlleleCodes {
 // the host never holds a whole matrix; with cluster also PREFIX.clusters.tsv: single linkage of the pairs with compared >= min_compared
 // (at least 1) and differ <= threshold, and every accession's nearest comparable neighbour.  ctx is not used (may be null) for a table
 // without accessions or without loci.  phase (may be null) is told when a part is done (COLORID_TIMING).  Says on stderr what it wrote.
+// With mst, after all that, PREFIX.mst.tsv and PREFIX.mst.nwk: the minimum spanning forest (cid_dists_forest: the pairs with compared >=
+// min_compared under the key differ, then more compared, then the earlier accessions) as an edge list in key order and as one Newick
+// line per tree, rooted at the tree's first accession, children in table order, branch length = differ.  With no_matrices the two A x A
+// files are not made: rows are fetched only for the clusters, and not at all without them.
 struct DistsOptions {
     bool cluster = false;
     uint64_t threshold = 0;      // --cluster T
-    uint64_t min_compared = 1;   // --min-compared M
+    uint64_t min_compared = 1;   // --min-compared M (for --cluster and --mst)
+    bool mst = false;            // --mst
+    bool no_matrices = false;    // --no-matrices (the caller refuses it without mst or cluster)
 };
 void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, const DistsOptions &opt, void (*phase)(const char *) = nullptr);
 

@@ -8,9 +8,15 @@
 //                accession (differ / compared), written row block by row block: the host never holds an A x A matrix
 //   PREFIX.clusters.tsv (--cluster T [--min-compared M])   i and j are linked when compared >= M (at least 1: a pair without a common locus
 //                never links) and differ <= T; clusters = connected components, numbered from 1 in order of their first member
+//   PREFIX.mst.tsv, PREFIX.mst.nwk (--mst [--min-compared M])   the minimum spanning forest of the graph whose edges are the pairs with
+//                compared >= M, under the key (differ, more compared first, earlier accessions first): cid_dists_forest, Borůvka rounds on
+//                the device, 8 bytes an accession a round over the bus.  Its edges with differ <= T span exactly the clusters at T.
+//   --no-matrices   the two A x A files are not made; rows are then fetched for --cluster only
 #include "colorid_host.hpp"
 
 #include <algorithm>
+#include <cctype>
+#include <cstring>
 #include <numeric>
 
 namespace colorid {
@@ -61,6 +67,83 @@ void append_row(std::string &line, const std::string &name, const uint32_t *v, s
         line.append(p, (size_t)(buf + sizeof buf - p));
     }
     line += '\n';
+}
+
+// A Newick label: bare, unless it is empty or holds whitespace or one of ( ) [ ] ' : ; , — then in single quotes, every ' doubled.
+void append_nwk_name(std::string &out, const std::string &name) {
+    bool quote = name.empty();
+    for (const char ch : name) quote |= isspace((unsigned char)ch) || strchr("()[]':;,", ch) != nullptr;
+    if (!quote) { out += name; return; }
+    out += '\'';
+    for (const char ch : name) { out += ch; if (ch == '\'') out += '\''; }
+    out += '\'';
+}
+
+// PREFIX.mst.tsv: the forest's edges (a < b, in edge-key order) by name.  PREFIX.mst.nwk: one line per tree in order of its first
+// accession, which is the root; a node is (child,child,..)name:differ with its children in table order, a leaf name:differ, the root
+// carries no length.  Written from an explicit stack: a chain of any length does not recurse.
+void write_forest(const std::vector<std::string> &names, const std::vector<cid_dists_edge> &edges, const std::string &prefix) {
+    const size_t A = names.size();
+    const std::string t_path = prefix + ".mst.tsv", n_path = prefix + ".mst.nwk";
+    FILE *ft = dists_out(t_path);
+    fputs("a\tb\tdiffer\tcompared\n", ft);
+    unsigned long long total = 0;
+    for (const cid_dists_edge &e : edges) {
+        fprintf(ft, "%s\t%s\t%u\t%u\n", names[e.a].c_str(), names[e.b].c_str(), e.differ, e.compared);
+        total += e.differ;
+    }
+    dists_close(ft, t_path);
+    // adjacency lists, one run per accession, sorted by the neighbour
+    struct Arc { uint32_t to, differ; };
+    std::vector<size_t> first(A + 1, 0);
+    for (const cid_dists_edge &e : edges) { ++first[e.a + 1]; ++first[e.b + 1]; }
+    for (size_t i = 0; i < A; ++i) first[i + 1] += first[i];
+    std::vector<Arc> arcs(2 * edges.size());
+    {
+        std::vector<size_t> fill(first.begin(), first.end() - 1);
+        for (const cid_dists_edge &e : edges) {
+            arcs[fill[e.a]++] = Arc{e.b, e.differ};
+            arcs[fill[e.b]++] = Arc{e.a, e.differ};
+        }
+    }
+    for (size_t i = 0; i < A; ++i)
+        std::sort(arcs.begin() + (ptrdiff_t)first[i], arcs.begin() + (ptrdiff_t)first[i + 1], [](const Arc &x, const Arc &y) { return x.to < y.to; });
+    FILE *fn = dists_out(n_path);
+    struct Frame { uint32_t node, up, differ; size_t next; bool opened; };   // up: the parent (the node itself at the root); next: the arc to look at
+    std::vector<bool> seen(A, false);
+    std::vector<Frame> stack;
+    std::string line;
+    char num[16];
+    for (size_t root = 0; root < A; ++root) {
+        if (seen[root]) continue;
+        line.clear();
+        stack.push_back(Frame{(uint32_t)root, (uint32_t)root, 0, first[root], false});
+        while (!stack.empty()) {
+            Frame &f = stack.back();
+            seen[f.node] = true;
+            while (f.next < first[f.node + 1] && arcs[f.next].to == f.up && f.up != f.node) ++f.next;   // not back up the tree
+            if (f.next < first[f.node + 1]) {
+                line += f.opened ? ',' : '(';
+                f.opened = true;
+                const Arc a = arcs[f.next++];
+                const uint32_t node = f.node;
+                stack.push_back(Frame{a.to, node, a.differ, first[a.to], false});   // (f is not used past this line)
+                continue;
+            }
+            if (f.opened) line += ')';
+            append_nwk_name(line, names[f.node]);
+            if (f.up != f.node) {
+                snprintf(num, sizeof num, ":%u", f.differ);
+                line += num;
+            }
+            stack.pop_back();
+        }
+        line += ";\n";
+        fwrite(line.data(), 1, line.size(), fn);
+    }
+    dists_close(fn, n_path);
+    fprintf(stderr, "dists: minimum spanning forest: %zu trees, %zu edges, total length %llu, written to %s, %s\n", A - edges.size(), edges.size(),
+            total, t_path.c_str(), n_path.c_str());
 }
 
 }  // namespace
@@ -142,13 +225,18 @@ AlleleCodes AlleleCodes::from_file(const std::string &path) {
 void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, const DistsOptions &opt, void (*phase)(const char *)) {
     const size_t A = t.accessions.size(), L = t.loci.size();
     const std::string d_path = prefix + ".dists.tsv", c_path = prefix + ".compared.tsv", k_path = prefix + ".clusters.tsv";
-    FILE *fd = dists_out(d_path), *fc = dists_out(c_path);
-    std::string header;
-    for (const std::string &a : t.accessions) { header += '\t'; header += a; }
-    if (A == 0) header += '\t';   // the raw table's convention for a header without columns
-    header += '\n';
-    fputs(header.c_str(), fd);
-    fputs(header.c_str(), fc);
+    const bool matrices = !opt.no_matrices;
+    FILE *fd = nullptr, *fc = nullptr;
+    if (matrices) {
+        fd = dists_out(d_path);
+        fc = dists_out(c_path);
+        std::string header;
+        for (const std::string &a : t.accessions) { header += '\t'; header += a; }
+        if (A == 0) header += '\t';   // the raw table's convention for a header without columns
+        header += '\n';
+        fputs(header.c_str(), fd);
+        fputs(header.c_str(), fc);
+    }
     const uint64_t min_compared = std::max<uint64_t>(opt.min_compared, 1);
     // clustering state, fed row by row: union-find over the links, and per accession its nearest comparable neighbour
     std::vector<uint32_t> parent(opt.cluster ? A : 0);
@@ -174,29 +262,31 @@ void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, co
         nearest[i] = best;
     };
     std::string line;
+    cid_dists *d = nullptr;
     if (A && L) {
-        cid_dists *d = nullptr;
         if (cid_dists_create(ctx, t.codes.data(), (uint32_t)A, (uint32_t)L, &d) != CID_OK) die("cid_dists_create: %s", cid_last_error());
         if (phase) phase("allele codes uploaded");
-        // row blocks of whole 64-row tiles, about 32 MiB per matrix
+        // row blocks of whole 64-row tiles, about 32 MiB per matrix; without the matrices only the clusters read rows
         size_t block = std::max<size_t>(64, ((32u << 20) / (A * 4)) & ~(size_t)63);
         block = std::min(block, A);
+        if (!matrices && !opt.cluster) block = 0;
         std::vector<uint32_t> differ(block * A), compared(block * A);
-        for (size_t r0 = 0; r0 < A; r0 += block) {
+        for (size_t r0 = 0; r0 < A && block; r0 += block) {
             const size_t nr = std::min(block, A - r0);
             if (cid_dists_rows(d, (uint32_t)r0, (uint32_t)nr, differ.data(), compared.data()) != CID_OK) die("cid_dists_rows: %s", cid_last_error());
             for (size_t r = 0; r < nr; ++r) {
-                line.clear();
-                append_row(line, t.accessions[r0 + r], &differ[r * A], A);
-                fwrite(line.data(), 1, line.size(), fd);
-                line.clear();
-                append_row(line, t.accessions[r0 + r], &compared[r * A], A);
-                fwrite(line.data(), 1, line.size(), fc);
+                if (matrices) {
+                    line.clear();
+                    append_row(line, t.accessions[r0 + r], &differ[r * A], A);
+                    fwrite(line.data(), 1, line.size(), fd);
+                    line.clear();
+                    append_row(line, t.accessions[r0 + r], &compared[r * A], A);
+                    fwrite(line.data(), 1, line.size(), fc);
+                }
                 if (opt.cluster) feed(r0 + r, &differ[r * A], &compared[r * A]);
             }
         }
-        cid_dists_destroy(d);
-    } else {   // no accession or no locus: nothing is compared anywhere, every cell is 0
+    } else if (matrices) {   // no accession or no locus: nothing is compared anywhere, every cell is 0
         const std::vector<uint32_t> zero(A, 0);
         for (size_t i = 0; i < A; ++i) {
             line.clear();
@@ -205,31 +295,49 @@ void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, co
             fwrite(line.data(), 1, line.size(), fc);
         }
     }
-    dists_close(fd, d_path);
-    dists_close(fc, c_path);
-    if (phase) phase("distances computed and written");
-    fprintf(stderr, "dists: %zu accessions x %zu loci written to %s, %s\n", A, L, d_path.c_str(), c_path.c_str());
-    if (!opt.cluster) return;
-    std::vector<uint32_t> size(A, 0), number(A, 0);
-    for (size_t i = 0; i < A; ++i) ++size[find((uint32_t)i)];
-    size_t n_multi = 0, in_multi = 0;
-    uint32_t next = 0;
-    FILE *fk = dists_out(k_path);
-    fputs("accession\tcluster\tsize\tnearest\tdiffer\tcompared\n", fk);
-    for (size_t i = 0; i < A; ++i) {
-        const uint32_t root = find((uint32_t)i);
-        if (!number[root]) {   // (the root is the component's first member: unions keep the smaller index)
-            number[root] = ++next;
-            if (size[root] >= 2) { ++n_multi; in_multi += size[root]; }
-        }
-        const Near &nb = nearest[i];
-        if (nb.j == kNone) fprintf(fk, "%s\t%u\t%u\t-\t-\t-\n", t.accessions[i].c_str(), number[root], size[root]);
-        else fprintf(fk, "%s\t%u\t%u\t%s\t%u\t%u\n", t.accessions[i].c_str(), number[root], size[root], t.accessions[nb.j].c_str(), nb.differ, nb.compared);
+    if (matrices) {
+        dists_close(fd, d_path);
+        dists_close(fc, c_path);
+        if (phase) phase("distances computed and written");
+        fprintf(stderr, "dists: %zu accessions x %zu loci written to %s, %s\n", A, L, d_path.c_str(), c_path.c_str());
+    } else {
+        if (phase) phase("distances computed");
+        fprintf(stderr, "dists: %zu accessions x %zu loci, matrices not written (--no-matrices)\n", A, L);
     }
-    dists_close(fk, k_path);
-    if (phase) phase("clusters written");
-    fprintf(stderr, "dists: %zu clusters of 2 or more at <= %llu differing loci hold %zu accessions, written to %s\n", n_multi,
-            (unsigned long long)opt.threshold, in_multi, k_path.c_str());
+    if (opt.cluster) {
+        std::vector<uint32_t> size(A, 0), number(A, 0);
+        for (size_t i = 0; i < A; ++i) ++size[find((uint32_t)i)];
+        size_t n_multi = 0, in_multi = 0;
+        uint32_t next = 0;
+        FILE *fk = dists_out(k_path);
+        fputs("accession\tcluster\tsize\tnearest\tdiffer\tcompared\n", fk);
+        for (size_t i = 0; i < A; ++i) {
+            const uint32_t root = find((uint32_t)i);
+            if (!number[root]) {   // (the root is the component's first member: unions keep the smaller index)
+                number[root] = ++next;
+                if (size[root] >= 2) { ++n_multi; in_multi += size[root]; }
+            }
+            const Near &nb = nearest[i];
+            if (nb.j == kNone) fprintf(fk, "%s\t%u\t%u\t-\t-\t-\n", t.accessions[i].c_str(), number[root], size[root]);
+            else fprintf(fk, "%s\t%u\t%u\t%s\t%u\t%u\n", t.accessions[i].c_str(), number[root], size[root], t.accessions[nb.j].c_str(), nb.differ, nb.compared);
+        }
+        dists_close(fk, k_path);
+        if (phase) phase("clusters written");
+        fprintf(stderr, "dists: %zu clusters of 2 or more at <= %llu differing loci hold %zu accessions, written to %s\n", n_multi,
+                (unsigned long long)opt.threshold, in_multi, k_path.c_str());
+    }
+    if (opt.mst) {
+        // (more than L shared loci are asked of no pair: the forest is then A single accessions, as it is without a locus)
+        std::vector<cid_dists_edge> edges(d && min_compared <= L ? A - 1 : 0);
+        if (!edges.empty()) {
+            uint32_t n_edges = 0, n_rounds = 0;
+            if (cid_dists_forest(d, (uint32_t)min_compared, edges.data(), &n_edges, &n_rounds) != CID_OK) die("cid_dists_forest: %s", cid_last_error());
+            edges.resize(n_edges);
+        }
+        write_forest(t.accessions, edges, prefix);
+        if (phase) phase("minimum spanning forest computed and written");
+    }
+    if (d) cid_dists_destroy(d);
 }
 
 }  // namespace colorid

@@ -642,11 +642,16 @@ uint64_t loci_arg(const Args &a, const char *key) {
     if (v.empty() || *end || n < 0 || errno) die("error: --%s expects a number of loci (0 or more), got '%s'", key, v.c_str());
     return (uint64_t)n;
 }
-// what --cluster and --min-compared ask for; refuses --min-compared without --cluster
+// what --cluster, --min-compared, --mst and --no-matrices ask for; refuses --min-compared without --cluster or --mst, and --no-matrices
+// when nothing else would be written
 DistsOptions dists_options(const Args &a) {
     DistsOptions o;
-    if (a.has("min-compared") && !a.has("cluster"))
-        die("error: --min-compared needs --cluster T (it is the least number of loci two accessions must share to be linked)");
+    o.mst = a.flags.count("mst") != 0;
+    o.no_matrices = a.flags.count("no-matrices") != 0;
+    if (a.has("min-compared") && !a.has("cluster") && !o.mst)
+        die("error: --min-compared needs --cluster T (it is the least number of loci two accessions must share to be linked) or --mst");
+    if (o.no_matrices && !a.has("cluster") && !o.mst)
+        die("error: --no-matrices needs --mst or --cluster T (without the two matrices nothing would be written)");
     if (a.has("cluster")) { o.cluster = true; o.threshold = loci_arg(a, "cluster"); }
     if (a.has("min-compared")) o.min_compared = loci_arg(a, "min-compared");
     return o;
@@ -670,6 +675,7 @@ int cmd_search(int argc, char **argv) {
                                                      {0, "alleles", true, false}, {0, "max-missing", true, false},
                                                      {0, "nearest", false, false}, {0, "dists", false, false},
                                                      {0, "cluster", true, false}, {0, "min-compared", true, false},
+                                                     {0, "mst", false, false}, {0, "no-matrices", false, false},
                                                      {0, "gather", true, false}, {0, "gather-min", true, false}, {0, "gather-max", true, false}}));
     for (const char *req : {"bigsi", "query"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
@@ -710,12 +716,14 @@ int cmd_search(int argc, char **argv) {
         if (a.has("gpus") || a.has("devices") || a.has("placement") || cli_env("COLORID_REDUCE"))
             die("error: --nearest runs on one GPU: it does not go with --gpus, --devices, --placement or COLORID_REDUCE");
     }
-    // -s -m --alleles PREFIX --dists [--cluster T [--min-compared M]]: after the tables, the pairwise allele distances of the raw table's
-    // accessions (the clean table's with --max-missing) and their clusters, on this run's context: the files `colorid dists -t
-    // PREFIX.raw.tsv` writes.  Refused here, before the GPU context is made
+    // -s -m --alleles PREFIX --dists [--cluster T] [--mst] [--min-compared M] [--no-matrices]: after the tables, the pairwise allele
+    // distances of the raw table's accessions (the clean table's with --max-missing), their clusters and their minimum spanning forest,
+    // on this run's context: the files `colorid dists -t PREFIX.raw.tsv` writes.  Refused here, before the GPU context is made
     const bool dists = a.flags.count("dists") != 0;
     if (dists && !a.has("alleles")) die("error: --dists needs -s -m --alleles PREFIX (it writes PREFIX.dists.tsv from the allele table)");
     if (!dists && a.has("cluster")) die("error: --cluster needs --dists (it clusters the allele distances)");
+    if (!dists && a.flags.count("mst")) die("error: --mst needs --dists (it is the minimum spanning forest of the allele distances)");
+    if (!dists && a.flags.count("no-matrices")) die("error: --no-matrices needs --dists (it leaves out PREFIX.dists.tsv and PREFIX.compared.tsv)");
     const DistsOptions dists_opt = dists_options(a);
     // -g -m --coverage: where on each record an accession hits (cid_search_cover).  FASTA records on one GPU; everything else is refused
     // here, before the GPU context is made
@@ -812,12 +820,14 @@ int cmd_alleles(int argc, char **argv) {
     return 0;
 }
 
-// dists: -t TABLE -o PREFIX [--cluster T [--min-compared M]] — PREFIX.dists.tsv and PREFIX.compared.tsv (and PREFIX.clusters.tsv) from
-// a table in the form of PREFIX.raw.tsv / PREFIX.clean.tsv.  The table is read and checked before the GPU is opened; a table without
-// accessions or without loci needs none.
+// dists: -t TABLE -o PREFIX [--cluster T] [--mst] [--min-compared M] [--no-matrices] — PREFIX.dists.tsv and PREFIX.compared.tsv (and
+// PREFIX.clusters.tsv; PREFIX.mst.tsv and PREFIX.mst.nwk) from a table in the form of PREFIX.raw.tsv / PREFIX.clean.tsv.  The flags are
+// checked before the table is read, the table is read and checked before the GPU is opened; a table without accessions or without loci
+// needs none.
 int cmd_dists(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, {{'t', "table", true, false}, {'o', "output", true, false}, {0, "cluster", true, false},
-                                         {0, "min-compared", true, false}, {0, "device", true, false}});
+                                         {0, "min-compared", true, false}, {0, "mst", false, false}, {0, "no-matrices", false, false},
+                                         {0, "device", true, false}});
     for (const char *req : {"table", "output"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const DistsOptions opt = dists_options(a);
@@ -1137,7 +1147,13 @@ int main(int argc, char **argv) {
                "                             PREFIX.compared.tsv: for every two accessions of the raw table (of the clean one with --max-missing)\n"
                "                             the loci where both have an allele and the alleles differ / where both have one; --cluster T:\n"
                "                             PREFIX.clusters.tsv, single linkage of the pairs at most T loci apart that share at least M (1)\n"
-               "    dists -t TABLE -o PREFIX [--cluster T [--min-compared M]]   the same files from a table in the form of PREFIX.raw.tsv\n"
+               "                             --dists --mst [--min-compared M]: PREFIX.mst.tsv and PREFIX.mst.nwk, the minimum spanning forest over\n"
+               "                             the pairs that share at least M (1) loci: fewest differing loci first, then most shared loci, then\n"
+               "                             the earlier accessions; edges a, b, differ, compared and one Newick line per tree (branch length =\n"
+               "                             differing loci); its edges of at most T are the clusters of --cluster T.  --no-matrices (with --mst\n"
+               "                             or --cluster): PREFIX.dists.tsv and PREFIX.compared.tsv are not written\n"
+               "    dists -t TABLE -o PREFIX [--cluster T] [--mst] [--min-compared M] [--no-matrices]   the same files from a table in the form\n"
+               "                             of PREFIX.raw.tsv\n"
                "    alleles -r ROWS -o PREFIX [--max-missing N]   the same tables from the saved stdout of a `search -s -m` run; no GPU\n\n"
                "INDEX MAINTENANCE:\n"
                "    collapse -b OUT -i idx.bxi -g groups.tsv      several accessions as one colour (groups.tsv: accession TAB group per line;\n"

@@ -428,6 +428,23 @@ class Dists:
         check(self.lib.cid_dists_rows(self.h, row0, n_rows, _p(differ), _p(comp)))
         return differ, comp
 
+    def best(self, comp, min_compared=1):
+        """one Borůvka round (cid_dists_best): comp = n_acc uint32 component labels -> (b, differ, compared), each n_acc uint32; b[i] is
+        the other end of accession i's least edge into another component, 0xFFFFFFFF when there is none"""
+        comp = np.ascontiguousarray(comp, np.uint32)
+        assert comp.shape == (self.n_acc,)
+        out = np.zeros((self.n_acc, 4), np.uint32)      # cid_dists_edge: a, b, differ, compared
+        check(self.lib.cid_dists_best(self.h, _p(comp), min_compared, _p(out)))
+        assert np.array_equal(out[:, 0], np.arange(self.n_acc, dtype=np.uint32))
+        return out[:, 1].copy(), out[:, 2].copy(), out[:, 3].copy()
+
+    def forest(self, min_compared=1):
+        """the minimum spanning forest (cid_dists_forest) -> (edges[n, 4] uint32: lo, hi, differ, compared in edge-key order, n_rounds)"""
+        out = np.zeros((max(self.n_acc - 1, 1), 4), np.uint32)
+        n, rounds = C.c_uint32(0), C.c_uint32(0)
+        check(self.lib.cid_dists_forest(self.h, min_compared, _p(out), C.byref(n), C.byref(rounds)))
+        return out[:n.value].copy(), rounds.value
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.cid_dists_destroy(self.h)

@@ -208,6 +208,25 @@ int cid_dists_create(cid_ctx *, const uint32_t *codes, uint32_t n_acc, uint32_t 
  * compared may be NULL.  n_rows == 0 is a no-op; row0 + n_rows > n_acc is CID_ERR_INVALID.  A block whose results exceed the ctx's
  * "dense_report_bytes" is cut into slices of at least one row inside the call. */
 int cid_dists_rows(cid_dists *, uint32_t row0, uint32_t n_rows, uint32_t *differ, uint32_t *compared);
+/* The minimum spanning forest of the table (`dists --mst`).  Graph: the accessions; {i, j}, i != j, is an edge iff compared(i, j) >=
+ * min_compared (>= 1: a pair without a common locus is never an edge).  Edge key, a strict total order: differ ascending, then compared
+ * DESCENDING, then min(i, j), then max(i, j).  The forest is the one Kruskal's algorithm gives over the edges sorted by that key; it is
+ * unique and does not depend on how the device splits the work.  Cutting it at differ <= T leaves the single-linkage clusters at T.
+ * cid_dists_best — one Borůvka round: comp[i] is accession i's component label (any u32); best[i] = {a = i, b = j, differ, compared} for
+ *   the edge {i, j} of least key over the j with comp[j] != comp[i] and compared(i, j) >= min_compared, or b = 0xFFFFFFFF and differ =
+ *   compared = 0 when there is none.  With every accession its own component this is its nearest comparable neighbour.
+ * cid_dists_forest — the whole forest: edges (room for n_acc - 1; may be NULL when n_acc == 1) receives *n_edges = n_acc - (number of
+ *   trees) edges with a < b, sorted by the edge key; *n_rounds = the rounds run, at most ceil(log2 n_acc) + 1 (0 when n_acc == 1).
+ * Every pair is visited on the device in every round and only 8 bytes an accession come back: no A x A matrix exists anywhere, device
+ * memory beside the table is 12 bytes an accession.
+ * LIMIT: a round packs (differ, n_loci - compared, j) into one 64-bit key, so 2 * ceil(log2(n_loci + 1)) + ceil(log2 n_acc) must be <= 64
+ * (any table of fewer than 2^20 loci x 2^24 accessions, or fewer than 2^24 loci x 2^16 accessions, is served); beyond it both calls return
+ * CID_ERR_UNSUPPORTED before anything is launched.  CID_ERR_INVALID: a null argument, min_compared == 0. */
+typedef struct cid_dists_edge {
+    uint32_t a, b, differ, compared;
+} cid_dists_edge;
+int cid_dists_best(cid_dists *, const uint32_t *comp, uint32_t min_compared, cid_dists_edge *best);
+int cid_dists_forest(cid_dists *, uint32_t min_compared, cid_dists_edge *edges, uint32_t *n_edges, uint32_t *n_rounds);
 void cid_dists_destroy(cid_dists *);
 
 /* ---- a5: proportional search, the hot loop of batch_search_pe::batch_search

@@ -1,7 +1,11 @@
 // Stand-alone host check of colorid_amd/csrc/host/dists.cpp under ASan + UBSan, no GPU and no libcolorid_hip.so: the table parser, the
-// allele encoder (both entrances), the row-block driver and the clustering, with a plain C++ cid_dists_* behind them.
-//   make -C tools bin/dists_host_check ;  tools/bin/dists_host_check TABLE PREFIX [T [M]]     (writes PREFIX.dists.tsv, .compared.tsv, .clusters.tsv)
+// allele encoder (both entrances), the row-block driver, the clustering and the forest and Newick writers, with a plain C++ cid_dists_*
+// behind them (the forest: Kruskal over the stand-in's own loop).
+//   make -C tools bin/dists_host_check ;  tools/bin/dists_host_check TABLE PREFIX [T [M [mst [no-matrices]]]]
+//   (writes PREFIX.dists.tsv, .compared.tsv, .clusters.tsv; T = - for no clusters; with mst also PREFIX.mst.tsv, .mst.nwk)
+#include <algorithm>
 #include <cstdarg>
+#include <numeric>
 #include "../colorid_amd/csrc/host/colorid_host.hpp"
 
 namespace colorid {
@@ -36,6 +40,50 @@ int cid_dists_rows(cid_dists *d, uint32_t row0, uint32_t n, uint32_t *differ, ui
         }
     return 0;
 }
+// the least edge of every accession into another label, by the loop above
+int cid_dists_best(cid_dists *d, const uint32_t *comp, uint32_t min_compared, cid_dists_edge *best) {
+    std::vector<uint32_t> differ(d->A), compared(d->A);
+    for (uint32_t i = 0; i < d->A; ++i) {
+        cid_dists_rows(d, i, 1, differ.data(), compared.data());
+        best[i] = cid_dists_edge{i, 0xFFFFFFFFu, 0, 0};
+        for (uint32_t j = 0; j < d->A; ++j) {
+            if (comp[j] == comp[i] || compared[j] < min_compared) continue;
+            if (best[i].b == 0xFFFFFFFFu || differ[j] < best[i].differ || (differ[j] == best[i].differ && compared[j] > best[i].compared))
+                best[i] = cid_dists_edge{i, j, differ[j], compared[j]};
+        }
+    }
+    return 0;
+}
+// Kruskal: every pair with compared >= min_compared, sorted by the edge key
+int cid_dists_forest(cid_dists *d, uint32_t min_compared, cid_dists_edge *edges, uint32_t *n_edges, uint32_t *n_rounds) {
+    std::vector<cid_dists_edge> all;
+    std::vector<uint32_t> differ(d->A), compared(d->A);
+    for (uint32_t i = 0; i < d->A; ++i) {
+        cid_dists_rows(d, i, 1, differ.data(), compared.data());
+        for (uint32_t j = i + 1; j < d->A; ++j)
+            if (compared[j] >= min_compared) all.push_back(cid_dists_edge{i, j, differ[j], compared[j]});
+    }
+    std::sort(all.begin(), all.end(), [](const cid_dists_edge &x, const cid_dists_edge &y) {
+        if (x.differ != y.differ) return x.differ < y.differ;
+        if (x.compared != y.compared) return x.compared > y.compared;
+        return x.a != y.a ? x.a < y.a : x.b < y.b;
+    });
+    std::vector<uint32_t> parent(d->A);
+    std::iota(parent.begin(), parent.end(), 0u);
+    auto find = [&](uint32_t x) {
+        while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
+        return x;
+    };
+    *n_edges = 0;
+    for (const cid_dists_edge &e : all) {
+        const uint32_t a = find(e.a), b = find(e.b);
+        if (a == b) continue;
+        parent[std::max(a, b)] = std::min(a, b);
+        edges[(*n_edges)++] = e;
+    }
+    *n_rounds = 1;
+    return 0;
+}
 void cid_dists_destroy(cid_dists *d) { delete d; }
 }
 
@@ -43,8 +91,10 @@ int main(int argc, char **argv) {
     using namespace colorid;
     if (argc < 3) return 2;
     DistsOptions o;
-    if (argc > 3) { o.cluster = true; o.threshold = strtoull(argv[3], nullptr, 10); }
+    if (argc > 3 && strcmp(argv[3], "-") != 0) { o.cluster = true; o.threshold = strtoull(argv[3], nullptr, 10); }
     if (argc > 4) o.min_compared = strtoull(argv[4], nullptr, 10);
+    o.mst = argc > 5;
+    o.no_matrices = argc > 6;
     const AlleleCodes t = AlleleCodes::from_file(argv[1]);
     dists_run(nullptr, t, argv[2], o);
     // the in-memory entrance over the same cells
