@@ -1,6 +1,6 @@
 // C ABI of libcolorid_hip.so, part 6: `colorid dists` — the pairwise allele distances of a cgMLST table: for two accessions the loci both
 // have a call at (compared) and those of them where the calls differ (differ), and the minimum spanning forest of the accessions under
-// them (cid_dists_best, cid_dists_forest).  Kernels: cid_dists.hip.
+// them (cid_dists_best, cid_dists_forest), and the pairs within a threshold as a list (cid_dists_within).  Kernels: cid_dists.hip.
 #include "cid_api_common.hpp"
 
 #include <numeric>
@@ -14,6 +14,22 @@ void dists_release(cid_dists *d) {
     if (d->mask_t) (void)hipFree(d->mask_t);
     delete d;
 }
+
+// a block of the ctx's cache for the length of a call
+template <typename T>
+struct Scratch {
+    cid_ctx *c;
+    T *p = nullptr;
+    explicit Scratch(cid_ctx *ctx) : c(ctx) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch() { if (p) cid::ctx_free(c, p); }
+    int alloc(size_t n) {   // (again: the block before goes back first)
+        if (p) cid::ctx_free(c, p);
+        p = nullptr;
+        return cid::ctx_alloc(c, n * sizeof(T), reinterpret_cast<void **>(&p));
+    }
+};
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;   // cid_dists_edge.b of an accession without a candidate
 static_assert(sizeof(cid_dists_edge) == 16, "cid_dists_edge is part of the ABI");
@@ -239,6 +255,97 @@ int cid_dists_forest(cid_dists *d, uint32_t min_compared, cid_dists_edge *edges,
     }
     std::sort(edges, edges + n, less);
     *n_edges = n;
+    return CID_OK;
+}
+
+// The neighbour list.  Device memory: one list of dense_report_bytes / 16 entries (no more than the rows can give, nor than the caller
+// has room for) and 8 bytes of cursor, both from the ctx's block cache.  The rows go out in slices of whole 64-row tiles, first as many
+// as a launch may hold; after each launch the cursor is read (8 bytes, one stream wait) and says exactly how many entries the slice has.
+// They fit the list: that many are copied to out and sorted there by (a, b) — slices are disjoint in a and taken in row order, so the
+// whole is sorted.  They do not: a slice of several tiles is halved and both halves run; a slice of one tile runs again with a list
+// grown to its count (at most 64 x n_acc entries: the "at least one row a slice" exemption of cid_dists_rows).  Once the caller's cap is
+// exceeded nothing more is stored and the remaining slices are only counted (capacity 0: one launch each, never a re-run).
+int cid_dists_within(cid_dists *d, uint32_t row0, uint32_t n_rows, uint32_t max_differ, uint32_t min_compared, uint32_t flags,
+                     cid_dists_edge *out, size_t cap, uint64_t *n_found) {
+    if (!d || !n_found) return fail(CID_ERR_INVALID, "null argument");
+    *n_found = 0;
+    if (min_compared == 0) return fail(CID_ERR_INVALID, "min_compared = 0: two accessions without a common locus are never within a distance");
+    if ((uint64_t)row0 + n_rows > d->n_acc)
+        return fail(CID_ERR_INVALID, "rows [%u, %llu) of a table of %u accessions", row0, (unsigned long long)row0 + n_rows, d->n_acc);
+    if (flags & ~CID_DISTS_UPPER) return fail(CID_ERR_INVALID, "unknown flags 0x%x", flags & ~CID_DISTS_UPPER);
+    if (!out && cap) return fail(CID_ERR_INVALID, "null out with room for %zu entries", cap);
+    if (n_rows == 0) return CID_OK;
+    cid_ctx *c = d->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t possible = (uint64_t)n_rows * (d->n_acc - 1);
+    uint64_t list_cap = std::min<uint64_t>({std::max<uint64_t>(c->tune.dense_report_bytes / sizeof(cid_dists_edge), 1), possible, cap});
+    Scratch<uint4> list(c), grown(c);
+    Scratch<unsigned long long> cursor(c);
+    int rc = cursor.alloc(1);
+    if (rc == CID_OK && list_cap) rc = list.alloc(list_cap);
+    if (rc != CID_OK) return rc;
+    cid::DistsParams p{};
+    p.T = d->codes_t; p.maskT = d->mask_t; p.Ap = d->acc_pad; p.A = d->n_acc; p.L = d->n_loci; p.W = d->n_words;
+    cid::DistsWithinParams w{};
+    w.cursor = cursor.p; w.max_differ = max_differ; w.min_compared = min_compared; w.upper = flags & CID_DISTS_UPPER;
+    struct Slice { uint32_t tile0, n_tiles; };   // tiles of 64 rows counted from row0
+    const uint32_t tiles = (uint32_t)(((uint64_t)n_rows + 63u) / 64u);
+    std::vector<Slice> todo;                      // a stack: the lowest rows on top
+    for (uint32_t t0 = tiles; t0 > 0;) {
+        const uint32_t n = t0 % cid::kDistsMaxRowTiles ? t0 % cid::kDistsMaxRowTiles : cid::kDistsMaxRowTiles;
+        t0 -= n;
+        todo.push_back(Slice{t0, n});
+    }
+    uint64_t total = 0, written = 0;
+    bool storing = cap != 0;
+    hipError_t e = hipSuccess;
+    // one launch: the slice's hits into `into` (room for `room`), *count = how many there are
+    auto run = [&](const Slice &s, uint4 *into, uint64_t room, unsigned long long *count) {
+        p.row0 = row0 + s.tile0 * 64u;
+        p.n_rows = (uint32_t)std::min<uint64_t>((uint64_t)s.n_tiles * 64u, n_rows - (uint64_t)s.tile0 * 64u);
+        w.list = into; w.cap = room;
+        hipError_t er = hipMemsetAsync(cursor.p, 0, 8, c->stream);
+        if (er == hipSuccess) er = cid::launch_dists_within(p, w, c->stream);
+        if (er == hipSuccess) er = hipMemcpyAsync(count, cursor.p, 8, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t es = hipStreamSynchronize(c->stream);   // (also after a failed launch: count is this frame's)
+        return er == hipSuccess ? es : er;
+    };
+    auto take = [&](const uint4 *from, uint64_t n) {   // a slice's entries: to the caller, sorted
+        hipError_t er = hipMemcpyAsync(out + written, from, n * sizeof(cid_dists_edge), hipMemcpyDeviceToHost, c->stream);
+        const hipError_t es = hipStreamSynchronize(c->stream);   // the list is the next slice's
+        if (er == hipSuccess) er = es;
+        if (er != hipSuccess) return er;
+        std::sort(out + written, out + written + n, [](const cid_dists_edge &x, const cid_dists_edge &y) { return x.a != y.a ? x.a < y.a : x.b < y.b; });
+        written += n;
+        return hipSuccess;
+    };
+    while (!todo.empty() && e == hipSuccess) {
+        const Slice s = todo.back();
+        todo.pop_back();
+        unsigned long long count = 0;
+        e = run(s, storing ? list.p : nullptr, storing ? list_cap : 0, &count);
+        if (e != hipSuccess) break;
+        if (storing && written + count > cap) storing = false;   // the caller comes back with room: the rest is counted
+        if (!storing || count == 0) { total += count; continue; }
+        if (count <= list_cap) {
+            total += count;
+            e = take(list.p, count);
+        } else if (s.n_tiles > 1) {
+            const uint32_t half = s.n_tiles / 2;
+            todo.push_back(Slice{s.tile0 + half, s.n_tiles - half});
+            todo.push_back(Slice{s.tile0, half});
+        } else {   // one tile of rows and more hits than the list holds: a list of its own, of exactly that many
+            rc = grown.alloc(count);
+            if (rc != CID_OK) return rc;
+            unsigned long long again = 0;
+            e = run(s, grown.p, count, &again);
+            if (e == hipSuccess && again != count) return fail(CID_ERR_STATE, "cid_dists_within: %llu hits, then %llu, in the same rows", count, again);
+            total += count;
+            if (e == hipSuccess) e = take(grown.p, count);
+        }
+    }
+    if (e != hipSuccess) return fail(CID_ERR_HIP, "cid_dists_within: %s", hipGetErrorString(e));
+    *n_found = total;
     return CID_OK;
 }
 

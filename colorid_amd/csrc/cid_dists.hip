@@ -57,7 +57,8 @@ __global__ __launch_bounds__(kBlock) void k_dists_mask(const uint32_t *codes, ui
 // row accessions past A are staged as missing and never stored, column accessions past A read T's zero padding (tile tails).
 // compared[i][j] = popcount(mask_i & mask_j) over the W mask words, differ = compared - equal.
 // BOUND: equal <= compared <= L < 2^32.
-// The walk is one body (dists_tile_walk) with two epilogues: k_dists_tile stores the counts, k_dists_best keeps a row's best pair.
+// The walk is one body (dists_tile_walk) with three epilogues: k_dists_tile stores the counts, k_dists_best keeps a row's best pair,
+// k_dists_within appends the pairs under a threshold to a list.
 __device__ __forceinline__ void dists_tile_walk(const DistsParams &p, uint32_t ty, uint32_t tx, uint64_t row_base, uint64_t col_base,
                                                 uint32_t (&eq)[4][4], uint32_t (&cmp)[4][4]) {
     __shared__ __attribute__((aligned(16))) uint32_t s_row[kDistsChunk][kDistsTile];
@@ -183,6 +184,68 @@ __global__ __launch_bounds__(kBlock) void k_dists_best(DistsParams p, DistsBestP
     }
 }
 
+// The neighbour list (cid_dists_within): the same walk, and instead of the store a pair (i, j) is a HIT when i is a row of the launch,
+// j < A, j != i, compared >= w.min_compared (>= 1), differ <= w.max_differ and — w.upper — j > i; every hit goes out as one 16-byte
+// entry {i, j, differ, compared}, compacted.  Slots: a thread counts its hits (a 16-bit mask of its 4 x 4), a wave scans the counts with
+// six shuffles, the four wave totals go through LDS, and thread 0 takes the workgroup's range with ONE 64-bit atomicAdd on *w.cursor —
+// none when the workgroup has no hit.  An entry whose slot is at or past w.cap is not stored and the cursor keeps counting: after the
+// launch it holds the exact number of hits whatever the capacity (cap = 0: a count, w.list is not touched).  Which slot a hit gets
+// depends on the order of the atomics; the set of entries does not, and the caller sorts.
+// Upper mode: a workgroup whose tile lies wholly on or below the diagonal — its last column col_base + 63 <= its first row, the real
+// one: row0 need not be a multiple of 64 — returns before the walk; the test is uniform over the workgroup and precedes every barrier.
+// Tails: a row past n_rows (so past A) is never reported; a column past A has zero masks, compared = 0 < min_compared, and is no hit.
+__global__ __launch_bounds__(kBlock) void k_dists_within(DistsParams p, DistsWithinParams w) {
+    __shared__ uint32_t s_wave[kBlock / kWave];
+    __shared__ unsigned long long s_base;
+    const uint32_t tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
+    const uint64_t col_base = (uint64_t)blockIdx.x * kDistsTile, row_base = (uint64_t)p.row0 + (uint64_t)blockIdx.y * kDistsTile;
+    if (w.upper && col_base + (kDistsTile - 1) <= row_base) return;
+    uint32_t eq[4][4], cmp[4][4];
+    dists_tile_walk(p, ty, tx, row_base, col_base, eq, cmp);
+    uint32_t hits = 0;   // bit 4 r + c
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const uint64_t local = (uint64_t)blockIdx.y * kDistsTile + 4u * ty + (uint32_t)r;   // the row within [row0, row0 + n_rows)
+        const uint64_t i = row_base + 4u * ty + (uint32_t)r;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint64_t j = col_base + 4u * tx + (uint32_t)c;
+            const bool hit = local < p.n_rows && j < p.A && j != i && cmp[r][c] >= w.min_compared && cmp[r][c] - eq[r][c] <= w.max_differ &&
+                             (!w.upper || j > i);
+            hits |= hit ? 1u << (4 * r + c) : 0u;
+        }
+    }
+    const uint32_t mine = (uint32_t)__popc(hits), lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    uint32_t inc = mine;
+#pragma unroll
+    for (int o = 1; o < (int)kWave; o <<= 1) {
+        const uint32_t up = __shfl_up(inc, o, kWave);
+        if (lane >= (uint32_t)o) inc += up;
+    }
+    if (lane == kWave - 1) s_wave[wave] = inc;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (uint32_t v = 0; v < kBlock / kWave; ++v) {
+        before += v < wave ? s_wave[v] : 0u;
+        total += s_wave[v];
+    }
+    if (total == 0) return;   // uniform over the workgroup
+    if (threadIdx.x == 0) s_base = atomicAdd(w.cursor, (unsigned long long)total);
+    __syncthreads();
+    unsigned long long slot = s_base + before + (inc - mine);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (!(hits >> (4 * r + c) & 1u)) continue;
+            if (slot < w.cap)
+                w.list[slot] = make_uint4((uint32_t)(row_base + 4u * ty + (uint32_t)r), (uint32_t)(col_base + 4u * tx + (uint32_t)c),
+                                          cmp[r][c] - eq[r][c], cmp[r][c]);
+            ++slot;
+        }
+}
+
 // ------------------------------------------------------------------------------------------------
 // launchers
 
@@ -205,6 +268,15 @@ hipError_t launch_dists_tile(const DistsParams &p, hipStream_t stream) {
     const uint32_t row_tiles = (p.n_rows + kDistsTile - 1) / kDistsTile;
     if (row_tiles > kDistsMaxRowTiles || (uint64_t)p.row0 + p.n_rows > p.A) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_dists_tile, dim3((unsigned)(p.Ap / kDistsTile), row_tiles), dim3(kBlock), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_dists_within(const DistsParams &p, const DistsWithinParams &w, hipStream_t stream) {
+    if (p.n_rows == 0 || p.A == 0) return hipSuccess;
+    const uint32_t row_tiles = (p.n_rows + kDistsTile - 1) / kDistsTile;
+    if (row_tiles > kDistsMaxRowTiles || (uint64_t)p.row0 + p.n_rows > p.A) return hipErrorInvalidValue;
+    if (w.min_compared == 0 || !w.cursor || (!w.list && w.cap)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dists_within, dim3((unsigned)(p.Ap / kDistsTile), row_tiles), dim3(kBlock), 0, stream, p, w);
     return hipGetLastError();
 }
 

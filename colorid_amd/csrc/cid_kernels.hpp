@@ -332,6 +332,18 @@ struct DistsBestParams {
 constexpr unsigned long long kDistsNoBest = ~0ull;
 bool dists_best_shifts(uint32_t A, uint32_t L, uint32_t *shift_differ, uint32_t *shift_compared);
 hipError_t launch_dists_best(DistsParams p, DistsBestParams b, hipStream_t stream);
+// The neighbour list over the same arrays (p's differ and compared are not read): every pair (i in [row0, row0 + n_rows), j < A, j != i)
+// with compared >= min_compared (>= 1) and differ <= max_differ — upper: also j > i — is appended to list as {i, j, differ, compared},
+// its slot taken from *cursor, which the caller has set to 0.  Entries at or past cap are not stored and still counted: after the launch
+// *cursor is the number of hits (cap = 0: a count, list may be null).  The order inside list is the order of the atomics: sort it.
+// At most kDistsMaxRowTiles tiles of 64 rows a launch.
+struct DistsWithinParams {
+    uint4 *list;                   // [cap] entries a, b, differ, compared
+    unsigned long long cap;
+    unsigned long long *cursor;
+    uint32_t max_differ, min_compared, upper;
+};
+hipError_t launch_dists_within(const DistsParams &p, const DistsWithinParams &w, hipStream_t stream);
 hipError_t launch_get_rows(const uint64_t *mat, uint32_t rs, const uint64_t *d_row_ids, uint32_t *d_words, uint32_t w32,
                            uint64_t n_rows, hipStream_t stream);
 hipError_t launch_insert_kmers(const InsertParams &p, hipStream_t stream);

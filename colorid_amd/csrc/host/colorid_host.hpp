@@ -452,10 +452,20 @@ class NearestTable {
 // appearance, 0 = no call (NA or an empty cell).  Made from an AlleleTable in memory (AlleleTable::codes) or from a table file in the form
 // of PREFIX.raw.tsv / PREFIX.clean.tsv (from_file: a missing header, a line with another number of cells — named by its number — and a
 // repeated accession end the run; it touches no GPU).
+// from_files (`dists --query`): the table's accessions, then the query file's, on the TABLE's loci in its order, the query's columns
+// matched to them by name (a query locus the table lacks is ignored, a table locus the query lacks is no call for the query's accessions)
+// and both files through one encoder.  No locus in common, a locus name repeated in either header and an accession in both files end
+// the run with the file and the name; it touches no GPU either.
+struct QueryAlign {
+    std::string table, query;                                    // the two paths
+    size_t n_table = 0;                                          // accessions [0, n_table) are the table's, the rest the query's
+    size_t common = 0, only_table = 0, only_query = 0;           // loci
+};
 struct AlleleCodes {
     std::vector<std::string> accessions, loci;
     std::vector<uint32_t> codes;   // accessions x loci, row-major
     static AlleleCodes from_file(const std::string &path);
+    static AlleleCodes from_files(const std::string &table, const std::string &query, QueryAlign &q);
 };
 // `dists`: PREFIX.dists.tsv and PREFIX.compared.tsv (A x A, one line per accession), written row block by row block from cid_dists_rows —
 // the host never holds a whole matrix; with cluster also PREFIX.clusters.tsv: single linkage of the pairs with compared >= min_compared
@@ -465,14 +475,26 @@ struct AlleleCodes {
 // min_compared under the key differ, then more compared, then the earlier accessions) as an edge list in key order and as one Newick
 // line per tree, rooted at the tree's first accession, children in table order, branch length = differ.  With no_matrices the two A x A
 // files are not made: rows are fetched only for the clusters, and not at all without them.
+// With within, after the matrices and before the clusters, PREFIX.within.tsv: a, b, differ, compared for every unordered pair with
+// compared >= min_compared and differ <= within_threshold, a before b in the table, in order of (a's row, b's row), written block of
+// rows by block of rows from cid_dists_within(CID_DISTS_UPPER): only those pairs leave the device.
 struct DistsOptions {
     bool cluster = false;
     uint64_t threshold = 0;      // --cluster T
-    uint64_t min_compared = 1;   // --min-compared M (for --cluster and --mst)
+    uint64_t min_compared = 1;   // --min-compared M (for --cluster, --mst and --within)
     bool mst = false;            // --mst
-    bool no_matrices = false;    // --no-matrices (the caller refuses it without mst or cluster)
+    bool no_matrices = false;    // --no-matrices (the caller refuses it without mst, cluster or within)
+    bool within = false;
+    uint64_t within_threshold = 0;   // --within T
 };
 void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, const DistsOptions &opt, void (*phase)(const char *) = nullptr);
+// `dists --query` (t, q from AlleleCodes::from_files; opt.within_threshold and opt.min_compared): PREFIX.query.tsv — query, neighbour, in
+// (table / query), differ, compared: for every query accession in file order its neighbours among the table's and the other query
+// accessions, nearest first (fewer differing loci, then more shared loci, then table before query, each in file order); one line of
+// dashes for a query accession without a neighbour.  One device table of all accessions, cid_dists_within over the query's rows.  ctx is
+// not used (may be null) when the query has no accession.  Says on stderr what it aligned, found and wrote.
+void dists_query_run(cid_ctx *ctx, const AlleleCodes &t, const QueryAlign &q, const std::string &prefix, const DistsOptions &opt,
+                     void (*phase)(const char *) = nullptr);
 
 // ---------------------------------------------------------------- several GPUs (--gpus N / --devices a,b,..)
 // When set, the drivers below shard every query over the group's ranks (cid_group_*); results are identical.

@@ -11,6 +11,13 @@
 //   PREFIX.mst.tsv, PREFIX.mst.nwk (--mst [--min-compared M])   the minimum spanning forest of the graph whose edges are the pairs with
 //                compared >= M, under the key (differ, more compared first, earlier accessions first): cid_dists_forest, Borůvka rounds on
 //                the device, 8 bytes an accession a round over the bus.  Its edges with differ <= T span exactly the clusters at T.
+//   PREFIX.within.tsv (--within T [--min-compared M])   a, b, differ, compared for every unordered pair with compared >= M and differ <= T,
+//                a before b in the table, in order of (a's row, b's row): cid_dists_within(CID_DISTS_UPPER) block of rows by block of rows —
+//                only those pairs leave the device.  Their components are the clusters at T; the forest's edges of at most T are among them.
+//   PREFIX.query.tsv (--query TABLE2 --within T [--min-compared M], `colorid dists` only, nothing else is written)   TABLE2's accessions
+//                on TABLE's loci, matched by name, through the same encoder (AlleleCodes::from_files); the device holds the one table of
+//                both and cid_dists_within answers for the query's rows: per query accession its neighbours among all the others,
+//                nearest first (differ, more compared first, table before query, file order), or one line of dashes
 //   --no-matrices   the two A x A files are not made; rows are then fetched for --cluster only
 #include "colorid_host.hpp"
 
@@ -174,16 +181,22 @@ AlleleCodes AlleleTable::codes(long long max_missing) const {
     return t;
 }
 
-AlleleCodes AlleleCodes::from_file(const std::string &path) {
+namespace {
+
+// One table file into t, through enc.  on_header gets the file's loci and says, per column of the file, which locus of t it is (kNoLocus:
+// the column is not kept); it sets t.loci and makes the encoder where the file is the first.  An accession's loci without a column are no call.
+constexpr size_t kNoLocus = ~(size_t)0;
+template <typename OnHeader>
+void read_table(const std::string &path, AlleleCodes &t, std::unique_ptr<AlleleEncoder> &enc, OnHeader on_header) {
     FILE *f = fopen(path.c_str(), "r");
     if (!f) die("dists: could not open %s", path.c_str());
-    AlleleCodes t;
     char *line = nullptr;
-    size_t cap = 0, line_no = 0;
+    size_t cap = 0, line_no = 0, n_cols = 0;
     ssize_t n;
-    std::unique_ptr<AlleleEncoder> enc;
     std::unordered_map<std::string, size_t> seen;   // accession -> its line
     std::vector<std::pair<const char *, size_t>> cells;
+    std::vector<size_t> to;                         // column of the file -> locus of t
+    std::vector<uint32_t> row;
     while ((n = getline(&line, &cap, f)) >= 0) {
         ++line_no;
         size_t len = (size_t)n;
@@ -201,26 +214,128 @@ AlleleCodes AlleleCodes::from_file(const std::string &path) {
             if (cells[0].second != 0)
                 die("dists: %s has no header: its first line begins with '%.*s', not with an empty cell before the loci", path.c_str(),
                     (int)std::min<size_t>(cells[0].second, 60), cells[0].first);
+            std::vector<std::string> loci;
             if (!(cells.size() == 2 && cells[1].second == 0))   // ("\t" alone: a table without loci)
-                for (size_t i = 1; i < cells.size(); ++i) t.loci.emplace_back(cells[i].first, cells[i].second);
-            enc.reset(new AlleleEncoder(t.loci.size()));
+                for (size_t i = 1; i < cells.size(); ++i) loci.emplace_back(cells[i].first, cells[i].second);
+            n_cols = loci.size();
+            to = on_header(loci);
             continue;
         }
-        if (cells.size() != t.loci.size() + 1)
-            die("dists: %s line %zu has %zu cells after the name, the header has %zu loci", path.c_str(), line_no, cells.size() - 1, t.loci.size());
+        if (cells.size() != n_cols + 1)
+            die("dists: %s line %zu has %zu cells after the name, the header has %zu loci", path.c_str(), line_no, cells.size() - 1, n_cols);
         std::string name(cells[0].first, cells[0].second);
         const auto ins = seen.emplace(name, line_no);
         if (!ins.second)
             die("dists: %s line %zu repeats the accession '%s' of line %zu", path.c_str(), line_no, name.c_str(), ins.first->second);
         t.accessions.push_back(std::move(name));
-        for (size_t l = 0; l < t.loci.size(); ++l) t.codes.push_back(enc->code(l, cells[l + 1].first, cells[l + 1].second));
+        row.assign(t.loci.size(), 0u);
+        for (size_t l = 0; l < n_cols; ++l)
+            if (to[l] != kNoLocus) row[to[l]] = enc->code(to[l], cells[l + 1].first, cells[l + 1].second);
+        t.codes.insert(t.codes.end(), row.begin(), row.end());
     }
     free(line);
     fclose(f);
     if (line_no == 0) die("dists: %s has no header: it is empty", path.c_str());
+}
+
+// the first table of a run: its header is t's loci
+auto first_table(AlleleCodes &t, std::unique_ptr<AlleleEncoder> &enc) {
+    return [&t, &enc](const std::vector<std::string> &loci) {
+        t.loci = loci;
+        enc.reset(new AlleleEncoder(loci.size()));
+        std::vector<size_t> to(loci.size());
+        std::iota(to.begin(), to.end(), (size_t)0);
+        return to;
+    };
+}
+
+void refuse_repeated_loci(const std::string &path, const std::vector<std::string> &loci) {
+    std::unordered_map<std::string, size_t> at;
+    for (size_t l = 0; l < loci.size(); ++l) {
+        const auto ins = at.emplace(loci[l], l);
+        if (!ins.second)
+            die("dists: %s repeats the locus '%s' in its header (columns %zu and %zu): with --query the loci are matched by name", path.c_str(),
+                loci[l].c_str(), ins.first->second + 1, l + 1);
+    }
+}
+
+}  // namespace
+
+AlleleCodes AlleleCodes::from_file(const std::string &path) {
+    AlleleCodes t;
+    std::unique_ptr<AlleleEncoder> enc;
+    read_table(path, t, enc, first_table(t, enc));
     check_shape(t.accessions.size(), t.loci.size());
     return t;
 }
+
+// `dists --query`: the database table, then the query table's accessions on the database's loci, matched by name, through the one
+// encoder (alleles are compared as text per locus).  A query locus the database does not have is ignored; a database locus the query
+// lacks is no call for every query accession.
+AlleleCodes AlleleCodes::from_files(const std::string &table, const std::string &query, QueryAlign &q) {
+    AlleleCodes t;
+    std::unique_ptr<AlleleEncoder> enc;
+    read_table(table, t, enc, [&](const std::vector<std::string> &loci) {
+        refuse_repeated_loci(table, loci);
+        return first_table(t, enc)(loci);
+    });
+    q = QueryAlign{};
+    q.table = table;
+    q.query = query;
+    q.n_table = t.accessions.size();
+    read_table(query, t, enc, [&](const std::vector<std::string> &loci) {
+        refuse_repeated_loci(query, loci);
+        std::unordered_map<std::string, size_t> at;
+        for (size_t l = 0; l < t.loci.size(); ++l) at.emplace(t.loci[l], l);
+        std::vector<size_t> to(loci.size(), kNoLocus);
+        for (size_t l = 0; l < loci.size(); ++l) {
+            const auto it = at.find(loci[l]);
+            if (it == at.end()) { ++q.only_query; continue; }
+            to[l] = it->second;
+            ++q.common;
+        }
+        q.only_table = t.loci.size() - q.common;
+        if (q.common == 0)
+            die("dists: %s and %s have no locus in common (%zu and %zu loci, matched by name)", table.c_str(), query.c_str(), t.loci.size(), loci.size());
+        return to;
+    });
+    std::unordered_map<std::string, size_t> in_table;
+    for (size_t a = 0; a < q.n_table; ++a) in_table.emplace(t.accessions[a], a);
+    for (size_t a = q.n_table; a < t.accessions.size(); ++a)
+        if (in_table.count(t.accessions[a]))
+            die("dists: the accession '%s' is in both %s and %s: a query accession needs a name of its own", t.accessions[a].c_str(), table.c_str(),
+                query.c_str());
+    check_shape(t.accessions.size(), t.loci.size());
+    return t;
+}
+
+namespace {
+
+// The pairs of cid_dists_within over the rows [r0, r1), block of rows by block of rows, each block handed to `sink` sorted by (a, b).
+// A block is 4096 rows; one that gives more than 2^24 pairs (256 MiB) is asked for again in halves, down to one tile of 64 rows.
+template <typename Sink>
+uint64_t within_blocks(cid_dists *d, size_t r0, size_t r1, uint64_t threshold, uint64_t min_compared, uint32_t flags, Sink sink) {
+    const uint32_t T = (uint32_t)std::min<uint64_t>(threshold, 0xFFFFFFFFull), M = (uint32_t)std::min<uint64_t>(min_compared, 0xFFFFFFFFull);
+    std::vector<cid_dists_edge> buf(1u << 16);
+    uint64_t total = 0;
+    size_t block = 4096;
+    for (size_t r = r0; r < r1;) {
+        const size_t nr = std::min(block, r1 - r);
+        uint64_t n = 0;
+        if (cid_dists_within(d, (uint32_t)r, (uint32_t)nr, T, M, flags, buf.data(), buf.size(), &n) != CID_OK) die("cid_dists_within: %s", cid_last_error());
+        if (n > buf.size()) {
+            if (n > (1ull << 24) && block > 64) { block /= 2; continue; }
+            buf.resize((size_t)n);   // come back with room
+            continue;
+        }
+        sink(buf.data(), (size_t)n);
+        total += n;
+        r += nr;
+    }
+    return total;
+}
+
+}  // namespace
 
 void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, const DistsOptions &opt, void (*phase)(const char *)) {
     const size_t A = t.accessions.size(), L = t.loci.size();
@@ -304,6 +419,21 @@ void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, co
         if (phase) phase("distances computed");
         fprintf(stderr, "dists: %zu accessions x %zu loci, matrices not written (--no-matrices)\n", A, L);
     }
+    if (opt.within) {
+        const std::string w_path = prefix + ".within.tsv";
+        FILE *fw = dists_out(w_path);
+        fputs("a\tb\tdiffer\tcompared\n", fw);
+        uint64_t n_pairs = 0;
+        if (d)
+            n_pairs = within_blocks(d, 0, A, opt.within_threshold, min_compared, CID_DISTS_UPPER, [&](const cid_dists_edge *e, size_t n) {
+                for (size_t k = 0; k < n; ++k)
+                    fprintf(fw, "%s\t%s\t%u\t%u\n", t.accessions[e[k].a].c_str(), t.accessions[e[k].b].c_str(), e[k].differ, e[k].compared);
+            });
+        dists_close(fw, w_path);
+        if (phase) phase("pairs within the threshold found and written");
+        fprintf(stderr, "dists: %llu pairs within %llu differing loci (at least %llu shared), written to %s\n", (unsigned long long)n_pairs,
+                (unsigned long long)opt.within_threshold, (unsigned long long)min_compared, w_path.c_str());
+    }
     if (opt.cluster) {
         std::vector<uint32_t> size(A, 0), number(A, 0);
         for (size_t i = 0; i < A; ++i) ++size[find((uint32_t)i)];
@@ -338,6 +468,57 @@ void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, co
         if (phase) phase("minimum spanning forest computed and written");
     }
     if (d) cid_dists_destroy(d);
+}
+
+// `dists --query`: the device holds the one table of D + Q accessions and the query's rows [D, D + Q) are asked for their neighbours
+// among all of them (flags = 0: a query accession's pair with another query accession is named from both ends).  Per query accession the
+// neighbours are put nearest first: fewer differing loci, then more shared loci, then the lower row — database accessions come before
+// query accessions, each in file order — which for a fixed query is the order of the `nearest` column and of the forest's edge key.
+void dists_query_run(cid_ctx *ctx, const AlleleCodes &t, const QueryAlign &q, const std::string &prefix, const DistsOptions &opt,
+                     void (*phase)(const char *)) {
+    const size_t A = t.accessions.size(), L = t.loci.size(), D = q.n_table, Q = A - D;
+    const uint64_t min_compared = std::max<uint64_t>(opt.min_compared, 1);
+    const std::string q_path = prefix + ".query.tsv";
+    FILE *fq = dists_out(q_path);
+    fputs("query\tneighbour\tin\tdiffer\tcompared\n", fq);
+    uint64_t n_found = 0;
+    size_t next = D, without = 0;   // next: the first query accession without its lines yet
+    auto none_up_to = [&](size_t end) {
+        for (; next < end; ++next, ++without) fprintf(fq, "%s\t-\t-\t-\t-\n", t.accessions[next].c_str());
+    };
+    if (Q && L) {
+        cid_dists *d = nullptr;
+        if (cid_dists_create(ctx, t.codes.data(), (uint32_t)A, (uint32_t)L, &d) != CID_OK) die("cid_dists_create: %s", cid_last_error());
+        if (phase) phase("allele codes uploaded");
+        std::vector<cid_dists_edge> run;
+        n_found = within_blocks(d, D, A, opt.within_threshold, min_compared, 0, [&](const cid_dists_edge *e, size_t n) {
+            for (size_t k = 0; k < n;) {   // (a block holds whole rows: an accession's neighbours are one run of it)
+                size_t end = k;
+                while (end < n && e[end].a == e[k].a) ++end;
+                none_up_to(e[k].a);
+                run.assign(e + k, e + end);
+                std::sort(run.begin(), run.end(), [](const cid_dists_edge &x, const cid_dists_edge &y) {
+                    if (x.differ != y.differ) return x.differ < y.differ;
+                    if (x.compared != y.compared) return x.compared > y.compared;
+                    return x.b < y.b;
+                });
+                for (const cid_dists_edge &x : run)
+                    fprintf(fq, "%s\t%s\t%s\t%u\t%u\n", t.accessions[x.a].c_str(), t.accessions[x.b].c_str(), x.b < D ? "table" : "query", x.differ,
+                            x.compared);
+                next = e[k].a + 1;
+                k = end;
+            }
+        });
+        cid_dists_destroy(d);
+    }
+    none_up_to(A);
+    dists_close(fq, q_path);
+    if (phase) phase("neighbours of the query accessions found and written");
+    fprintf(stderr,
+            "dists: %zu query accessions against %zu, %zu loci in common (%zu only in %s, %zu only in %s); %llu neighbours within %llu differing loci "
+            "(at least %llu shared), %zu queries without one, written to %s\n",
+            Q, D, q.common, q.only_table, q.table.c_str(), q.only_query, q.query.c_str(), (unsigned long long)n_found,
+            (unsigned long long)opt.within_threshold, (unsigned long long)min_compared, without, q_path.c_str());
 }
 
 }  // namespace colorid

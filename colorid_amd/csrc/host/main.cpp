@@ -633,7 +633,7 @@ long long max_missing_arg(const Args &a) {
     return n;
 }
 
-// --cluster T / --min-compared M (search --dists, dists): a number of loci
+// --cluster T / --within T / --min-compared M (search --dists, dists): a number of loci
 uint64_t loci_arg(const Args &a, const char *key) {
     const std::string &v = a.one(key);
     char *end = nullptr;
@@ -642,17 +642,18 @@ uint64_t loci_arg(const Args &a, const char *key) {
     if (v.empty() || *end || n < 0 || errno) die("error: --%s expects a number of loci (0 or more), got '%s'", key, v.c_str());
     return (uint64_t)n;
 }
-// what --cluster, --min-compared, --mst and --no-matrices ask for; refuses --min-compared without --cluster or --mst, and --no-matrices
-// when nothing else would be written
+// what --cluster, --within, --min-compared, --mst and --no-matrices ask for; refuses --min-compared without --cluster, --mst or --within,
+// and --no-matrices when nothing else would be written
 DistsOptions dists_options(const Args &a) {
     DistsOptions o;
     o.mst = a.flags.count("mst") != 0;
     o.no_matrices = a.flags.count("no-matrices") != 0;
-    if (a.has("min-compared") && !a.has("cluster") && !o.mst)
-        die("error: --min-compared needs --cluster T (it is the least number of loci two accessions must share to be linked) or --mst");
-    if (o.no_matrices && !a.has("cluster") && !o.mst)
-        die("error: --no-matrices needs --mst or --cluster T (without the two matrices nothing would be written)");
+    if (a.has("min-compared") && !a.has("cluster") && !o.mst && !a.has("within"))
+        die("error: --min-compared needs --cluster T (it is the least number of loci two accessions must share to be linked), --mst or --within T");
+    if (o.no_matrices && !a.has("cluster") && !o.mst && !a.has("within"))
+        die("error: --no-matrices needs --mst or --cluster T or --within T (without the two matrices nothing would be written)");
     if (a.has("cluster")) { o.cluster = true; o.threshold = loci_arg(a, "cluster"); }
+    if (a.has("within")) { o.within = true; o.within_threshold = loci_arg(a, "within"); }
     if (a.has("min-compared")) o.min_compared = loci_arg(a, "min-compared");
     return o;
 }
@@ -675,7 +676,7 @@ int cmd_search(int argc, char **argv) {
                                                      {0, "alleles", true, false}, {0, "max-missing", true, false},
                                                      {0, "nearest", false, false}, {0, "dists", false, false},
                                                      {0, "cluster", true, false}, {0, "min-compared", true, false},
-                                                     {0, "mst", false, false}, {0, "no-matrices", false, false},
+                                                     {0, "mst", false, false}, {0, "no-matrices", false, false}, {0, "within", true, false},
                                                      {0, "gather", true, false}, {0, "gather-min", true, false}, {0, "gather-max", true, false}}));
     for (const char *req : {"bigsi", "query"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
@@ -716,12 +717,13 @@ int cmd_search(int argc, char **argv) {
         if (a.has("gpus") || a.has("devices") || a.has("placement") || cli_env("COLORID_REDUCE"))
             die("error: --nearest runs on one GPU: it does not go with --gpus, --devices, --placement or COLORID_REDUCE");
     }
-    // -s -m --alleles PREFIX --dists [--cluster T] [--mst] [--min-compared M] [--no-matrices]: after the tables, the pairwise allele
-    // distances of the raw table's accessions (the clean table's with --max-missing), their clusters and their minimum spanning forest,
-    // on this run's context: the files `colorid dists -t PREFIX.raw.tsv` writes.  Refused here, before the GPU context is made
+    // -s -m --alleles PREFIX --dists [--cluster T] [--within T] [--mst] [--min-compared M] [--no-matrices]: after the tables, the pairwise
+    // allele distances of the raw table's accessions (the clean table's with --max-missing), the pairs within T, their clusters and their
+    // minimum spanning forest, on this run's context: the files `colorid dists -t PREFIX.raw.tsv` writes.  Refused here, before the GPU context is made
     const bool dists = a.flags.count("dists") != 0;
     if (dists && !a.has("alleles")) die("error: --dists needs -s -m --alleles PREFIX (it writes PREFIX.dists.tsv from the allele table)");
     if (!dists && a.has("cluster")) die("error: --cluster needs --dists (it clusters the allele distances)");
+    if (!dists && a.has("within")) die("error: --within needs --dists (it lists the pairs of accessions at most T alleles apart)");
     if (!dists && a.flags.count("mst")) die("error: --mst needs --dists (it is the minimum spanning forest of the allele distances)");
     if (!dists && a.flags.count("no-matrices")) die("error: --no-matrices needs --dists (it leaves out PREFIX.dists.tsv and PREFIX.compared.tsv)");
     const DistsOptions dists_opt = dists_options(a);
@@ -820,17 +822,38 @@ int cmd_alleles(int argc, char **argv) {
     return 0;
 }
 
-// dists: -t TABLE -o PREFIX [--cluster T] [--mst] [--min-compared M] [--no-matrices] — PREFIX.dists.tsv and PREFIX.compared.tsv (and
-// PREFIX.clusters.tsv; PREFIX.mst.tsv and PREFIX.mst.nwk) from a table in the form of PREFIX.raw.tsv / PREFIX.clean.tsv.  The flags are
-// checked before the table is read, the table is read and checked before the GPU is opened; a table without accessions or without loci
-// needs none.
+// dists: -t TABLE -o PREFIX [--cluster T] [--within T] [--mst] [--min-compared M] [--no-matrices] — PREFIX.dists.tsv and
+// PREFIX.compared.tsv (and PREFIX.clusters.tsv; PREFIX.within.tsv; PREFIX.mst.tsv and PREFIX.mst.nwk) from a table in the form of
+// PREFIX.raw.tsv / PREFIX.clean.tsv.  The flags are checked before the table is read, the table is read and checked before the GPU is
+// opened; a table without accessions or without loci needs none.
+// dists: -t TABLE --query TABLE2 -o PREFIX --within T [--min-compared M] — PREFIX.query.tsv alone: the neighbours of TABLE2's accessions
+// among TABLE's and each other, the loci matched by name; a query table without accessions needs no GPU.
 int cmd_dists(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, {{'t', "table", true, false}, {'o', "output", true, false}, {0, "cluster", true, false},
                                          {0, "min-compared", true, false}, {0, "mst", false, false}, {0, "no-matrices", false, false},
-                                         {0, "device", true, false}});
+                                         {0, "within", true, false}, {0, "query", true, false}, {0, "device", true, false}});
     for (const char *req : {"table", "output"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
+    if (a.has("query")) {
+        if (!a.has("within")) die("error: --query needs --within T (it lists the query accessions' neighbours at most T alleles apart)");
+        if (a.has("cluster")) die("error: --query writes PREFIX.query.tsv alone and does not go with --cluster");
+        if (a.flags.count("mst")) die("error: --query writes PREFIX.query.tsv alone and does not go with --mst");
+        if (a.flags.count("no-matrices")) die("error: --query writes PREFIX.query.tsv alone and does not go with --no-matrices (no matrix is made)");
+    }
     const DistsOptions opt = dists_options(a);
+    if (a.has("query")) {
+        QueryAlign q;
+        const AlleleCodes both = AlleleCodes::from_files(a.one("table"), a.one("query"), q);
+        phase_done("tables read");
+        cid_ctx *ctx = nullptr;
+        if (both.accessions.size() > q.n_table && !both.loci.empty()) {
+            ctx = make_ctx(a);
+            phase_done("GPU context");
+        }
+        dists_query_run(ctx, both, q, a.one("output"), opt, phase_done);
+        if (ctx) cid_ctx_destroy(ctx);
+        return 0;
+    }
     const AlleleCodes table = AlleleCodes::from_file(a.one("table"));
     phase_done("table read");
     cid_ctx *ctx = nullptr;
@@ -1152,8 +1175,16 @@ int main(int argc, char **argv) {
                "                             the earlier accessions; edges a, b, differ, compared and one Newick line per tree (branch length =\n"
                "                             differing loci); its edges of at most T are the clusters of --cluster T.  --no-matrices (with --mst\n"
                "                             or --cluster): PREFIX.dists.tsv and PREFIX.compared.tsv are not written\n"
+               "                             --dists --within T [--min-compared M]: PREFIX.within.tsv, a, b, differ, compared for every two\n"
+               "                             accessions that share at least M (1) loci and differ at no more than T of them, a before b in the\n"
+               "                             table: the pairs are found on the GPU and only they come back (goes with --no-matrices); their\n"
+               "                             connected components are the clusters of --cluster T\n"
                "    dists -t TABLE -o PREFIX [--cluster T] [--mst] [--min-compared M] [--no-matrices]   the same files from a table in the form\n"
-               "                             of PREFIX.raw.tsv\n"
+               "                             of PREFIX.raw.tsv; [--within T] as above\n"
+               "    dists -t TABLE --query TABLE2 -o PREFIX --within T [--min-compared M]   PREFIX.query.tsv alone: for every accession of TABLE2\n"
+               "                             the accessions of TABLE and of TABLE2 within T, nearest first (query, neighbour, in = table or\n"
+               "                             query, differ, compared; a line of - for none); loci are matched by name: TABLE's are used, one that\n"
+               "                             TABLE2 lacks is no call there, one only TABLE2 has is ignored\n"
                "    alleles -r ROWS -o PREFIX [--max-missing N]   the same tables from the saved stdout of a `search -s -m` run; no GPU\n\n"
                "INDEX MAINTENANCE:\n"
                "    collapse -b OUT -i idx.bxi -g groups.tsv      several accessions as one colour (groups.tsv: accession TAB group per line;\n"

@@ -445,6 +445,28 @@ class Dists:
         check(self.lib.cid_dists_forest(self.h, min_compared, _p(out), C.byref(n), C.byref(rounds)))
         return out[:n.value].copy(), rounds.value
 
+    def within_count(self, max_differ, min_compared=1, row0=0, n_rows=None, upper=False):
+        """how many pairs within() would return (cid_dists_within with cap = 0)"""
+        if n_rows is None:
+            n_rows = self.n_acc - row0
+        n = C.c_uint64(0)
+        check(self.lib.cid_dists_within(self.h, row0, n_rows, max_differ, min_compared, 1 if upper else 0, None, 0, C.byref(n)))
+        return n.value
+
+    def within(self, max_differ, min_compared=1, row0=0, n_rows=None, upper=False):
+        """the neighbour list (cid_dists_within) -> [n, 4] uint32: a, b, differ, compared for every pair (a in [row0, row0 + n_rows), b != a)
+        with compared >= min_compared and differ <= max_differ — upper: b > a only — sorted by (a, b)"""
+        if n_rows is None:
+            n_rows = self.n_acc - row0
+        cap = min(max(n_rows, 0) * max(self.n_acc - 1, 0), 1 << 16)
+        while True:
+            out = np.zeros((max(cap, 1), 4), np.uint32)      # cid_dists_edge: a, b, differ, compared
+            n = C.c_uint64(0)
+            check(self.lib.cid_dists_within(self.h, row0, n_rows, max_differ, min_compared, 1 if upper else 0, _p(out), cap, C.byref(n)))
+            if n.value <= cap:
+                return out[:n.value].copy()
+            cap = n.value                                     # come back with room
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.cid_dists_destroy(self.h)

@@ -227,6 +227,18 @@ typedef struct cid_dists_edge {
 } cid_dists_edge;
 int cid_dists_best(cid_dists *, const uint32_t *comp, uint32_t min_compared, cid_dists_edge *best);
 int cid_dists_forest(cid_dists *, uint32_t min_compared, cid_dists_edge *edges, uint32_t *n_edges, uint32_t *n_rounds);
+/* The neighbour list (`dists --within T`, `dists --query`): every pair {a in [row0, row0 + n_rows), b in [0, n_acc), b != a} with
+ * compared(a, b) >= min_compared (>= 1) and differ(a, b) <= max_differ — with CID_DISTS_UPPER also b > a, so that a query over all rows
+ * names every unordered pair once — as {a, b, differ, compared}, sorted by (a, b): the order is part of the contract and does not depend
+ * on how the device splits the work.  *n_found is the number of such pairs, always.  If *n_found <= cap, out[0 .. *n_found) holds them;
+ * if it is larger the contents of out are unspecified and the caller comes back with room for *n_found.  out may be NULL when cap == 0:
+ * that is a count.  n_rows == 0 is a no-op with *n_found = 0.  The pairs are found on the device and only they cross the bus: no A x A
+ * matrix exists anywhere.  Device memory beside the table: a list of at most "dense_report_bytes" / 16 entries (rows whose pairs exceed
+ * it are cut into slices inside the call; one 64-row tile may need up to 64 x n_acc entries whatever the budget) and 8 bytes.
+ * CID_ERR_INVALID: null handle or n_found, min_compared == 0, row0 + n_rows > n_acc, unknown flag bits, out == NULL with cap > 0. */
+#define CID_DISTS_UPPER 1u   /* only pairs with b > a: each unordered pair of a symmetric query once */
+int cid_dists_within(cid_dists *, uint32_t row0, uint32_t n_rows, uint32_t max_differ, uint32_t min_compared,
+                     uint32_t flags, cid_dists_edge *out, size_t cap, uint64_t *n_found);
 void cid_dists_destroy(cid_dists *);
 
 /* ---- a5: proportional search, the hot loop of batch_search_pe::batch_search

@@ -1,8 +1,9 @@
 // Stand-alone host check of colorid_amd/csrc/host/dists.cpp under ASan + UBSan, no GPU and no libcolorid_hip.so: the table parser, the
 // allele encoder (both entrances), the row-block driver, the clustering and the forest and Newick writers, with a plain C++ cid_dists_*
-// behind them (the forest: Kruskal over the stand-in's own loop).
-//   make -C tools bin/dists_host_check ;  tools/bin/dists_host_check TABLE PREFIX [T [M [mst [no-matrices]]]]
-//   (writes PREFIX.dists.tsv, .compared.tsv, .clusters.tsv; T = - for no clusters; with mst also PREFIX.mst.tsv, .mst.nwk)
+// behind them (the forest: Kruskal over the stand-in's own loop; the neighbour list: the same loop, filtered).
+//   make -C tools bin/dists_host_check ;  tools/bin/dists_host_check TABLE PREFIX [T [M [mst [no-matrices]]]] [within=T] [query=TABLE2]
+//   (writes PREFIX.dists.tsv, .compared.tsv, .clusters.tsv; T = - for no clusters; with mst also PREFIX.mst.tsv, .mst.nwk; with within=T
+//   also PREFIX.within.tsv; with query=TABLE2 — and within=T — PREFIX.query.tsv alone, the two tables aligned by AlleleCodes::from_files)
 #include <algorithm>
 #include <cstdarg>
 #include <numeric>
@@ -84,17 +85,46 @@ int cid_dists_forest(cid_dists *d, uint32_t min_compared, cid_dists_edge *edges,
     *n_rounds = 1;
     return 0;
 }
+// the pairs of the loop above that pass, in (a, b) order; a small cap makes dists.cpp come back with room
+int cid_dists_within(cid_dists *d, uint32_t row0, uint32_t n, uint32_t max_differ, uint32_t min_compared, uint32_t flags, cid_dists_edge *out,
+                     size_t cap, uint64_t *n_found) {
+    std::vector<uint32_t> differ(d->A), compared(d->A);
+    *n_found = 0;
+    for (uint32_t i = row0; i < row0 + n; ++i) {
+        cid_dists_rows(d, i, 1, differ.data(), compared.data());
+        for (uint32_t j = (flags & CID_DISTS_UPPER) ? i + 1 : 0; j < d->A; ++j) {
+            if (j == i || compared[j] < min_compared || differ[j] > max_differ) continue;
+            if (*n_found < cap) out[*n_found] = cid_dists_edge{i, j, differ[j], compared[j]};
+            ++*n_found;
+        }
+    }
+    return 0;
+}
 void cid_dists_destroy(cid_dists *d) { delete d; }
 }
 
 int main(int argc, char **argv) {
     using namespace colorid;
-    if (argc < 3) return 2;
     DistsOptions o;
+    std::string query;
+    int kept = 1;   // within=T and query=TABLE2 come out of the positional arguments
+    for (int i = 1; i < argc; ++i) {
+        if (strncmp(argv[i], "within=", 7) == 0) { o.within = true; o.within_threshold = strtoull(argv[i] + 7, nullptr, 10); }
+        else if (strncmp(argv[i], "query=", 6) == 0) query = argv[i] + 6;
+        else argv[kept++] = argv[i];
+    }
+    argc = kept;
+    if (argc < 3) return 2;
     if (argc > 3 && strcmp(argv[3], "-") != 0) { o.cluster = true; o.threshold = strtoull(argv[3], nullptr, 10); }
     if (argc > 4) o.min_compared = strtoull(argv[4], nullptr, 10);
     o.mst = argc > 5;
     o.no_matrices = argc > 6;
+    if (!query.empty()) {
+        QueryAlign q;
+        const AlleleCodes both = AlleleCodes::from_files(argv[1], query, q);
+        dists_query_run(nullptr, both, q, argv[2], o);
+        return 0;
+    }
     const AlleleCodes t = AlleleCodes::from_file(argv[1]);
     dists_run(nullptr, t, argv[2], o);
     // the in-memory entrance over the same cells
