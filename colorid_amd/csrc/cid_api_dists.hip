@@ -1,6 +1,7 @@
 // C ABI of libcolorid_hip.so, part 6: `colorid dists` — the pairwise allele distances of a cgMLST table: for two accessions the loci both
 // have a call at (compared) and those of them where the calls differ (differ), and the minimum spanning forest of the accessions under
-// them (cid_dists_best, cid_dists_forest), and the pairs within a threshold as a list (cid_dists_within).  Kernels: cid_dists.hip.
+// them (cid_dists_best, cid_dists_forest), the pairs within a threshold as a list (cid_dists_within), and every accession's K nearest
+// (cid_dists_closest).  Kernels: cid_dists.hip.
 #include "cid_api_common.hpp"
 
 #include <numeric>
@@ -33,6 +34,7 @@ struct Scratch {
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;   // cid_dists_edge.b of an accession without a candidate
 static_assert(sizeof(cid_dists_edge) == 16, "cid_dists_edge is part of the ABI");
+static_assert(CID_DISTS_CLOSEST_MAX == cid::kDistsClosestMax, "the header's limit is the kernels'");
 
 // the packing limit of k_dists_best's key, refused before anything is launched
 int check_best_shape(const cid_dists *d) {
@@ -346,6 +348,68 @@ int cid_dists_within(cid_dists *d, uint32_t row0, uint32_t n_rows, uint32_t max_
     }
     if (e != hipSuccess) return fail(CID_ERR_HIP, "cid_dists_within: %s", hipGetErrorString(e));
     *n_found = total;
+    return CID_OK;
+}
+
+// The K nearest.  Device memory, all from the ctx's block cache: part, rows x (acc_pad / 64) x k keys of 8 bytes — the rows go out in
+// slices of whole 64-row tiles so that it stays within dense_report_bytes, at least one tile a slice whatever the budget (the exemption
+// of cid_dists_rows) — and the merge's levels, each a 64th of the one before.  A slice is one k_dists_closest launch, then
+// k_dists_closest_merge level by level until a row has one list (one level up to 4 096 accessions, two up to 262 144), then one copy of
+// rows x k keys, unpacked here as cid_dists_best's are.  A table of up to 64 accessions has one list a row from the start and still
+// takes one level: one path, and the copy reads what the merge wrote.
+int cid_dists_closest(cid_dists *d, uint32_t row0, uint32_t n_rows, uint32_t k, uint32_t max_differ, uint32_t min_compared, cid_dists_edge *out) {
+    if (!d) return fail(CID_ERR_INVALID, "null argument");
+    if (k == 0) return fail(CID_ERR_INVALID, "k = 0: the nearest none");
+    if (min_compared == 0) return fail(CID_ERR_INVALID, "min_compared = 0: two accessions without a common locus are never neighbours");
+    if ((uint64_t)row0 + n_rows > d->n_acc)
+        return fail(CID_ERR_INVALID, "rows [%u, %llu) of a table of %u accessions", row0, (unsigned long long)row0 + n_rows, d->n_acc);
+    if (!out && n_rows) return fail(CID_ERR_INVALID, "null out");
+    if (k > CID_DISTS_CLOSEST_MAX)
+        return fail(CID_ERR_UNSUPPORTED, "k = %u: at most %u nearest an accession (cid_dists_within gives longer lists)", k, CID_DISTS_CLOSEST_MAX);
+    int rc = check_best_shape(d);
+    if (rc != CID_OK) return rc;
+    if (n_rows == 0) return CID_OK;
+    cid_ctx *c = d->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint64_t tiles = d->acc_pad / 64u, row_bytes = tiles * k * 8ull;   // of part
+    uint64_t per = std::max<uint64_t>(c->tune.dense_report_bytes / row_bytes & ~63ull, 64);
+    per = std::min<uint64_t>({per, 64ull * cid::kDistsMaxRowTiles, ((uint64_t)n_rows + 63u) & ~63ull});
+    const uint64_t held = std::min<uint64_t>(per, n_rows);   // rows a slice really has
+    const uint64_t lists1 = (tiles + 63u) / 64u, lists2 = (lists1 + 63u) / 64u;
+    Scratch<unsigned long long> part(c), even(c), odd(c);    // the merge's levels go to even, odd, even, ..
+    rc = part.alloc(held * tiles * k);
+    if (rc == CID_OK) rc = even.alloc(held * lists1 * k);
+    if (rc == CID_OK && lists1 > 1) rc = odd.alloc(held * lists2 * k);
+    if (rc != CID_OK) return rc;
+    cid::DistsParams p{};
+    p.T = d->codes_t; p.maskT = d->mask_t; p.Ap = d->acc_pad; p.A = d->n_acc; p.L = d->n_loci; p.W = d->n_words;
+    cid::DistsClosestParams q{};
+    q.part = part.p; q.k = k; q.max_differ = max_differ; q.min_compared = min_compared;
+    const BestRound key(d);   // (its shifts and its unpack; it allocates nothing until it runs)
+    std::vector<unsigned long long> keys(held * k);
+    hipError_t e = hipSuccess;
+    for (uint64_t r = 0; r < n_rows && e == hipSuccess; r += per) {
+        const uint64_t n = std::min<uint64_t>(per, n_rows - r);
+        p.row0 = row0 + (uint32_t)r; p.n_rows = (uint32_t)n;
+        e = cid::launch_dists_closest(p, q, c->stream);
+        const unsigned long long *from = part.p;
+        bool to_even = true;
+        for (uint64_t lists = tiles; e == hipSuccess;) {
+            unsigned long long *to = to_even ? even.p : odd.p;
+            e = cid::launch_dists_closest_merge(from, to, n, lists, k, c->stream);
+            from = to;
+            to_even = !to_even;
+            lists = (lists + 63u) / 64u;
+            if (lists == 1) break;
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(keys.data(), from, n * k * 8ull, hipMemcpyDeviceToHost, c->stream);
+        const hipError_t es = hipStreamSynchronize(c->stream);   // the slice's buffers are the next slice's
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) break;
+        for (uint64_t i = 0; i < n; ++i)
+            for (uint32_t x = 0; x < k; ++x) out[(r + i) * k + x] = key.unpack(row0 + (uint32_t)(r + i), keys[i * k + x]);
+    }
+    if (e != hipSuccess) return fail(CID_ERR_HIP, "cid_dists_closest: %s", hipGetErrorString(e));
     return CID_OK;
 }
 

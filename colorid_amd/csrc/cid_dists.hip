@@ -57,8 +57,8 @@ __global__ __launch_bounds__(kBlock) void k_dists_mask(const uint32_t *codes, ui
 // row accessions past A are staged as missing and never stored, column accessions past A read T's zero padding (tile tails).
 // compared[i][j] = popcount(mask_i & mask_j) over the W mask words, differ = compared - equal.
 // BOUND: equal <= compared <= L < 2^32.
-// The walk is one body (dists_tile_walk) with three epilogues: k_dists_tile stores the counts, k_dists_best keeps a row's best pair,
-// k_dists_within appends the pairs under a threshold to a list.
+// The walk is one body (dists_tile_walk) with four epilogues: k_dists_tile stores the counts, k_dists_best keeps a row's best pair,
+// k_dists_within appends the pairs under a threshold to a list, k_dists_closest keeps a row's k best pairs of the tile.
 __device__ __forceinline__ void dists_tile_walk(const DistsParams &p, uint32_t ty, uint32_t tx, uint64_t row_base, uint64_t col_base,
                                                 uint32_t (&eq)[4][4], uint32_t (&cmp)[4][4]) {
     __shared__ __attribute__((aligned(16))) uint32_t s_row[kDistsChunk][kDistsTile];
@@ -246,6 +246,88 @@ __global__ __launch_bounds__(kBlock) void k_dists_within(DistsParams p, DistsWit
         }
 }
 
+// The K nearest (cid_dists_closest): the same walk, and instead of the store every pair of the tile becomes the key of k_dists_best —
+// differ << shift_differ | (L - compared) << shift_compared | j, the same shifts — or kDistsNoBest when it is no CANDIDATE: a row past
+// the launch, j >= A, j == i, compared < q.min_compared (>= 1) or differ > q.max_differ.  For a fixed row the keys of its candidates are
+// distinct (j is part of them) and their order is the order asked for: differ ascending, compared descending, j ascending.  A row's 64
+// columns of the tile sit in 16 adjacent tx lanes x 4 registers, and the tile's q.k (<= 64) least keys of the row come out in q.k rounds
+// of "the least key at or above floor": a minimum over the thread's four registers, four xor shuffles over the row's 16 lanes, and
+// floor = that minimum + 1 — the order is strict, so nothing is removed between rounds; once the minimum is kDistsNoBest the floor stays
+// there and so does every later round's result.  The four rows of a thread go through a round together (16 keys, 32 registers: the
+// walk's counters are dead by then).  Lane tx = 0 stores round n of local row r to part[(r * tiles + bx) * k + n]: every slot of every
+// row of the launch is written by exactly one lane — part needs no preset, there is no atomic and no result depends on scheduling.
+// k_dists_closest_merge puts a row's tiles together.
+__global__ __launch_bounds__(kBlock) void k_dists_closest(DistsParams p, DistsClosestParams q) {
+    const uint32_t tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
+    const uint64_t col_base = (uint64_t)blockIdx.x * kDistsTile, row_base = (uint64_t)p.row0 + (uint64_t)blockIdx.y * kDistsTile;
+    uint32_t eq[4][4], cmp[4][4];
+    dists_tile_walk(p, ty, tx, row_base, col_base, eq, cmp);
+    unsigned long long key[4][4], floor[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const uint64_t local = (uint64_t)blockIdx.y * kDistsTile + 4u * ty + (uint32_t)r;   // the row within [row0, row0 + n_rows)
+        const uint64_t i = row_base + 4u * ty + (uint32_t)r;
+        floor[r] = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const uint64_t j = col_base + 4u * tx + (uint32_t)c;
+            const uint32_t differ = cmp[r][c] - eq[r][c];
+            const bool cand = local < p.n_rows && j < p.A && j != i && cmp[r][c] >= q.min_compared && differ <= q.max_differ;
+            key[r][c] = cand ? ((unsigned long long)differ << q.shift_differ) | ((unsigned long long)(p.L - cmp[r][c]) << q.shift_compared) | j
+                             : kDistsNoBest;
+        }
+    }
+    const uint64_t tiles = gridDim.x;
+    for (uint32_t n = 0; n < q.k; ++n) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            unsigned long long m = kDistsNoBest;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) m = (key[r][c] >= floor[r] && key[r][c] < m) ? key[r][c] : m;
+#pragma unroll
+            for (int x = 1; x < 16; x <<= 1) {
+                const unsigned long long o = __shfl_xor(m, x, 16);
+                m = o < m ? o : m;
+            }
+            floor[r] = m == kDistsNoBest ? m : m + 1;
+            const uint64_t local = (uint64_t)blockIdx.y * kDistsTile + 4u * ty + (uint32_t)r;
+            if (tx == 0 && local < p.n_rows) q.part[(local * tiles + blockIdx.x) * q.k + n] = m;
+        }
+    }
+}
+
+// One level of the merge: `in` holds, per row, n_lists lists of k keys, each ascending with kDistsNoBest behind its last key, and no key
+// but that one twice in a row; a wave takes 64 adjacent lists of a row — lane t the list 64 g + t, its head in a register — and gives
+// their k least keys, ascending, as list g of the row in `out` (n_groups = ceil(n_lists / 64) lists a row).  A round is the minimum of
+// the 64 heads by six xor shuffles; the one lane whose head it is moves on to its list's next key (none when it is kDistsNoBest: every
+// head is, and stays).  Lane n keeps round n's key and the k of them go out in one store.  Level by level a row's lists become one: its
+// k nearest.  Nothing is shared between waves: no LDS, no barrier, no atomic.
+__global__ __launch_bounds__(kBlock) void k_dists_closest_merge(const unsigned long long *in, unsigned long long *out, uint64_t n_rows,
+                                                                uint64_t n_lists, uint64_t n_groups, uint32_t k) {
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint64_t job = (uint64_t)blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+    if (job >= n_rows * n_groups) return;   // wave-uniform
+    const uint64_t row = job / n_groups, g = job % n_groups;
+    const uint64_t t = g * kWave + lane;
+    const unsigned long long *list = in + (row * n_lists + (t < n_lists ? t : 0)) * k;
+    uint32_t cur = 0;
+    unsigned long long head = t < n_lists ? list[0] : kDistsNoBest, mine = kDistsNoBest;
+    for (uint32_t n = 0; n < k; ++n) {
+        unsigned long long m = head;
+#pragma unroll
+        for (int x = 1; x < (int)kWave; x <<= 1) {
+            const unsigned long long o = __shfl_xor(m, x, kWave);
+            m = o < m ? o : m;
+        }
+        if (lane == n) mine = m;
+        if (head == m && m != kDistsNoBest) {
+            ++cur;
+            head = cur < k ? list[cur] : kDistsNoBest;
+        }
+    }
+    if (lane < k) out[job * k + lane] = mine;
+}
+
 // ------------------------------------------------------------------------------------------------
 // launchers
 
@@ -302,6 +384,26 @@ hipError_t launch_dists_best(DistsParams p, DistsBestParams b, hipStream_t strea
         e = hipGetLastError();
     }
     return e;
+}
+
+hipError_t launch_dists_closest(const DistsParams &p, DistsClosestParams q, hipStream_t stream) {
+    if (p.n_rows == 0 || p.A == 0) return hipSuccess;
+    const uint32_t row_tiles = (p.n_rows + kDistsTile - 1) / kDistsTile;
+    if (row_tiles > kDistsMaxRowTiles || (uint64_t)p.row0 + p.n_rows > p.A) return hipErrorInvalidValue;
+    if (q.k == 0 || q.k > kDistsClosestMax || q.min_compared == 0 || !q.part) return hipErrorInvalidValue;
+    if (!dists_best_shifts(p.A, p.L, &q.shift_differ, &q.shift_compared)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dists_closest, dim3((unsigned)(p.Ap / kDistsTile), row_tiles), dim3(kBlock), 0, stream, p, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_dists_closest_merge(const unsigned long long *in, unsigned long long *out, uint64_t n_rows, uint64_t n_lists, uint32_t k,
+                                      hipStream_t stream) {
+    if (n_rows == 0) return hipSuccess;
+    if (!in || !out || n_lists == 0 || k == 0 || k > kDistsClosestMax) return hipErrorInvalidValue;
+    const uint64_t n_groups = (n_lists + kWave - 1) / kWave, blocks = (n_rows * n_groups + kBlock / kWave - 1) / (kBlock / kWave);
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dists_closest_merge, dim3((unsigned)blocks), dim3(kBlock), 0, stream, in, out, n_rows, n_lists, n_groups, k);
+    return hipGetLastError();
 }
 
 }  // namespace cid

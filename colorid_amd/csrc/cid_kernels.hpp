@@ -344,6 +344,20 @@ struct DistsWithinParams {
     uint32_t max_differ, min_compared, upper;
 };
 hipError_t launch_dists_within(const DistsParams &p, const DistsWithinParams &w, hipStream_t stream);
+// The K nearest over the same arrays (p's differ and compared are not read): for every row i of [row0, row0 + n_rows) and every column
+// tile t, part[((i - row0) * (Ap / 64) + t) * k + n] = the n-th least key (k_dists_best's, the same shifts: the launcher fills them in) over
+// the tile's columns j != i, j < A with compared >= min_compared (>= 1) and differ <= max_differ, or kDistsNoBest past the last of them.
+// Every one of those slots is written: part needs no preset.  1 <= k <= kDistsClosestMax; at most kDistsMaxRowTiles tiles of 64 rows a
+// launch.  launch_dists_closest_merge: one level of the merge — per row n_lists such lists of k keys in, ceil(n_lists / 64) out, list g
+// the k least keys of the lists [64 g, 64 g + 64) in order; repeated until one list a row is left, that is the row's k nearest.
+constexpr uint32_t kDistsClosestMax = 64;   // CID_DISTS_CLOSEST_MAX; no more than a tile's 64 columns: a tile's list is k long, not min(k, 64)
+struct DistsClosestParams {
+    unsigned long long *part;      // [n_rows][Ap / 64][k]
+    uint32_t k, max_differ, min_compared, shift_differ, shift_compared;
+};
+hipError_t launch_dists_closest(const DistsParams &p, DistsClosestParams q, hipStream_t stream);
+hipError_t launch_dists_closest_merge(const unsigned long long *in, unsigned long long *out, uint64_t n_rows, uint64_t n_lists, uint32_t k,
+                                      hipStream_t stream);
 hipError_t launch_get_rows(const uint64_t *mat, uint32_t rs, const uint64_t *d_row_ids, uint32_t *d_words, uint32_t w32,
                            uint64_t n_rows, hipStream_t stream);
 hipError_t launch_insert_kmers(const InsertParams &p, hipStream_t stream);

@@ -478,6 +478,9 @@ struct AlleleCodes {
 // With within, after the matrices and before the clusters, PREFIX.within.tsv: a, b, differ, compared for every unordered pair with
 // compared >= min_compared and differ <= within_threshold, a before b in the table, in order of (a's row, b's row), written block of
 // rows by block of rows from cid_dists_within(CID_DISTS_UPPER): only those pairs leave the device.
+// With closest = K (1 .. CID_DISTS_CLOSEST_MAX), after that, PREFIX.closest.tsv: accession, neighbour, differ, compared — the accessions
+// in table order, under each its up to K nearest (cid_dists_closest: the others with compared >= min_compared and, with within,
+// differ <= within_threshold; fewer differing loci first, then more shared loci, then table order), or one line of dashes.
 struct DistsOptions {
     bool cluster = false;
     uint64_t threshold = 0;      // --cluster T
@@ -486,13 +489,16 @@ struct DistsOptions {
     bool no_matrices = false;    // --no-matrices (the caller refuses it without mst, cluster or within)
     bool within = false;
     uint64_t within_threshold = 0;   // --within T
+    uint32_t closest = 0;            // --closest K (0: not asked for)
 };
 void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, const DistsOptions &opt, void (*phase)(const char *) = nullptr);
 // `dists --query` (t, q from AlleleCodes::from_files; opt.within_threshold and opt.min_compared): PREFIX.query.tsv — query, neighbour, in
 // (table / query), differ, compared: for every query accession in file order its neighbours among the table's and the other query
 // accessions, nearest first (fewer differing loci, then more shared loci, then table before query, each in file order); one line of
-// dashes for a query accession without a neighbour.  One device table of all accessions, cid_dists_within over the query's rows.  ctx is
-// not used (may be null) when the query has no accession.  Says on stderr what it aligned, found and wrote.
+// dashes for a query accession without a neighbour.  One device table of all accessions, cid_dists_within over the query's rows.  With
+// opt.closest = K a query accession's list is its first K lines (cid_dists_closest over the query's rows instead), within the threshold
+// when opt.within is set and whatever the distance when it is not.  ctx is not used (may be null) when the query has no accession.
+// Says on stderr what it aligned, found and wrote.
 void dists_query_run(cid_ctx *ctx, const AlleleCodes &t, const QueryAlign &q, const std::string &prefix, const DistsOptions &opt,
                      void (*phase)(const char *) = nullptr);
 

@@ -18,6 +18,11 @@
 //                on TABLE's loci, matched by name, through the same encoder (AlleleCodes::from_files); the device holds the one table of
 //                both and cid_dists_within answers for the query's rows: per query accession its neighbours among all the others,
 //                nearest first (differ, more compared first, table before query, file order), or one line of dashes
+//   PREFIX.closest.tsv (--closest K [--within T] [--min-compared M], K = 1 .. 64)   accession, neighbour, differ, compared: the accessions in
+//                table order and under each its up to K nearest among the others with compared >= M (and differ <= T), nearest first in
+//                the order of PREFIX.query.tsv; an accession without one gets a line of dashes: cid_dists_closest, K x 16 bytes an
+//                accession over the bus.  With --query it cuts every query accession's list in PREFIX.query.tsv to its first K lines,
+//                and --within is then optional: without it the K nearest however far they are
 //   --no-matrices   the two A x A files are not made; rows are then fetched for --cluster only
 #include "colorid_host.hpp"
 
@@ -335,6 +340,23 @@ uint64_t within_blocks(cid_dists *d, size_t r0, size_t r1, uint64_t threshold, u
     return total;
 }
 
+constexpr uint32_t kNoNeighbour = 0xFFFFFFFFu;   // cid_dists_edge.b of a rank past an accession's last candidate
+
+// cid_dists_closest over the rows [r0, r1) in blocks of 4096 rows; `sink` gets every row's k entries (the ranks past its candidates
+// have b = kNoNeighbour).  Without within the distance is not bounded.
+template <typename Sink>
+void closest_blocks(cid_dists *d, size_t r0, size_t r1, const DistsOptions &opt, uint64_t min_compared, Sink sink) {
+    const uint32_t T = opt.within ? (uint32_t)std::min<uint64_t>(opt.within_threshold, 0xFFFFFFFFull) : 0xFFFFFFFFu;
+    const uint32_t M = (uint32_t)std::min<uint64_t>(min_compared, 0xFFFFFFFFull), K = opt.closest;
+    const size_t block = 4096;
+    std::vector<cid_dists_edge> buf(std::min(block, r1 - r0) * K);
+    for (size_t r = r0; r < r1; r += block) {
+        const size_t nr = std::min(block, r1 - r);
+        if (cid_dists_closest(d, (uint32_t)r, (uint32_t)nr, K, T, M, buf.data()) != CID_OK) die("cid_dists_closest: %s", cid_last_error());
+        for (size_t i = 0; i < nr; ++i) sink(r + i, &buf[i * K]);
+    }
+}
+
 }  // namespace
 
 void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, const DistsOptions &opt, void (*phase)(const char *)) {
@@ -434,6 +456,32 @@ void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, co
         fprintf(stderr, "dists: %llu pairs within %llu differing loci (at least %llu shared), written to %s\n", (unsigned long long)n_pairs,
                 (unsigned long long)opt.within_threshold, (unsigned long long)min_compared, w_path.c_str());
     }
+    if (opt.closest) {
+        const std::string n_path = prefix + ".closest.tsv";
+        FILE *fn = dists_out(n_path);
+        fputs("accession\tneighbour\tdiffer\tcompared\n", fn);
+        uint64_t n_lines = 0;
+        size_t without = 0;
+        auto none = [&](size_t a) {
+            fprintf(fn, "%s\t-\t-\t-\n", t.accessions[a].c_str());
+            ++n_lines;
+            ++without;
+        };
+        if (d)
+            closest_blocks(d, 0, A, opt, min_compared, [&](size_t a, const cid_dists_edge *e) {
+                if (e[0].b == kNoNeighbour) none(a);
+                for (uint32_t k = 0; k < opt.closest && e[k].b != kNoNeighbour; ++k, ++n_lines)
+                    fprintf(fn, "%s\t%s\t%u\t%u\n", t.accessions[a].c_str(), t.accessions[e[k].b].c_str(), e[k].differ, e[k].compared);
+            });
+        else
+            for (size_t a = 0; a < A; ++a) none(a);   // no locus: nothing is compared
+        dists_close(fn, n_path);
+        if (phase) phase("closest accessions found and written");
+        std::string bound;
+        if (opt.within) bound = " within " + std::to_string(opt.within_threshold) + " differing loci";
+        fprintf(stderr, "dists: %zu accessions, the %u closest of each%s (at least %llu shared): %llu lines, %zu accessions without a neighbour, written to %s\n",
+                A, opt.closest, bound.c_str(), (unsigned long long)min_compared, (unsigned long long)n_lines, without, n_path.c_str());
+    }
     if (opt.cluster) {
         std::vector<uint32_t> size(A, 0), number(A, 0);
         for (size_t i = 0; i < A; ++i) ++size[find((uint32_t)i)];
@@ -474,6 +522,8 @@ void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, co
 // among all of them (flags = 0: a query accession's pair with another query accession is named from both ends).  Per query accession the
 // neighbours are put nearest first: fewer differing loci, then more shared loci, then the lower row — database accessions come before
 // query accessions, each in file order — which for a fixed query is the order of the `nearest` column and of the forest's edge key.
+// With opt.closest = K the list is cut to its first K: cid_dists_closest over the same rows, which gives them in that order — bounded by
+// the threshold only when opt.within is set.
 void dists_query_run(cid_ctx *ctx, const AlleleCodes &t, const QueryAlign &q, const std::string &prefix, const DistsOptions &opt,
                      void (*phase)(const char *)) {
     const size_t A = t.accessions.size(), L = t.loci.size(), D = q.n_table, Q = A - D;
@@ -491,7 +541,15 @@ void dists_query_run(cid_ctx *ctx, const AlleleCodes &t, const QueryAlign &q, co
         if (cid_dists_create(ctx, t.codes.data(), (uint32_t)A, (uint32_t)L, &d) != CID_OK) die("cid_dists_create: %s", cid_last_error());
         if (phase) phase("allele codes uploaded");
         std::vector<cid_dists_edge> run;
-        n_found = within_blocks(d, D, A, opt.within_threshold, min_compared, 0, [&](const cid_dists_edge *e, size_t n) {
+        if (opt.closest)   // the first K lines of every list: cid_dists_closest's order is the file's
+            closest_blocks(d, D, A, opt, min_compared, [&](size_t a, const cid_dists_edge *e) {
+                for (uint32_t k = 0; k < opt.closest && e[k].b != kNoNeighbour; ++k, ++n_found)
+                    fprintf(fq, "%s\t%s\t%s\t%u\t%u\n", t.accessions[a].c_str(), t.accessions[e[k].b].c_str(), e[k].b < D ? "table" : "query", e[k].differ,
+                            e[k].compared);
+                if (e[0].b != kNoNeighbour) next = a + 1;
+                else none_up_to(a + 1);
+            });
+        else n_found = within_blocks(d, D, A, opt.within_threshold, min_compared, 0, [&](const cid_dists_edge *e, size_t n) {
             for (size_t k = 0; k < n;) {   // (a block holds whole rows: an accession's neighbours are one run of it)
                 size_t end = k;
                 while (end < n && e[end].a == e[k].a) ++end;
@@ -514,6 +572,16 @@ void dists_query_run(cid_ctx *ctx, const AlleleCodes &t, const QueryAlign &q, co
     none_up_to(A);
     dists_close(fq, q_path);
     if (phase) phase("neighbours of the query accessions found and written");
+    if (opt.closest) {
+        std::string bound;
+        if (opt.within) bound = " within " + std::to_string(opt.within_threshold) + " differing loci";
+        fprintf(stderr,
+                "dists: %zu query accessions against %zu, %zu loci in common (%zu only in %s, %zu only in %s); %llu neighbours, the %u closest of each%s "
+                "(at least %llu shared), %zu queries without one, written to %s\n",
+                Q, D, q.common, q.only_table, q.table.c_str(), q.only_query, q.query.c_str(), (unsigned long long)n_found, opt.closest, bound.c_str(),
+                (unsigned long long)min_compared, without, q_path.c_str());
+        return;
+    }
     fprintf(stderr,
             "dists: %zu query accessions against %zu, %zu loci in common (%zu only in %s, %zu only in %s); %llu neighbours within %llu differing loci "
             "(at least %llu shared), %zu queries without one, written to %s\n",

@@ -642,16 +642,28 @@ uint64_t loci_arg(const Args &a, const char *key) {
     if (v.empty() || *end || n < 0 || errno) die("error: --%s expects a number of loci (0 or more), got '%s'", key, v.c_str());
     return (uint64_t)n;
 }
-// what --cluster, --within, --min-compared, --mst and --no-matrices ask for; refuses --min-compared without --cluster, --mst or --within,
-// and --no-matrices when nothing else would be written
+// --closest K (search --dists, dists): a number of neighbours, 1 .. CID_DISTS_CLOSEST_MAX
+uint32_t closest_arg(const Args &a) {
+    const std::string &v = a.one("closest");
+    char *end = nullptr;
+    errno = 0;
+    const long long n = strtoll(v.c_str(), &end, 10);
+    if (v.empty() || *end || errno || n < 1 || n > (long long)CID_DISTS_CLOSEST_MAX)
+        die("error: --closest expects a number of neighbours from 1 to %u, got '%s' (--within T lists every accession within a distance, however many)",
+            CID_DISTS_CLOSEST_MAX, v.c_str());
+    return (uint32_t)n;
+}
+// what --cluster, --within, --closest, --min-compared, --mst and --no-matrices ask for; refuses --min-compared without --cluster, --mst,
+// --within or --closest, and --no-matrices when nothing else would be written
 DistsOptions dists_options(const Args &a) {
     DistsOptions o;
     o.mst = a.flags.count("mst") != 0;
     o.no_matrices = a.flags.count("no-matrices") != 0;
-    if (a.has("min-compared") && !a.has("cluster") && !o.mst && !a.has("within"))
-        die("error: --min-compared needs --cluster T (it is the least number of loci two accessions must share to be linked), --mst or --within T");
-    if (o.no_matrices && !a.has("cluster") && !o.mst && !a.has("within"))
-        die("error: --no-matrices needs --mst or --cluster T or --within T (without the two matrices nothing would be written)");
+    if (a.has("min-compared") && !a.has("cluster") && !o.mst && !a.has("within") && !a.has("closest"))
+        die("error: --min-compared needs --cluster T (it is the least number of loci two accessions must share to be linked), --mst or --within T, or --closest K");
+    if (o.no_matrices && !a.has("cluster") && !o.mst && !a.has("within") && !a.has("closest"))
+        die("error: --no-matrices needs --mst or --cluster T or --within T (without the two matrices nothing would be written), or --closest K");
+    if (a.has("closest")) o.closest = closest_arg(a);
     if (a.has("cluster")) { o.cluster = true; o.threshold = loci_arg(a, "cluster"); }
     if (a.has("within")) { o.within = true; o.within_threshold = loci_arg(a, "within"); }
     if (a.has("min-compared")) o.min_compared = loci_arg(a, "min-compared");
@@ -677,7 +689,7 @@ int cmd_search(int argc, char **argv) {
                                                      {0, "nearest", false, false}, {0, "dists", false, false},
                                                      {0, "cluster", true, false}, {0, "min-compared", true, false},
                                                      {0, "mst", false, false}, {0, "no-matrices", false, false}, {0, "within", true, false},
-                                                     {0, "gather", true, false}, {0, "gather-min", true, false}, {0, "gather-max", true, false}}));
+                                                     {0, "closest", true, false}, {0, "gather", true, false}, {0, "gather-min", true, false}, {0, "gather-max", true, false}}));
     for (const char *req : {"bigsi", "query"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const std::vector<std::string> files1 = a.values.at("query");
@@ -717,13 +729,14 @@ int cmd_search(int argc, char **argv) {
         if (a.has("gpus") || a.has("devices") || a.has("placement") || cli_env("COLORID_REDUCE"))
             die("error: --nearest runs on one GPU: it does not go with --gpus, --devices, --placement or COLORID_REDUCE");
     }
-    // -s -m --alleles PREFIX --dists [--cluster T] [--within T] [--mst] [--min-compared M] [--no-matrices]: after the tables, the pairwise
-    // allele distances of the raw table's accessions (the clean table's with --max-missing), the pairs within T, their clusters and their
-    // minimum spanning forest, on this run's context: the files `colorid dists -t PREFIX.raw.tsv` writes.  Refused here, before the GPU context is made
+    // -s -m --alleles PREFIX --dists [--cluster T] [--within T] [--closest K] [--mst] [--min-compared M] [--no-matrices]: after the tables,
+    // the pairwise allele distances of the raw table's accessions (the clean table's with --max-missing), the pairs within T, every
+    // accession's K nearest, their clusters and their minimum spanning forest, on this run's context: the files `colorid dists -t PREFIX.raw.tsv` writes.  Refused here, before the GPU context is made
     const bool dists = a.flags.count("dists") != 0;
     if (dists && !a.has("alleles")) die("error: --dists needs -s -m --alleles PREFIX (it writes PREFIX.dists.tsv from the allele table)");
     if (!dists && a.has("cluster")) die("error: --cluster needs --dists (it clusters the allele distances)");
     if (!dists && a.has("within")) die("error: --within needs --dists (it lists the pairs of accessions at most T alleles apart)");
+    if (!dists && a.has("closest")) die("error: --closest needs --dists (it lists every accession's K nearest by allele distance)");
     if (!dists && a.flags.count("mst")) die("error: --mst needs --dists (it is the minimum spanning forest of the allele distances)");
     if (!dists && a.flags.count("no-matrices")) die("error: --no-matrices needs --dists (it leaves out PREFIX.dists.tsv and PREFIX.compared.tsv)");
     const DistsOptions dists_opt = dists_options(a);
@@ -822,20 +835,24 @@ int cmd_alleles(int argc, char **argv) {
     return 0;
 }
 
-// dists: -t TABLE -o PREFIX [--cluster T] [--within T] [--mst] [--min-compared M] [--no-matrices] — PREFIX.dists.tsv and
-// PREFIX.compared.tsv (and PREFIX.clusters.tsv; PREFIX.within.tsv; PREFIX.mst.tsv and PREFIX.mst.nwk) from a table in the form of
+// dists: -t TABLE -o PREFIX [--cluster T] [--within T] [--closest K] [--mst] [--min-compared M] [--no-matrices] — PREFIX.dists.tsv and
+// PREFIX.compared.tsv (and PREFIX.clusters.tsv; PREFIX.within.tsv; PREFIX.closest.tsv; PREFIX.mst.tsv and PREFIX.mst.nwk) from a table in the form of
 // PREFIX.raw.tsv / PREFIX.clean.tsv.  The flags are checked before the table is read, the table is read and checked before the GPU is
 // opened; a table without accessions or without loci needs none.
 // dists: -t TABLE --query TABLE2 -o PREFIX --within T [--min-compared M] — PREFIX.query.tsv alone: the neighbours of TABLE2's accessions
 // among TABLE's and each other, the loci matched by name; a query table without accessions needs no GPU.
+// --closest K (1 .. 64, checked with the flags): every accession's K nearest — PREFIX.closest.tsv, within T where --within is given too —
+// and with --query, where it may stand in for --within, the first K lines of every query accession's list.
 int cmd_dists(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, {{'t', "table", true, false}, {'o', "output", true, false}, {0, "cluster", true, false},
                                          {0, "min-compared", true, false}, {0, "mst", false, false}, {0, "no-matrices", false, false},
-                                         {0, "within", true, false}, {0, "query", true, false}, {0, "device", true, false}});
+                                         {0, "within", true, false}, {0, "closest", true, false}, {0, "query", true, false},
+                                         {0, "device", true, false}});
     for (const char *req : {"table", "output"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     if (a.has("query")) {
-        if (!a.has("within")) die("error: --query needs --within T (it lists the query accessions' neighbours at most T alleles apart)");
+        if (!a.has("within") && !a.has("closest"))
+            die("error: --query needs --within T or --closest K (it lists the query accessions' neighbours at most T alleles apart, or the K nearest of each)");
         if (a.has("cluster")) die("error: --query writes PREFIX.query.tsv alone and does not go with --cluster");
         if (a.flags.count("mst")) die("error: --query writes PREFIX.query.tsv alone and does not go with --mst");
         if (a.flags.count("no-matrices")) die("error: --query writes PREFIX.query.tsv alone and does not go with --no-matrices (no matrix is made)");
@@ -1179,12 +1196,18 @@ int main(int argc, char **argv) {
                "                             accessions that share at least M (1) loci and differ at no more than T of them, a before b in the\n"
                "                             table: the pairs are found on the GPU and only they come back (goes with --no-matrices); their\n"
                "                             connected components are the clusters of --cluster T\n"
+               "                             --dists --closest K [--within T] [--min-compared M]: PREFIX.closest.tsv, accession, neighbour, differ,\n"
+               "                             compared: under every accession its K (1 .. 64) nearest among those that share at least M (1) loci\n"
+               "                             with it (and differ at no more than T), fewest differing loci first, then most shared loci, then\n"
+               "                             table order; a line of - for none; found on the GPU, no matrix is made (goes with --no-matrices)\n"
                "    dists -t TABLE -o PREFIX [--cluster T] [--mst] [--min-compared M] [--no-matrices]   the same files from a table in the form\n"
-               "                             of PREFIX.raw.tsv; [--within T] as above\n"
+               "                             of PREFIX.raw.tsv; [--within T] [--closest K] as above\n"
                "    dists -t TABLE --query TABLE2 -o PREFIX --within T [--min-compared M]   PREFIX.query.tsv alone: for every accession of TABLE2\n"
                "                             the accessions of TABLE and of TABLE2 within T, nearest first (query, neighbour, in = table or\n"
                "                             query, differ, compared; a line of - for none); loci are matched by name: TABLE's are used, one that\n"
                "                             TABLE2 lacks is no call there, one only TABLE2 has is ignored\n"
+               "    dists -t TABLE --query TABLE2 -o PREFIX --closest K [--within T] [--min-compared M]   the same file, every list cut to its K\n"
+               "                             nearest; without --within however far they are\n"
                "    alleles -r ROWS -o PREFIX [--max-missing N]   the same tables from the saved stdout of a `search -s -m` run; no GPU\n\n"
                "INDEX MAINTENANCE:\n"
                "    collapse -b OUT -i idx.bxi -g groups.tsv      several accessions as one colour (groups.tsv: accession TAB group per line;\n"

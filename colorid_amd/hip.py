@@ -467,6 +467,16 @@ class Dists:
                 return out[:n.value].copy()
             cap = n.value                                     # come back with room
 
+    def closest(self, k, max_differ=0xFFFFFFFF, min_compared=1, row0=0, n_rows=None):
+        """every accession's k nearest (cid_dists_closest) -> [n_rows, k, 4] uint32: a, b, differ, compared; per row a its candidates (b != a,
+        compared >= min_compared, differ <= max_differ) by (differ, more compared first, b), b = 0xFFFFFFFF past the last of them"""
+        if n_rows is None:
+            n_rows = self.n_acc - row0
+        out = np.zeros((max(n_rows, 0), max(k, 0), 4), np.uint32)      # cid_dists_edge: a, b, differ, compared
+        buf = out if out.size else np.zeros(4, np.uint32)
+        check(self.lib.cid_dists_closest(self.h, row0, n_rows, k, max_differ, min_compared, _p(buf)))
+        return out
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.cid_dists_destroy(self.h)

@@ -239,6 +239,21 @@ int cid_dists_forest(cid_dists *, uint32_t min_compared, cid_dists_edge *edges, 
 #define CID_DISTS_UPPER 1u   /* only pairs with b > a: each unordered pair of a symmetric query once */
 int cid_dists_within(cid_dists *, uint32_t row0, uint32_t n_rows, uint32_t max_differ, uint32_t min_compared,
                      uint32_t flags, cid_dists_edge *out, size_t cap, uint64_t *n_found);
+/* Every accession's K nearest (`dists --closest K`): for every a in [row0, row0 + n_rows) the CANDIDATES are the b != a with
+ * compared(a, b) >= min_compared (>= 1) and differ(a, b) <= max_differ (0xFFFFFFFF: no bound), and out[(a - row0) * k + r] is the
+ * candidate of rank r in the order differ ascending, then compared DESCENDING, then b ascending — cid_dists_best's order, and the order
+ * of PREFIX.query.tsv — as {a, b, differ, compared}.  Ranks past the number of candidates are {a, 0xFFFFFFFF, 0, 0}, the "none" of
+ * cid_dists_best.  The order is strict for a fixed a, so the result is a pure function of the table and the arguments: the same bytes on
+ * every call, however the device splits the work.  With k = 1 and no bound it is cid_dists_best with every accession its own component.
+ * n_rows == 0 is a no-op.  Only n_rows x k x 8 bytes cross the bus; device memory beside the table: n_rows x ceil(n_acc / 64) x k x 8
+ * bytes and a 64th of that again, the rows cut into slices of whole 64-row tiles inside the call so that it stays within
+ * "dense_report_bytes" (at least one tile a slice, whatever the budget).
+ * CID_ERR_INVALID: null handle, out == NULL with n_rows > 0, k == 0, min_compared == 0, row0 + n_rows > n_acc.
+ * CID_ERR_UNSUPPORTED, before anything is launched: k > CID_DISTS_CLOSEST_MAX (cid_dists_within gives longer lists); a table beyond the
+ * LIMIT of cid_dists_best's key. */
+#define CID_DISTS_CLOSEST_MAX 64u
+int cid_dists_closest(cid_dists *, uint32_t row0, uint32_t n_rows, uint32_t k, uint32_t max_differ, uint32_t min_compared,
+                      cid_dists_edge *out /* n_rows x k */);
 void cid_dists_destroy(cid_dists *);
 
 /* ---- a5: proportional search, the hot loop of batch_search_pe::batch_search

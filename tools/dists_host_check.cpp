@@ -1,9 +1,11 @@
 // Stand-alone host check of colorid_amd/csrc/host/dists.cpp under ASan + UBSan, no GPU and no libcolorid_hip.so: the table parser, the
 // allele encoder (both entrances), the row-block driver, the clustering and the forest and Newick writers, with a plain C++ cid_dists_*
-// behind them (the forest: Kruskal over the stand-in's own loop; the neighbour list: the same loop, filtered).
-//   make -C tools bin/dists_host_check ;  tools/bin/dists_host_check TABLE PREFIX [T [M [mst [no-matrices]]]] [within=T] [query=TABLE2]
+// behind them (the forest: Kruskal over the stand-in's own loop; the neighbour list: the same loop, filtered; the K nearest: the same
+// loop, sorted and cut).
+//   make -C tools bin/dists_host_check ;  tools/bin/dists_host_check TABLE PREFIX [T [M [mst [no-matrices]]]] [within=T] [closest=K] [query=TABLE2]
 //   (writes PREFIX.dists.tsv, .compared.tsv, .clusters.tsv; T = - for no clusters; with mst also PREFIX.mst.tsv, .mst.nwk; with within=T
-//   also PREFIX.within.tsv; with query=TABLE2 — and within=T — PREFIX.query.tsv alone, the two tables aligned by AlleleCodes::from_files)
+//   also PREFIX.within.tsv; with closest=K also PREFIX.closest.tsv; with query=TABLE2 — and within=T or closest=K — PREFIX.query.tsv
+//   alone, the two tables aligned by AlleleCodes::from_files)
 #include <algorithm>
 #include <cstdarg>
 #include <numeric>
@@ -100,6 +102,23 @@ int cid_dists_within(cid_dists *d, uint32_t row0, uint32_t n, uint32_t max_diffe
     }
     return 0;
 }
+// the candidates of the loop above, sorted by (differ, more compared first, b) and cut at k; the ranks past them are "none"
+int cid_dists_closest(cid_dists *d, uint32_t row0, uint32_t n, uint32_t k, uint32_t max_differ, uint32_t min_compared, cid_dists_edge *out) {
+    std::vector<uint32_t> differ(d->A), compared(d->A);
+    std::vector<cid_dists_edge> cand;
+    for (uint32_t i = row0; i < row0 + n; ++i) {
+        cid_dists_rows(d, i, 1, differ.data(), compared.data());
+        cand.clear();
+        for (uint32_t j = 0; j < d->A; ++j)
+            if (j != i && compared[j] >= min_compared && differ[j] <= max_differ) cand.push_back(cid_dists_edge{i, j, differ[j], compared[j]});
+        std::sort(cand.begin(), cand.end(), [](const cid_dists_edge &x, const cid_dists_edge &y) {
+            if (x.differ != y.differ) return x.differ < y.differ;
+            return x.compared != y.compared ? x.compared > y.compared : x.b < y.b;
+        });
+        for (uint32_t r = 0; r < k; ++r) out[(size_t)(i - row0) * k + r] = r < cand.size() ? cand[r] : cid_dists_edge{i, 0xFFFFFFFFu, 0, 0};
+    }
+    return 0;
+}
 void cid_dists_destroy(cid_dists *d) { delete d; }
 }
 
@@ -107,9 +126,10 @@ int main(int argc, char **argv) {
     using namespace colorid;
     DistsOptions o;
     std::string query;
-    int kept = 1;   // within=T and query=TABLE2 come out of the positional arguments
+    int kept = 1;   // within=T, closest=K and query=TABLE2 come out of the positional arguments
     for (int i = 1; i < argc; ++i) {
         if (strncmp(argv[i], "within=", 7) == 0) { o.within = true; o.within_threshold = strtoull(argv[i] + 7, nullptr, 10); }
+        else if (strncmp(argv[i], "closest=", 8) == 0) o.closest = (uint32_t)strtoul(argv[i] + 8, nullptr, 10);
         else if (strncmp(argv[i], "query=", 6) == 0) query = argv[i] + 6;
         else argv[kept++] = argv[i];
     }
