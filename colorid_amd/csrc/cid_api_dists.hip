@@ -1,7 +1,7 @@
 // C ABI of libcolorid_hip.so, part 6: `colorid dists` — the pairwise allele distances of a cgMLST table: for two accessions the loci both
 // have a call at (compared) and those of them where the calls differ (differ), and the minimum spanning forest of the accessions under
-// them (cid_dists_best, cid_dists_forest), the pairs within a threshold as a list (cid_dists_within), and every accession's K nearest
-// (cid_dists_closest).  Kernels: cid_dists.hip.
+// them (cid_dists_best, cid_dists_forest), the pairs within a threshold as a list (cid_dists_within), every accession's K nearest
+// (cid_dists_closest), and the pairs counted by compared and by differ (cid_dists_hist).  Kernels: cid_dists.hip.
 #include "cid_api_common.hpp"
 
 #include <numeric>
@@ -410,6 +410,43 @@ int cid_dists_closest(cid_dists *d, uint32_t row0, uint32_t n_rows, uint32_t k, 
             for (uint32_t x = 0; x < k; ++x) out[(r + i) * k + x] = key.unpack(row0 + (uint32_t)(r + i), keys[i * k + x]);
     }
     if (e != hipSuccess) return fail(CID_ERR_HIP, "cid_dists_closest: %s", hipGetErrorString(e));
+    return CID_OK;
+}
+
+// The two histograms.  Device memory: 2 x (n_loci + 1) x 8 bytes from the ctx's block cache, differ's bins and then compared's, set to zero
+// on the ctx's stream before the one launch; one copy back and one stream wait.  The rows are not sliced: what comes back does not grow
+// with them, and launch_dists_hist takes any number.
+int cid_dists_hist(cid_dists *d, uint32_t row0, uint32_t n_rows, uint32_t min_compared, uint32_t flags, uint64_t *differ_hist,
+                   uint64_t *compared_hist) {
+    if (!d) return fail(CID_ERR_INVALID, "null argument");
+    if (!differ_hist) return fail(CID_ERR_INVALID, "null differ_hist");
+    if (min_compared == 0) return fail(CID_ERR_INVALID, "min_compared = 0: two accessions without a common locus have no distance to count");
+    if ((uint64_t)row0 + n_rows > d->n_acc)
+        return fail(CID_ERR_INVALID, "rows [%u, %llu) of a table of %u accessions", row0, (unsigned long long)row0 + n_rows, d->n_acc);
+    if (flags & ~CID_DISTS_UPPER) return fail(CID_ERR_INVALID, "unknown flags 0x%x", flags & ~CID_DISTS_UPPER);
+    const size_t bins = (size_t)d->n_loci + 1;
+    std::fill(differ_hist, differ_hist + bins, (uint64_t)0);
+    if (compared_hist) std::fill(compared_hist, compared_hist + bins, (uint64_t)0);
+    if (n_rows == 0) return CID_OK;
+    cid_ctx *c = d->ctx;
+    HIP_TRY(hipSetDevice(c->device));
+    Scratch<unsigned long long> dev(c);
+    const int rc = dev.alloc(2 * bins);
+    if (rc != CID_OK) return rc;
+    cid::DistsParams p{};
+    p.T = d->codes_t; p.maskT = d->mask_t; p.Ap = d->acc_pad; p.A = d->n_acc; p.L = d->n_loci; p.W = d->n_words;
+    p.row0 = row0; p.n_rows = n_rows;
+    cid::DistsHistParams h{};
+    h.differ_hist = dev.p; h.compared_hist = dev.p + bins; h.min_compared = min_compared; h.upper = flags & CID_DISTS_UPPER;
+    std::vector<unsigned long long> back((compared_hist ? 2 : 1) * bins);
+    hipError_t e = hipMemsetAsync(dev.p, 0, 2 * bins * 8, c->stream);
+    if (e == hipSuccess) e = cid::launch_dists_hist(p, h, c->n_cu, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(back.data(), dev.p, back.size() * 8, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);   // (also after a failed launch: back is this frame's)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(CID_ERR_HIP, "cid_dists_hist: %s", hipGetErrorString(e));
+    std::copy(back.begin(), back.begin() + (ptrdiff_t)bins, differ_hist);
+    if (compared_hist) std::copy(back.begin() + (ptrdiff_t)bins, back.end(), compared_hist);
     return CID_OK;
 }
 

@@ -57,8 +57,9 @@ __global__ __launch_bounds__(kBlock) void k_dists_mask(const uint32_t *codes, ui
 // row accessions past A are staged as missing and never stored, column accessions past A read T's zero padding (tile tails).
 // compared[i][j] = popcount(mask_i & mask_j) over the W mask words, differ = compared - equal.
 // BOUND: equal <= compared <= L < 2^32.
-// The walk is one body (dists_tile_walk) with four epilogues: k_dists_tile stores the counts, k_dists_best keeps a row's best pair,
-// k_dists_within appends the pairs under a threshold to a list, k_dists_closest keeps a row's k best pairs of the tile.
+// The walk is one body (dists_tile_walk) with five epilogues: k_dists_tile stores the counts, k_dists_best keeps a row's best pair,
+// k_dists_within appends the pairs under a threshold to a list, k_dists_closest keeps a row's k best pairs of the tile, k_dists_hist
+// counts the pairs by compared and by differ.
 __device__ __forceinline__ void dists_tile_walk(const DistsParams &p, uint32_t ty, uint32_t tx, uint64_t row_base, uint64_t col_base,
                                                 uint32_t (&eq)[4][4], uint32_t (&cmp)[4][4]) {
     __shared__ __attribute__((aligned(16))) uint32_t s_row[kDistsChunk][kDistsTile];
@@ -328,6 +329,82 @@ __global__ __launch_bounds__(kBlock) void k_dists_closest_merge(const unsigned l
     if (lane < k) out[job * k + lane] = mine;
 }
 
+// The histograms (cid_dists_hist): the same walk, and instead of the store a pair (i, j) is COUNTED when i is a row of the launch, j < A,
+// j != i and — h.upper — j > i: it adds 1 to compared_hist[compared] whatever h.min_compared is (bin 0: the pairs without a common locus)
+// and, when compared >= h.min_compared (>= 1), 1 to differ_hist[differ].  Bins 0 .. L.  A column past A is dropped by j < A and by nothing
+// else: its zero masks give compared = 0, which is a bin.
+// Where the counts go: a workgroup keeps the bins 0 .. kDistsHistWindow - 1 of both histograms as u32 in LDS (2 x 16 KiB beside the walk's
+// 16 KiB) with one LDS atomic per count — 2 x 4 096 a tile against the walk's 2 L LDS reads and 16 L compares a thread — and walks SEVERAL
+// tiles, a contiguous share of the launch's tile list, before it adds its non-zero bins to the global u64 histograms, one 64-bit atomic
+// a bin, once.  A count for a bin at or past the window (L >= 4 096) goes to the global word at once: the one path there is, slow and exact.
+// The tile list: tile t of full mode is (row tile t / C, column tile t % C), C = Ap / 64.  Upper mode lists only the tiles not wholly on
+// or below the diagonal: those of k_dists_within's test with the real first row — column tile bx of row tile by stays when 64 bx + 63 >
+// row0 + 64 by, that is bx >= q0 + by with q0 = (row0 + 1) / 64 — so row tile by has n0 - by of them, n0 = C - q0 (none at all for a last
+// row tile that begins at A - 1 = 64 C - 1), and before it lie by n0 - by (by - 1) / 2: a workgroup finds its first tile by bisection
+// and steps from there.  Workgroup g of G takes the tiles [g share + min(g, rest), ..) — share = n_tiles / G, rest = n_tiles % G, one
+// more for g < rest; everything about the list is uniform over the workgroup.
+// BOUND: a tile adds at most 64 x 64 to one bin, a workgroup owns at most kDistsHistMaxShare = (2^32 - 1) / 4 096 tiles
+// (launch_dists_hist grows the grid beyond that), so no u32 bin wraps; the u64 bins hold at most A^2 < 2^64.
+static_assert(kDistsHistMaxShare * kDistsTile * kDistsTile <= 0xFFFFFFFFull, "k_dists_hist: a workgroup's u32 bins");
+__device__ __forceinline__ uint64_t dists_hist_before(uint64_t by, uint64_t n0) { return by * n0 - by * (by - 1) / 2; }
+
+__global__ __launch_bounds__(kBlock) void k_dists_hist(DistsParams p, DistsHistParams h) {
+    __shared__ uint32_t s_differ[kDistsHistWindow], s_compared[kDistsHistWindow];
+    const uint32_t tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
+    for (uint32_t b = threadIdx.x; b < kDistsHistWindow; b += kBlock) s_differ[b] = s_compared[b] = 0u;
+    __syncthreads();
+    const uint64_t C = p.Ap / kDistsTile, R = ((uint64_t)p.n_rows + kDistsTile - 1) / kDistsTile;
+    const uint64_t q0 = ((uint64_t)p.row0 + 1u) / kDistsTile, n0 = C - q0;
+    const uint64_t share = h.n_tiles / gridDim.x, rest = h.n_tiles % gridDim.x, g = blockIdx.x;
+    const uint64_t t0 = g * share + (g < rest ? g : rest), n_mine = share + (g < rest ? 1u : 0u);
+    uint64_t by, bx;
+    if (h.upper) {
+        uint64_t lo = 0, hi = R - 1;   // the last row tile that begins at or before t0
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi + 1) / 2;
+            if (dists_hist_before(mid, n0) <= t0) lo = mid;
+            else hi = mid - 1;
+        }
+        by = lo;
+        bx = q0 + by + (t0 - dists_hist_before(by, n0));
+    } else {
+        by = t0 / C;
+        bx = t0 % C;
+    }
+    for (uint64_t n = 0; n < n_mine; ++n) {
+        const uint64_t col_base = bx * kDistsTile, row_base = (uint64_t)p.row0 + by * kDistsTile;
+        uint32_t eq[4][4], cmp[4][4];
+        dists_tile_walk(p, ty, tx, row_base, col_base, eq, cmp);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const uint64_t local = by * kDistsTile + 4u * ty + (uint32_t)r;   // the row within [row0, row0 + n_rows)
+            const uint64_t i = row_base + 4u * ty + (uint32_t)r;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const uint64_t j = col_base + 4u * tx + (uint32_t)c;
+                if (!(local < p.n_rows && j < p.A && j != i && (!h.upper || j > i))) continue;
+                const uint32_t compared = cmp[r][c], differ = cmp[r][c] - eq[r][c];
+                if (compared < kDistsHistWindow) atomicAdd(&s_compared[compared], 1u);
+                else atomicAdd(&h.compared_hist[compared], 1ull);
+                if (compared < h.min_compared) continue;
+                if (differ < kDistsHistWindow) atomicAdd(&s_differ[differ], 1u);
+                else atomicAdd(&h.differ_hist[differ], 1ull);
+            }
+        }
+        if (++bx == C) {
+            ++by;
+            bx = h.upper ? q0 + by : 0;
+        }
+    }
+    __syncthreads();
+    const uint32_t in_lds = p.L < kDistsHistWindow ? p.L + 1u : kDistsHistWindow;   // the bins there are, of those kept here
+    for (uint32_t b = threadIdx.x; b < in_lds; b += kBlock) {
+        const uint32_t nd = s_differ[b], nc = s_compared[b];
+        if (nd) atomicAdd(&h.differ_hist[b], (unsigned long long)nd);
+        if (nc) atomicAdd(&h.compared_hist[b], (unsigned long long)nc);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // launchers
 
@@ -403,6 +480,20 @@ hipError_t launch_dists_closest_merge(const unsigned long long *in, unsigned lon
     const uint64_t n_groups = (n_lists + kWave - 1) / kWave, blocks = (n_rows * n_groups + kBlock / kWave - 1) / (kBlock / kWave);
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_dists_closest_merge, dim3((unsigned)blocks), dim3(kBlock), 0, stream, in, out, n_rows, n_lists, n_groups, k);
+    return hipGetLastError();
+}
+
+hipError_t launch_dists_hist(const DistsParams &p, DistsHistParams h, int n_cu, hipStream_t stream) {
+    if (p.n_rows == 0 || p.A == 0 || p.L == 0) return hipSuccess;
+    if ((uint64_t)p.row0 + p.n_rows > p.A || h.min_compared == 0 || !h.differ_hist || !h.compared_hist || n_cu <= 0) return hipErrorInvalidValue;
+    const uint64_t C = p.Ap / kDistsTile, R = ((uint64_t)p.n_rows + kDistsTile - 1) / kDistsTile;
+    const uint64_t n0 = C - ((uint64_t)p.row0 + 1u) / kDistsTile;   // upper: the tiles of the first row tile, one fewer each row tile down
+    h.n_tiles = h.upper ? R * n0 - R * (R - 1) / 2 : R * C;
+    if (h.n_tiles == 0) return hipSuccess;                          // (upper, and the one row is A - 1 = 64 C - 1)
+    const uint64_t grid = std::max(std::min<uint64_t>(h.n_tiles, (uint64_t)n_cu * kDistsHistBlocksPerCu),
+                                   (h.n_tiles + kDistsHistMaxShare - 1) / kDistsHistMaxShare);
+    if (grid > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dists_hist, dim3((unsigned)grid), dim3(kBlock), 0, stream, p, h);
     return hipGetLastError();
 }
 

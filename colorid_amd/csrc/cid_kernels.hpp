@@ -358,6 +358,20 @@ struct DistsClosestParams {
 hipError_t launch_dists_closest(const DistsParams &p, DistsClosestParams q, hipStream_t stream);
 hipError_t launch_dists_closest_merge(const unsigned long long *in, unsigned long long *out, uint64_t n_rows, uint64_t n_lists, uint32_t k,
                                       hipStream_t stream);
+// The two histograms over the same arrays (p's differ and compared are not read): every pair (i in [row0, row0 + n_rows), j < A, j != i)
+// — upper: also j > i — adds 1 to compared_hist[compared] and, when compared >= min_compared (>= 1), 1 to differ_hist[differ]; both are
+// L + 1 u64 that the caller has set to 0.  Any number of rows a launch: the grid is one-dimensional, at most kDistsHistBlocksPerCu
+// workgroups a CU (n_cu: the device's), each with a contiguous share of the tiles that hold a pair — in upper mode those not wholly on
+// or below the diagonal — of at most kDistsHistMaxShare tiles: with more tiles than that the grid grows instead.
+struct DistsHistParams {
+    unsigned long long *differ_hist, *compared_hist;   // [L + 1] each
+    uint32_t min_compared, upper;
+    uint64_t n_tiles;                                  // (filled in by the launcher)
+};
+constexpr uint32_t kDistsHistWindow = 4096;            // bins 0 .. 4095 of either histogram are counted in LDS, the bins above in place
+constexpr uint32_t kDistsHistBlocksPerCu = 3;          // what 16 KiB of walk + 2 x 16 KiB of bins leave room for in a CU's 160 KiB of LDS
+constexpr uint64_t kDistsHistMaxShare = 0xFFFFFFFFull / (64 * 64);   // tiles a workgroup may own: 4 096 pairs a tile and no u32 bin wraps
+hipError_t launch_dists_hist(const DistsParams &p, DistsHistParams h, int n_cu, hipStream_t stream);
 hipError_t launch_get_rows(const uint64_t *mat, uint32_t rs, const uint64_t *d_row_ids, uint32_t *d_words, uint32_t w32,
                            uint64_t n_rows, hipStream_t stream);
 hipError_t launch_insert_kmers(const InsertParams &p, hipStream_t stream);

@@ -481,15 +481,24 @@ struct AlleleCodes {
 // With closest = K (1 .. CID_DISTS_CLOSEST_MAX), after that, PREFIX.closest.tsv: accession, neighbour, differ, compared — the accessions
 // in table order, under each its up to K nearest (cid_dists_closest: the others with compared >= min_compared and, with within,
 // differ <= within_threshold; fewer differing loci first, then more shared loci, then table order), or one line of dashes.
+// With hist, after that, PREFIX.hist.tsv: loci, differ_pairs, differ_cumulative, compared_pairs — one line per n = 0 .. L: the unordered
+// pairs with compared >= min_compared and differ = n, their running sum, and the unordered pairs with compared = n
+// (cid_dists_hist(CID_DISTS_UPPER) over all rows: 16 bytes a line leave the device).
+// With levels (coarse to fine, 1 .. kDistsMaxLevels of them), before the forest's files, PREFIX.levels.tsv: accession, one column T<t> per
+// level = the `cluster` column of PREFIX.clusters.tsv at threshold t, and address = those numbers joined by '.'; from the edges of the
+// one cid_dists_forest call that mst takes its files from.
+constexpr size_t kDistsMaxLevels = 32;
 struct DistsOptions {
     bool cluster = false;
     uint64_t threshold = 0;      // --cluster T
     uint64_t min_compared = 1;   // --min-compared M (for --cluster, --mst and --within)
     bool mst = false;            // --mst
-    bool no_matrices = false;    // --no-matrices (the caller refuses it without mst, cluster or within)
+    bool no_matrices = false;    // --no-matrices (the caller refuses it without mst, cluster, within, closest, hist or levels)
     bool within = false;
     uint64_t within_threshold = 0;   // --within T
     uint32_t closest = 0;            // --closest K (0: not asked for)
+    bool hist = false;               // --hist
+    std::vector<uint64_t> levels;    // --levels T1,T2,..: descending, no value twice (empty: not asked for)
 };
 void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, const DistsOptions &opt, void (*phase)(const char *) = nullptr);
 // `dists --query` (t, q from AlleleCodes::from_files; opt.within_threshold and opt.min_compared): PREFIX.query.tsv — query, neighbour, in

@@ -23,6 +23,16 @@
 //                the order of PREFIX.query.tsv; an accession without one gets a line of dashes: cid_dists_closest, K x 16 bytes an
 //                accession over the bus.  With --query it cuts every query accession's list in PREFIX.query.tsv to its first K lines,
 //                and --within is then optional: without it the K nearest however far they are
+//   PREFIX.hist.tsv (--hist [--min-compared M])   loci, differ_pairs, differ_cumulative, compared_pairs: one line for every n = 0 .. L, the
+//                empty ones too: the unordered pairs with compared >= M and differ = n, the running sum of that column (= the lines
+//                --within n would write), and the unordered pairs of all accessions with compared = n (whatever M is; n = 0: no common
+//                locus): cid_dists_hist(CID_DISTS_UPPER) over all rows, 16 bytes a line over the bus.  A table without accessions or
+//                loci gets L + 1 lines of zeros
+//   PREFIX.levels.tsv (--levels T1,T2,.. [--min-compared M], 1 .. 32 thresholds)   accession, one column T<t> per threshold from the
+//                largest t to the smallest, address: in table order, every accession's cluster at each threshold — the `cluster` column
+//                of PREFIX.clusters.tsv from --cluster t: single linkage, numbered from 1 in order of the first member — and the
+//                numbers joined by '.'.  The levels nest.  From the edges of ONE cid_dists_forest call (the one --mst writes), a
+//                union-find over them in key order, read off at each threshold: no row leaves the device
 //   --no-matrices   the two A x A files are not made; rows are then fetched for --cluster only
 #include "colorid_host.hpp"
 
@@ -156,6 +166,58 @@ void write_forest(const std::vector<std::string> &names, const std::vector<cid_d
     dists_close(fn, n_path);
     fprintf(stderr, "dists: minimum spanning forest: %zu trees, %zu edges, total length %llu, written to %s, %s\n", A - edges.size(), edges.size(),
             total, t_path.c_str(), n_path.c_str());
+}
+
+// PREFIX.levels.tsv from the forest's edges (in edge-key order, so by differ ascending): the edges of at most t span the clusters at t, so
+// one union-find takes the edges in that order and is read off at every threshold on the way, finest first.  The smaller root stays the
+// root: a cluster's root is its first member, and numbering the roots as the accessions come by is numbering the clusters from 1 in
+// order of their first member.  levels: descending.  Host memory: 4 bytes an accession and level.
+void write_levels(const std::vector<std::string> &names, const std::vector<cid_dists_edge> &edges, const std::vector<uint64_t> &levels,
+                  uint64_t min_compared, const std::string &prefix) {
+    const size_t A = names.size(), n_levels = levels.size();
+    std::vector<uint32_t> parent(A), number(A), of(A * n_levels);   // of[i * n_levels + k]: accession i's cluster at levels[k]
+    std::iota(parent.begin(), parent.end(), 0u);
+    auto find = [&](uint32_t x) {
+        while (parent[x] != x) { parent[x] = parent[parent[x]]; x = parent[x]; }
+        return x;
+    };
+    std::vector<uint32_t> n_clusters(n_levels, 0);
+    size_t e = 0;
+    for (size_t k = n_levels; k-- > 0;) {
+        for (; e < edges.size() && edges[e].differ <= levels[k]; ++e) {
+            const uint32_t a = find(edges[e].a), b = find(edges[e].b);
+            if (a != b) parent[std::max(a, b)] = std::min(a, b);
+        }
+        std::fill(number.begin(), number.end(), 0u);
+        for (size_t i = 0; i < A; ++i) {
+            const uint32_t root = find((uint32_t)i);
+            if (!number[root]) number[root] = ++n_clusters[k];
+            of[i * n_levels + k] = number[root];
+        }
+    }
+    const std::string l_path = prefix + ".levels.tsv";
+    FILE *fl = dists_out(l_path);
+    std::string line = "accession", said;
+    for (size_t k = 0; k < n_levels; ++k) {
+        line += "\tT" + std::to_string(levels[k]);
+        said += (k ? ", " : "") + std::to_string(n_clusters[k]) + " at <= " + std::to_string(levels[k]);
+    }
+    line += "\taddress\n";
+    fputs(line.c_str(), fl);
+    for (size_t i = 0; i < A; ++i) {
+        line = names[i];
+        std::string address;
+        for (size_t k = 0; k < n_levels; ++k) {
+            const std::string n = std::to_string(of[i * n_levels + k]);
+            line += '\t' + n;
+            address += (k ? "." : "") + n;
+        }
+        line += '\t' + address + '\n';
+        fwrite(line.data(), 1, line.size(), fl);
+    }
+    dists_close(fl, l_path);
+    fprintf(stderr, "dists: cluster addresses of %zu accessions (at least %llu shared): %s differing loci, written to %s\n", A,
+            (unsigned long long)min_compared, said.c_str(), l_path.c_str());
 }
 
 }  // namespace
@@ -482,6 +544,25 @@ void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, co
         fprintf(stderr, "dists: %zu accessions, the %u closest of each%s (at least %llu shared): %llu lines, %zu accessions without a neighbour, written to %s\n",
                 A, opt.closest, bound.c_str(), (unsigned long long)min_compared, (unsigned long long)n_lines, without, n_path.c_str());
     }
+    if (opt.hist) {
+        const std::string h_path = prefix + ".hist.tsv";
+        std::vector<uint64_t> differ_hist(L + 1, 0), compared_hist(L + 1, 0);
+        if (d && cid_dists_hist(d, 0, (uint32_t)A, (uint32_t)std::min<uint64_t>(min_compared, 0xFFFFFFFFull), CID_DISTS_UPPER, differ_hist.data(),
+                                compared_hist.data()) != CID_OK)
+            die("cid_dists_hist: %s", cid_last_error());
+        FILE *fh = dists_out(h_path);
+        fputs("loci\tdiffer_pairs\tdiffer_cumulative\tcompared_pairs\n", fh);
+        unsigned long long within = 0, pairs = 0;
+        for (size_t n = 0; n <= L; ++n) {
+            within += differ_hist[n];
+            pairs += compared_hist[n];
+            fprintf(fh, "%zu\t%llu\t%llu\t%llu\n", n, (unsigned long long)differ_hist[n], within, (unsigned long long)compared_hist[n]);
+        }
+        dists_close(fh, h_path);
+        if (phase) phase("pairs counted and written");
+        fprintf(stderr, "dists: %llu pairs counted, %llu of them left out of the differ columns for sharing fewer than %llu loci, written to %s\n", pairs,
+                pairs - within, (unsigned long long)min_compared, h_path.c_str());
+    }
     if (opt.cluster) {
         std::vector<uint32_t> size(A, 0), number(A, 0);
         for (size_t i = 0; i < A; ++i) ++size[find((uint32_t)i)];
@@ -504,7 +585,7 @@ void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, co
         fprintf(stderr, "dists: %zu clusters of 2 or more at <= %llu differing loci hold %zu accessions, written to %s\n", n_multi,
                 (unsigned long long)opt.threshold, in_multi, k_path.c_str());
     }
-    if (opt.mst) {
+    if (opt.mst || !opt.levels.empty()) {
         // (more than L shared loci are asked of no pair: the forest is then A single accessions, as it is without a locus)
         std::vector<cid_dists_edge> edges(d && min_compared <= L ? A - 1 : 0);
         if (!edges.empty()) {
@@ -512,8 +593,14 @@ void dists_run(cid_ctx *ctx, const AlleleCodes &t, const std::string &prefix, co
             if (cid_dists_forest(d, (uint32_t)min_compared, edges.data(), &n_edges, &n_rounds) != CID_OK) die("cid_dists_forest: %s", cid_last_error());
             edges.resize(n_edges);
         }
-        write_forest(t.accessions, edges, prefix);
-        if (phase) phase("minimum spanning forest computed and written");
+        if (!opt.levels.empty()) {
+            write_levels(t.accessions, edges, opt.levels, min_compared, prefix);
+            if (phase) phase("minimum spanning forest computed and cluster addresses written");
+        }
+        if (opt.mst) {
+            write_forest(t.accessions, edges, prefix);
+            if (phase) phase(opt.levels.empty() ? "minimum spanning forest computed and written" : "minimum spanning forest written");
+        }
     }
     if (d) cid_dists_destroy(d);
 }

@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <thread>
 #include <unistd.h>
 
@@ -653,16 +654,43 @@ uint32_t closest_arg(const Args &a) {
             CID_DISTS_CLOSEST_MAX, v.c_str());
     return (uint32_t)n;
 }
-// what --cluster, --within, --closest, --min-compared, --mst and --no-matrices ask for; refuses --min-compared without --cluster, --mst,
-// --within or --closest, and --no-matrices when nothing else would be written
+// --levels T1,T2,.. (search --dists, dists): 1 .. kDistsMaxLevels different numbers of loci, in any order; returned coarse to fine
+std::vector<uint64_t> levels_arg(const Args &a) {
+    const std::string &v = a.values.at("levels")[0];
+    std::vector<uint64_t> levels;
+    bool ok = !v.empty();
+    for (size_t at = 0; ok && at <= v.size();) {
+        const size_t comma = std::min(v.find(',', at), v.size());
+        const std::string item = v.substr(at, comma - at);
+        char *end = nullptr;
+        errno = 0;
+        const unsigned long long n = strtoull(item.c_str(), &end, 10);
+        ok = !item.empty() && item.find_first_not_of("0123456789") == std::string::npos && !*end && !errno &&
+             std::find(levels.begin(), levels.end(), (uint64_t)n) == levels.end() && levels.size() < kDistsMaxLevels;
+        levels.push_back((uint64_t)n);
+        at = comma + 1;
+    }
+    if (!ok)
+        die("error: --levels expects 1 to %zu different numbers of loci (0 or more) separated by commas, as in 0,2,7, got '%s'", kDistsMaxLevels,
+            v.c_str());
+    std::sort(levels.begin(), levels.end(), std::greater<uint64_t>());
+    return levels;
+}
+// what --cluster, --within, --closest, --hist, --levels, --min-compared, --mst and --no-matrices ask for; refuses --min-compared without
+// --cluster, --mst, --within, --closest, --hist or --levels, and --no-matrices when nothing else would be written
 DistsOptions dists_options(const Args &a) {
     DistsOptions o;
     o.mst = a.flags.count("mst") != 0;
     o.no_matrices = a.flags.count("no-matrices") != 0;
-    if (a.has("min-compared") && !a.has("cluster") && !o.mst && !a.has("within") && !a.has("closest"))
-        die("error: --min-compared needs --cluster T (it is the least number of loci two accessions must share to be linked), --mst or --within T, or --closest K");
-    if (o.no_matrices && !a.has("cluster") && !o.mst && !a.has("within") && !a.has("closest"))
-        die("error: --no-matrices needs --mst or --cluster T or --within T (without the two matrices nothing would be written), or --closest K");
+    o.hist = a.flags.count("hist") != 0;
+    const bool levels = a.values.count("levels") != 0;   // (an empty list is refused as a list, not overlooked)
+    if (a.has("min-compared") && !a.has("cluster") && !o.mst && !a.has("within") && !a.has("closest") && !o.hist && !levels)
+        die("error: --min-compared needs --cluster T (it is the least number of loci two accessions must share to be linked), --mst or --within T, or --closest K, "
+            "--hist or --levels T1,T2,..");
+    if (o.no_matrices && !a.has("cluster") && !o.mst && !a.has("within") && !a.has("closest") && !o.hist && !levels)
+        die("error: --no-matrices needs --mst or --cluster T or --within T (without the two matrices nothing would be written), or --closest K, --hist or "
+            "--levels T1,T2,..");
+    if (levels) o.levels = levels_arg(a);
     if (a.has("closest")) o.closest = closest_arg(a);
     if (a.has("cluster")) { o.cluster = true; o.threshold = loci_arg(a, "cluster"); }
     if (a.has("within")) { o.within = true; o.within_threshold = loci_arg(a, "within"); }
@@ -689,7 +717,8 @@ int cmd_search(int argc, char **argv) {
                                                      {0, "nearest", false, false}, {0, "dists", false, false},
                                                      {0, "cluster", true, false}, {0, "min-compared", true, false},
                                                      {0, "mst", false, false}, {0, "no-matrices", false, false}, {0, "within", true, false},
-                                                     {0, "closest", true, false}, {0, "gather", true, false}, {0, "gather-min", true, false}, {0, "gather-max", true, false}}));
+                                                     {0, "closest", true, false}, {0, "hist", false, false}, {0, "levels", true, false},
+                                                     {0, "gather", true, false}, {0, "gather-min", true, false}, {0, "gather-max", true, false}}));
     for (const char *req : {"bigsi", "query"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     const std::vector<std::string> files1 = a.values.at("query");
@@ -729,15 +758,18 @@ int cmd_search(int argc, char **argv) {
         if (a.has("gpus") || a.has("devices") || a.has("placement") || cli_env("COLORID_REDUCE"))
             die("error: --nearest runs on one GPU: it does not go with --gpus, --devices, --placement or COLORID_REDUCE");
     }
-    // -s -m --alleles PREFIX --dists [--cluster T] [--within T] [--closest K] [--mst] [--min-compared M] [--no-matrices]: after the tables,
-    // the pairwise allele distances of the raw table's accessions (the clean table's with --max-missing), the pairs within T, every
-    // accession's K nearest, their clusters and their minimum spanning forest, on this run's context: the files `colorid dists -t PREFIX.raw.tsv` writes.  Refused here, before the GPU context is made
+    // -s -m --alleles PREFIX --dists [--cluster T] [--within T] [--closest K] [--hist] [--levels T1,T2,..] [--mst] [--min-compared M]
+    // [--no-matrices]: after the tables, the pairwise allele distances of the raw table's accessions (the clean table's with
+    // --max-missing), the pairs within T, every accession's K nearest, the pairs counted by distance, their clusters at one threshold
+    // or several and their minimum spanning forest, on this run's context: the files `colorid dists -t PREFIX.raw.tsv` writes.  Refused here, before the GPU context is made
     const bool dists = a.flags.count("dists") != 0;
     if (dists && !a.has("alleles")) die("error: --dists needs -s -m --alleles PREFIX (it writes PREFIX.dists.tsv from the allele table)");
     if (!dists && a.has("cluster")) die("error: --cluster needs --dists (it clusters the allele distances)");
     if (!dists && a.has("within")) die("error: --within needs --dists (it lists the pairs of accessions at most T alleles apart)");
     if (!dists && a.has("closest")) die("error: --closest needs --dists (it lists every accession's K nearest by allele distance)");
     if (!dists && a.flags.count("mst")) die("error: --mst needs --dists (it is the minimum spanning forest of the allele distances)");
+    if (!dists && a.flags.count("hist")) die("error: --hist needs --dists (it counts the pairs of accessions by their allele distance)");
+    if (!dists && a.values.count("levels")) die("error: --levels needs --dists (it clusters the allele distances at several thresholds)");
     if (!dists && a.flags.count("no-matrices")) die("error: --no-matrices needs --dists (it leaves out PREFIX.dists.tsv and PREFIX.compared.tsv)");
     const DistsOptions dists_opt = dists_options(a);
     // -g -m --coverage: where on each record an accession hits (cid_search_cover).  FASTA records on one GPU; everything else is refused
@@ -843,11 +875,13 @@ int cmd_alleles(int argc, char **argv) {
 // among TABLE's and each other, the loci matched by name; a query table without accessions needs no GPU.
 // --closest K (1 .. 64, checked with the flags): every accession's K nearest — PREFIX.closest.tsv, within T where --within is given too —
 // and with --query, where it may stand in for --within, the first K lines of every query accession's list.
+// --hist: PREFIX.hist.tsv, the unordered pairs counted by differ and by compared; --levels T1,T2,.. (1 .. 32 of them, checked with the
+// flags): PREFIX.levels.tsv, every accession's cluster at each threshold.  Neither goes with --query.
 int cmd_dists(int argc, char **argv) {
     const Args a = parse(argc, argv, 2, {{'t', "table", true, false}, {'o', "output", true, false}, {0, "cluster", true, false},
                                          {0, "min-compared", true, false}, {0, "mst", false, false}, {0, "no-matrices", false, false},
                                          {0, "within", true, false}, {0, "closest", true, false}, {0, "query", true, false},
-                                         {0, "device", true, false}});
+                                         {0, "hist", false, false}, {0, "levels", true, false}, {0, "device", true, false}});
     for (const char *req : {"table", "output"})
         if (!a.has(req)) die("error: The following required arguments were not provided: --%s", req);
     if (a.has("query")) {
@@ -856,6 +890,8 @@ int cmd_dists(int argc, char **argv) {
         if (a.has("cluster")) die("error: --query writes PREFIX.query.tsv alone and does not go with --cluster");
         if (a.flags.count("mst")) die("error: --query writes PREFIX.query.tsv alone and does not go with --mst");
         if (a.flags.count("no-matrices")) die("error: --query writes PREFIX.query.tsv alone and does not go with --no-matrices (no matrix is made)");
+        if (a.flags.count("hist")) die("error: --query writes PREFIX.query.tsv alone and does not go with --hist");
+        if (a.values.count("levels")) die("error: --query writes PREFIX.query.tsv alone and does not go with --levels");
     }
     const DistsOptions opt = dists_options(a);
     if (a.has("query")) {
@@ -1200,8 +1236,15 @@ int main(int argc, char **argv) {
                "                             compared: under every accession its K (1 .. 64) nearest among those that share at least M (1) loci\n"
                "                             with it (and differ at no more than T), fewest differing loci first, then most shared loci, then\n"
                "                             table order; a line of - for none; found on the GPU, no matrix is made (goes with --no-matrices)\n"
+               "                             --dists --hist [--min-compared M]: PREFIX.hist.tsv, loci, differ_pairs, differ_cumulative,\n"
+               "                             compared_pairs: for n = 0 .. the number of loci, the unordered pairs that share at least M (1) loci\n"
+               "                             and differ at exactly n, their running sum (the lines --within n would write), and the pairs that\n"
+               "                             share exactly n loci: where to put T and M; counted on the GPU (goes with --no-matrices)\n"
+               "                             --dists --levels T1,T2,.. [--min-compared M]: PREFIX.levels.tsv, accession, one column T<t> per\n"
+               "                             threshold (1 .. 32 of them, coarse to fine) = the cluster column of --cluster t, and address, the\n"
+               "                             numbers joined by '.': all from the one minimum spanning forest (goes with --no-matrices)\n"
                "    dists -t TABLE -o PREFIX [--cluster T] [--mst] [--min-compared M] [--no-matrices]   the same files from a table in the form\n"
-               "                             of PREFIX.raw.tsv; [--within T] [--closest K] as above\n"
+               "                             of PREFIX.raw.tsv; [--within T] [--closest K] [--hist] [--levels T1,T2,..] as above\n"
                "    dists -t TABLE --query TABLE2 -o PREFIX --within T [--min-compared M]   PREFIX.query.tsv alone: for every accession of TABLE2\n"
                "                             the accessions of TABLE and of TABLE2 within T, nearest first (query, neighbour, in = table or\n"
                "                             query, differ, compared; a line of - for none); loci are matched by name: TABLE's are used, one that\n"

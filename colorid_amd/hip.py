@@ -477,6 +477,17 @@ class Dists:
         check(self.lib.cid_dists_closest(self.h, row0, n_rows, k, max_differ, min_compared, _p(buf)))
         return out
 
+    def hist(self, min_compared=1, row0=0, n_rows=None, upper=False):
+        """the pairs counted (cid_dists_hist) -> (differ_hist, compared_hist), each n_loci + 1 uint64: over the pairs (a in [row0, row0 +
+        n_rows), b != a) — upper: b > a only — compared_hist[n] = those that share n loci, differ_hist[n] = those that share at least
+        min_compared and differ at n"""
+        if n_rows is None:
+            n_rows = self.n_acc - row0
+        differ = np.zeros(self.n_loci + 1, np.uint64)
+        comp = np.zeros(self.n_loci + 1, np.uint64)
+        check(self.lib.cid_dists_hist(self.h, row0, n_rows, min_compared, 1 if upper else 0, _p(differ), _p(comp)))
+        return differ, comp
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.cid_dists_destroy(self.h)

@@ -254,6 +254,17 @@ int cid_dists_within(cid_dists *, uint32_t row0, uint32_t n_rows, uint32_t max_d
 #define CID_DISTS_CLOSEST_MAX 64u
 int cid_dists_closest(cid_dists *, uint32_t row0, uint32_t n_rows, uint32_t k, uint32_t max_differ, uint32_t min_compared,
                       cid_dists_edge *out /* n_rows x k */);
+/* The pairs counted (`dists --hist`): every pair {a in [row0, row0 + n_rows), b in [0, n_acc), b != a} — with CID_DISTS_UPPER also b > a,
+ * so that a call over all rows counts every unordered pair once — adds 1 to compared_hist[compared(a, b)], whatever min_compared is (bin
+ * 0: the pairs without a common locus), and, when compared(a, b) >= min_compared (>= 1), 1 to differ_hist[differ(a, b)].  Both have the
+ * bins 0 .. n_loci, n_loci + 1 of them; compared_hist may be NULL.  So sum(compared_hist) is the number of pairs, sum(differ_hist) =
+ * sum(compared_hist[min_compared ..]), and the running sum of differ_hist at T is *n_found of cid_dists_within(max_differ = T) with the
+ * same rows, min_compared and flags.  The counts are integers: the same bytes on every call, however the device splits the work.
+ * n_rows == 0 gives two histograms of zeros.  Every pair is visited on the device and 16 bytes a bin come back: no A x A matrix exists
+ * anywhere, the rows are not sliced, device memory beside the table is 16 bytes a bin.
+ * CID_ERR_INVALID: null handle or differ_hist, min_compared == 0, row0 + n_rows > n_acc, unknown flag bits. */
+int cid_dists_hist(cid_dists *, uint32_t row0, uint32_t n_rows, uint32_t min_compared, uint32_t flags,
+                   uint64_t *differ_hist /* n_loci + 1 */, uint64_t *compared_hist /* n_loci + 1; may be NULL */);
 void cid_dists_destroy(cid_dists *);
 
 /* ---- a5: proportional search, the hot loop of batch_search_pe::batch_search

@@ -1,11 +1,13 @@
 // Stand-alone host check of colorid_amd/csrc/host/dists.cpp under ASan + UBSan, no GPU and no libcolorid_hip.so: the table parser, the
 // allele encoder (both entrances), the row-block driver, the clustering and the forest and Newick writers, with a plain C++ cid_dists_*
 // behind them (the forest: Kruskal over the stand-in's own loop; the neighbour list: the same loop, filtered; the K nearest: the same
-// loop, sorted and cut).
-//   make -C tools bin/dists_host_check ;  tools/bin/dists_host_check TABLE PREFIX [T [M [mst [no-matrices]]]] [within=T] [closest=K] [query=TABLE2]
+// loop, sorted and cut; the histograms: the same loop, counted).
+//   make -C tools bin/dists_host_check ;  tools/bin/dists_host_check TABLE PREFIX [T [M [mst [no-matrices]]]] [within=T] [closest=K] [hist]
+//   [levels=T1,T2,..] [query=TABLE2]
 //   (writes PREFIX.dists.tsv, .compared.tsv, .clusters.tsv; T = - for no clusters; with mst also PREFIX.mst.tsv, .mst.nwk; with within=T
-//   also PREFIX.within.tsv; with closest=K also PREFIX.closest.tsv; with query=TABLE2 — and within=T or closest=K — PREFIX.query.tsv
-//   alone, the two tables aligned by AlleleCodes::from_files)
+//   also PREFIX.within.tsv; with closest=K also PREFIX.closest.tsv; with hist also PREFIX.hist.tsv; with levels= also PREFIX.levels.tsv
+//   (the thresholds as given: put them in descending order); with query=TABLE2 — and within=T or closest=K — PREFIX.query.tsv alone,
+//   the two tables aligned by AlleleCodes::from_files)
 #include <algorithm>
 #include <cstdarg>
 #include <numeric>
@@ -119,6 +121,21 @@ int cid_dists_closest(cid_dists *d, uint32_t row0, uint32_t n, uint32_t k, uint3
     }
     return 0;
 }
+// the pairs of the loop above, counted by compared and — with compared >= min_compared — by differ
+int cid_dists_hist(cid_dists *d, uint32_t row0, uint32_t n, uint32_t min_compared, uint32_t flags, uint64_t *differ_hist, uint64_t *compared_hist) {
+    std::vector<uint32_t> differ(d->A), compared(d->A);
+    std::fill(differ_hist, differ_hist + d->L + 1, (uint64_t)0);
+    if (compared_hist) std::fill(compared_hist, compared_hist + d->L + 1, (uint64_t)0);
+    for (uint32_t i = row0; i < row0 + n; ++i) {
+        cid_dists_rows(d, i, 1, differ.data(), compared.data());
+        for (uint32_t j = (flags & CID_DISTS_UPPER) ? i + 1 : 0; j < d->A; ++j) {
+            if (j == i) continue;
+            if (compared_hist) ++compared_hist[compared[j]];
+            if (compared[j] >= min_compared) ++differ_hist[differ[j]];
+        }
+    }
+    return 0;
+}
 void cid_dists_destroy(cid_dists *d) { delete d; }
 }
 
@@ -126,10 +143,17 @@ int main(int argc, char **argv) {
     using namespace colorid;
     DistsOptions o;
     std::string query;
-    int kept = 1;   // within=T, closest=K and query=TABLE2 come out of the positional arguments
+    int kept = 1;   // within=T, closest=K, hist, levels=.. and query=TABLE2 come out of the positional arguments
     for (int i = 1; i < argc; ++i) {
         if (strncmp(argv[i], "within=", 7) == 0) { o.within = true; o.within_threshold = strtoull(argv[i] + 7, nullptr, 10); }
         else if (strncmp(argv[i], "closest=", 8) == 0) o.closest = (uint32_t)strtoul(argv[i] + 8, nullptr, 10);
+        else if (strcmp(argv[i], "hist") == 0) o.hist = true;
+        else if (strncmp(argv[i], "levels=", 7) == 0)
+            for (const char *p = argv[i] + 7; *p;) {
+                char *end = nullptr;
+                o.levels.push_back(strtoull(p, &end, 10));
+                p = *end ? end + 1 : end;
+            }
         else if (strncmp(argv[i], "query=", 6) == 0) query = argv[i] + 6;
         else argv[kept++] = argv[i];
     }
